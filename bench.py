@@ -17,6 +17,14 @@ Configs 3-5 shard ONE batch over the ranks (strong scaling, contiguous ranges: h
 One "step" = one traverse_grid call over this rank's rays, resident in HBM.  The grid is built on rank 0 with the gfx950
 construction passes and broadcast once (RCCL); no collective sits on the timed path.  Rank 0 prints ONE JSON line.
 
+A plain run does what the headline needs: scene, grid (with `build_ms`, the mean of --build-iter timed constructions), rays,
+traversal setup, the warm-up and the K timed steps, and the line (`value`, `ms_per_step`, `build_ms`, the configuration).
+--full adds everything else the line used to carry, each outside the timed region: the statistics pass (`hit_fraction`,
+algorithmic bytes), the roofline blocks, the default tile order and moving-camera loops (`tile_order`), calls in flight
+(`pipelined`), the critical path, the measured copy bandwidth, `memory`, and on one rank the CPU baseline with its parity check.
+--dump-outputs DIR writes the hits of the last timed step (rank 0's rays) as DIR/hits_{id,t,u,v}.npy + DIR/ray_index.npy:
+every ray up to 2M rays, above that a fixed, seeded sample of 2M (about 56 MB in all).
+
 Everything measured runs through the C ABI (hagrid_amd/libhagrid_amd.so).  The CPU oracle is used only (a) as the checker
 of the GPU hits and (b) as the timed `cpu_baseline` (rank 0, N = 1), never as the thing measured.
 """
@@ -141,6 +149,35 @@ def upload_generated(mem, d_rays, gen, first, count, chunk=1 << 20, threads=None
     return np.concatenate(kept) if kept else np.zeros((0, 8), np.float32)
 
 
+DUMP_MAX_RAYS = 1 << 21         # 28 bytes per ray dumped: at most 56 MB
+
+
+def dump_hits(mem, d_hits, n_rays, out_dir):
+    """The hits a caller of traverse_grid receives, as DIR/hits_id.npy (float64: every int32 id exactly, -1 = no hit), hits_t / hits_u /
+    hits_v.npy (float32) and ray_index.npy (float64: the ray each row belongs to).  Up to DUMP_MAX_RAYS rays all of them, above that the same
+    seeded sample of DUMP_MAX_RAYS indices on every run, in ascending order."""
+    from hagrid_amd import api
+    os.makedirs(out_dir, exist_ok=True)
+    if n_rays <= DUMP_MAX_RAYS:
+        idx = np.arange(n_rays, dtype=np.int64)
+        hits = mem.download(d_hits, api.HIT_DTYPE, n_rays)
+    else:
+        idx = np.sort(np.random.default_rng(20240611).choice(n_rays, DUMP_MAX_RAYS, replace=False))
+        hits = np.empty(DUMP_MAX_RAYS, api.HIT_DTYPE)
+        chunk = 1 << 22                                  # download in slices: the whole buffer of a large batch is gigabytes
+        for lo in range(0, n_rays, chunk):
+            hi = min(lo + chunk, n_rays)
+            a, b = np.searchsorted(idx, [lo, hi])
+            if b > a:
+                part = mem.download(d_hits + 16 * lo, api.HIT_DTYPE, hi - lo)
+                hits[a:b] = part[idx[a:b] - lo]
+    np.save(os.path.join(out_dir, "ray_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "hits_id.npy"), hits["id"].astype(np.float64))
+    for f in ("t", "u", "v"):
+        np.save(os.path.join(out_dir, f"hits_{f}.npy"), np.ascontiguousarray(hits[f], dtype=np.float32))
+    log(f"[bench] dumped the hits of {len(idx)} of {n_rays} rays to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -177,6 +214,10 @@ def main():
     ap.add_argument("--shard", default=None, metavar="R/W", help="one GPU, strong scaling only: trace the contiguous range rank R of W ranks would get (the per-GPU share of an 8-GPU run, "
                     "e.g. --config 4 --shard 3/8 = 16M of the 128M rays); `value` is then this GPU's rate on that share, the line says so in config.shard")
     ap.add_argument("--force-dist", action="store_true", help="run the multi-rank code path (process group, broadcast, all-reduce) even with one rank")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline, outside the timed steps: statistics pass, roofline, tile-order and "
+                    "moving-camera loops, calls in flight, critical path, copy bandwidth, memory, CPU baseline + parity (the --no-cpu-baseline, "
+                    "--no-order-compare, --inflight and --cpu-seconds options refine it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the hits of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
 
     cfg = CONFIGS[args.config]
@@ -190,24 +231,26 @@ def main():
     expansion = args.expansion if args.expansion is not None else cfg["params"].get("expansion", 3)
     compress = args.compress or cfg["params"].get("compress", False)
 
-    import torch
-    import torch.distributed as dist
-    from hagrid_amd import api, scene, dist as hdist
-
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         if "WORLD_SIZE" not in os.environ and "RANK" not in os.environ and args.gpus > 1:
-            # started bare (`python bench.py --gpus N`, the shape of the driver's N = 1 command): become the launch line DESIGN.md section 7
-            # names -- one rank per GPU under torch.distributed.run -- instead of giving up; rank 0's JSON line is this process's stdout.
+            # started bare (`python bench.py --gpus N`, the shape of the driver's N = 1 command): run the launch line DESIGN.md section 7
+            # names -- one rank per GPU under torch.distributed.run -- as a child process, before anything here touches a GPU, instead of
+            # giving up; rank 0's JSON line is this process's stdout, the launcher's exit status this process's.
+            import subprocess
             port = os.environ.get("MASTER_PORT") or str(29600 + os.getpid() % 2000)
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                    "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
             log(f"[bench] --gpus {args.gpus} without a launcher: re-executing under torch.distributed.run (port {port})")
             sys.stdout.flush(); sys.stderr.flush()
-            os.execv(sys.executable, cmd)
+            raise SystemExit(subprocess.call(cmd))
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
+
+    import torch
+    import torch.distributed as dist
+    from hagrid_amd import api, scene, dist as hdist
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (there is no CPU fallback of the product path)")
     device = local_rank if args.device is None else args.device
@@ -255,12 +298,13 @@ def main():
             grid.free()
             times.append(api.profile(lambda: build(grid), mem))
         build_ms = float(np.mean(times)); build_ms_min = float(min(times))
-        bc = mem.build_counts()
-        bb = api.build_algorithmic_bytes(bc)
-        build_block = {"bytes": bb, "ms": round(build_ms, 3), "achieved": round(bb["total"] / (build_ms * 1e6), 1), "unit": "GB/s",
-                       "frac": round(bb["total"] / (build_ms * 1e6) / HBM_PEAK_GBPS, 4),
-                       "formula": "SURVEY.md 8(d) 'algorithmic bytes -- build' on the sizes the passes recorded (hagrid_get_build_counts)",
-                       "counts": {k: bc[k] for k in ("top_refs", "level_refs", "level_cells", "build_cells", "build_refs", "build_entries", "merge_passes", "merged_cells", "merged_refs", "flatten_entries_out")}}
+        if args.full:
+            bc = mem.build_counts()
+            bb = api.build_algorithmic_bytes(bc)
+            build_block = {"bytes": bb, "ms": round(build_ms, 3), "achieved": round(bb["total"] / (build_ms * 1e6), 1), "unit": "GB/s",
+                           "frac": round(bb["total"] / (build_ms * 1e6) / HBM_PEAK_GBPS, 4),
+                           "formula": "SURVEY.md 8(d) 'algorithmic bytes -- build' on the sizes the passes recorded (hagrid_get_build_counts)",
+                           "counts": {k: bc[k] for k in ("top_refs", "level_refs", "level_cells", "build_cells", "build_refs", "build_entries", "merge_passes", "merged_cells", "merged_refs", "flatten_entries_out")}}
         log(f"[bench] grid {grid.summary()} build_ms {build_ms:.2f} (min {min(times):.2f})")
     if multi:
         barrier(); t0 = time.perf_counter()
@@ -305,7 +349,7 @@ def main():
     for kv in filter(None, args.opts.split(",")):                 # experiments: any hagrid_set_option key
         k, v = kv.split("="); mem.set_option(k, int(v))
     api.setup_traversal(grid)                        # main.cpp:535; builds the traversal image (outside every timed region)
-    setup_ms = api.profile(lambda: api.setup_traversal(grid), mem)
+    setup_ms = api.profile(lambda: api.setup_traversal(grid), mem) if args.full else None
     if ray_kind == "bounce":
         # BASELINE config 5: diffuse-bounce rays leaving the primary hit points, in the image order of the primary rays
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n_rays)
@@ -324,9 +368,10 @@ def main():
     mem.set_ray_binning(bin_rays)
 
     # exact algorithmic byte counters of this batch (outside the timed region)
-    stats = api.traverse_grid_stats(grid, d_tris, d_rays, d_hits, n_rays)
     record_bytes = mem.image_record_bytes(grid) if args.image else 32
-    ab = api.algorithmic_bytes(stats, compressed, record_bytes)
+    if args.full:
+        stats = api.traverse_grid_stats(grid, d_tris, d_rays, d_hits, n_rays)
+        ab = api.algorithmic_bytes(stats, compressed, record_bytes)
 
     # ---- timed region: W warm-up steps, then exactly K steps between barrier + synchronize ------------------------------
     # the statistics pass and the host work above leave the GPU idle for a while; a short burst of the same step lets the clocks
@@ -347,18 +392,26 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0                                       # this rank's K steps; MAX over ranks below
     barrier()
-    sums = [ab["B_ray"], ab["B_walk"], stats["hits"], stats["rays_hit_grid"], n_rays, ab["B_image"]]
+    if rank == 0 and args.dump_outputs:          # what the last timed step left in the hit buffer, before anything else runs over it
+        dump_hits(mem, d_hits, n_rays, args.dump_outputs)
     if multi:
         t = torch.tensor([elapsed, kernel_ms_total], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms_total = float(t[0]), float(t[1])
-        s = torch.tensor(sums, dtype=torch.float64, device="cuda")
-        dist.all_reduce(s, op=dist.ReduceOp.SUM)
-        sums = [float(v) for v in s]
-    tot_bytes, tot_walk, tot_hits, tot_in, total_rays, tot_image = sums
-
-    n_head = rays_head.shape[0]
-    hits = mem.download(d_hits, api.HIT_DTYPE, n_head)
+    total_rays = n_rays                                                      # the job's rays: the sum over the ranks
+    if multi:
+        t = torch.tensor([float(n_rays)], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        total_rays = float(t[0])
+    if args.full:
+        sums = [ab["B_ray"], ab["B_walk"], stats["hits"], stats["rays_hit_grid"], n_rays, ab["B_image"]]
+        if multi:
+            s = torch.tensor(sums, dtype=torch.float64, device="cuda")
+            dist.all_reduce(s, op=dist.ReduceOp.SUM)
+            sums = [float(v) for v in s]
+        tot_bytes, tot_walk, tot_hits, tot_in, total_rays, tot_image = sums
+        n_head = rays_head.shape[0]
+        hits = mem.download(d_hits, api.HIT_DTYPE, n_head)
     hits_sha = None
     if args.hits_hash:      # (experiments: two libraries or two code paths over the same rays must leave the same bytes)
         import hashlib
@@ -370,7 +423,7 @@ def main():
     # reference's own benchmark loop measures (main.cpp:398-447: the same rays, iteration after iteration).  The same K steps in the default
     # order (= what the FIRST launch over a new buffer costs) are reported next to it.
     tile_order = None
-    if not bin_rays and not args.no_order_compare:
+    if args.full and not bin_rays and not args.no_order_compare:
         try:
             mem.set_option("traverse.tile_order", 0)
             for _ in range(max(args.warmup, 1)):
@@ -436,7 +489,7 @@ def main():
     # One launch over 1M rays keeps the machine full for half of its time, the rest is the drain of its last wavefronts.  A caller
     # with independent batches puts each on a stream of its own: contexts 1.. traverse with context 0's traversal image.
     pipelined = None
-    if args.inflight > 1 and not multi and not bin_rays and args.image:
+    if args.full and args.inflight > 1 and not multi and not bin_rays and args.image:
         try:
             k = args.inflight
             streams = [torch.cuda.Stream() for _ in range(k)]
@@ -480,7 +533,7 @@ def main():
     # a launch of their own on an otherwise empty GPU, as one wavefront (one ray per lane, four once 16 are left: how the tile runs inside the full launch) and as
     # four wavefronts with four lanes per ray from the start; an empty launch (64 rays that miss the grid) gives the launch overhead to subtract.
     critical_path = None
-    if ray_kind == "primary" and n_rays == width * height and n_rays <= (1 << 22) and world == 1 and not bin_rays and args.image and not args.no_order_compare:
+    if args.full and ray_kind == "primary" and n_rays == width * height and n_rays <= (1 << 22) and world == 1 and not bin_rays and args.image and not args.no_order_compare:
         try:
             d_steps = mem.alloc(4 * n_rays)
             api.traverse_grid_stats(grid, d_tris, d_rays, d_hits, n_rays, d_steps)
@@ -519,48 +572,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
         value = total_rays / (ms_per_step * 1e3)                   # Mrays/s, whole job
-        kernel_ms = kernel_ms_total / args.steps                   # average duration of a step on the launch stream (HIP events)
-        achieved = ab["B_ray"] / (kernel_ms * 1e6)                 # GB/s of algorithmic bytes (SURVEY formula), rank-0 kernel
-        achieved_img = ab["B_image"] / (kernel_ms * 1e6)           # GB/s of the bytes the image kernel gathers for the same walk
-        peak = mem.bandwidth_probe(1 << 30, 5)                     # measured in this process: float4 copy / triad over 1 GiB arrays
-        traffic = None; traffic_source = None; l2_hit = None
-        # HBM bytes per launch and the other counters of `binding`: collected in separate rocprofv3 --pmc passes of this very command
-        # (tools/gpu_traffic_config.sh) and committed as profiles/traffic_config<C>.json together with the hash of the kernel sources and the
-        # ray count of the launches it measured.  A file measured on other sources or another batch is refused: traffic = null, traffic_source says why.
-        from hagrid_amd import build as _build
-        src_hash = _build.source_hash()
-        # (a batch of another ray kind than the configuration's own -- `--config clustered --rays aimed` -- has a counter file of its own)
-        tpath = os.path.join(ROOT, "profiles", f"traffic_config{args.config}{'' if ray_kind == cfg['rays'] else '_' + ray_kind}.json")
-        counters = None
-        std_shape = (args.image == 2 and n_tris == cfg["tris"] and (ray_kind in ("incoherent", "aimed") or (width, height) == (cfg.get("width"), cfg.get("height")))
-                     and (top_density, snd_density, expansion, bool(compress)) == (cfg["params"].get("top_density", 0.12), cfg["params"].get("snd_density", 2.4), cfg["params"].get("expansion", 3), bool(cfg["params"].get("compress", False)))
-                     and not args.opts)
-        if os.path.exists(tpath) and world == 1 and std_shape:
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("source_hash") != src_hash:
-                    traffic_source = f"stale: {os.path.relpath(tpath, ROOT)} measured kernel sources {tj.get('source_hash', 'unknown')}, this run has {src_hash}"
-                elif tj.get("rays", n_rays) != n_rays:
-                    traffic_source = f"other batch: {os.path.relpath(tpath, ROOT)} measured launches of {tj.get('rays')} rays, this run has {n_rays}"
-                else:
-                    # fabric-side bytes: by request size where that pass exists; else FETCH_SIZE raw (+ WRITE_SIZE) for the gather kernels -- their L2 misses
-                    # fetch 64-byte sectors (52.8 / 62.8 bytes per miss in profiles/r4a) -- and the x2-corrected figure only in round 3's file
-                    traffic = tj.get("hbm_bytes_per_launch_by_request_size") or (tj.get("hbm_bytes_per_launch_raw") if "counters" in tj else tj.get("hbm_bytes_per_launch"))
-                    l2_hit = tj.get("l2_hit_rate"); counters = tj.get("counters")
-                    traffic_source = f"{os.path.relpath(tpath, ROOT)} (kernel sources {src_hash}, commit {tj.get('commit', '?')}): " + tj.get("source", "")
-            except Exception as e:
-                traffic = None; traffic_source = f"unreadable: {e}"
-        fmt = mem.image_format(grid) if args.image else {}
-        tail = fmt.get("slim_id_bits") and "traverse.tail=0" not in args.opts and "traverse.variant" not in args.opts
-        kernel_name = ("traverse_kernel_tail" if tail else "traverse_kernel_img") if args.image else "traverse_kernel_v2"
-        # what the roofline is quoted on: with a traversal image the bytes the image kernel gathers for the walk (B_image: 48 per ray +
-        # record bytes per cell + 48 per test + 4 per id of a by-index list) -- `frac` then cannot exceed what a copy reaches; the
-        # SURVEY 8(d) formula on the CONSTRUCTION format (entries + cells + ids + triangles, which this kernel never reads) is
-        # carried next to it as `*_contract`.  Without an image the two are the same thing.
-        ach = achieved_img if args.image else achieved
-        head_achieved, head_frac, head_kind = roofline_headline(ach, traffic, kernel_ms)
-        cells_b = grid.num_cells * (16 if compressed else 32)
-        image_b = mem.image_bytes(grid)
         out = {
             "metric": "Mrays/s (primary traversal) + grid build ms, 1M-tri scene @1/2/4/8 MI355X",
             "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -578,126 +589,171 @@ def main():
             "build_ms": None if build_ms is None else round(build_ms, 3),                   # mean of --build-iter full constructions after two warm-up builds
             "build_ms_min": None if build_ms is None else round(build_ms_min, 3),
             "grid_broadcast_ms": round(t_bcast, 3),
-            "setup_traversal_ms": round(setup_ms, 3),
             "hits_sha256": hits_sha,
-            "hit_fraction": round(tot_hits / total_rays, 4), "rays_entering_grid": round(tot_in / total_rays, 4),
-            # `achieved` / `frac`: measured HBM bytes per launch over the kernel time against the HBM peak (roofline_headline above); `binding` names what
-            # does bind, from the counters of this configuration measured on these kernel sources (tools/gpu_traffic_config.sh): every fraction there is
-            # against what the part delivers for that access pattern.
-            "roofline": {
-                "bound": "hbm", "achieved": head_achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": head_frac, "frac_kind": head_kind,
-                # the algorithmic figures next to it: what the kernel gathers (image records, triangles, ids of long lists) and the SURVEY.md 8(d) formula on the
-                # construction format (entries + cells + ids + triangles, which this kernel never reads); neither is a bound for a cache-resident working set
-                "achieved_image": round(ach, 1), "frac_image": round(ach / HBM_PEAK_GBPS, 4),
-                "bytes": "B_image: what the traversal-image kernel gathers (DESIGN.md 4.2)" if args.image else "B_ray: SURVEY.md 8(d) on the construction format",
-                "achieved_contract": round(achieved, 1), "frac_contract": round(achieved / HBM_PEAK_GBPS, 4),     # SURVEY.md 8(d) formula, construction format
-                "traffic": traffic, "traffic_source": traffic_source,
-                "binding": None,
-                "hbm_measured": None if traffic is None else round(traffic / (kernel_ms * 1e6), 1),
-                "hbm_measured_frac": None if traffic is None else round(traffic / (kernel_ms * 1e6) / HBM_PEAK_GBPS, 4),
-                "l2_hit_rate": l2_hit,
-                "peak_measured": {"copy": round(peak["copy_GBps"], 1), "triad": round(peak["triad_GBps"], 1), "unit": "GB/s",
-                                  "frac_of_copy": round(head_achieved / max(peak["copy_GBps"], 1e-9), 4)},
-                "kernel": kernel_name, "kernel_ms": round(kernel_ms, 5), "kernel_sources": src_hash,
-                "bytes_per_ray": round((ab["B_image"] if args.image else ab["B_ray"]) / n_rays, 1),
-                "bytes_per_ray_contract": round(ab["B_ray"] / n_rays, 1),
-                "walk_achieved": round(ab["B_walk"] / (kernel_ms * 1e6), 1),
-                "walk_frac": round(ab["B_walk"] / (kernel_ms * 1e6) / HBM_PEAK_GBPS, 4),
-                "walk_target": 0.40,
-                "walk_achieved_image": round(ab["B_image_walk"] / (kernel_ms * 1e6), 1)},
-            "pipelined": pipelined,
-            "tile_order": tile_order,
-            "roofline_build": build_block,
-            "memory": {"cells": cells_b, "entries": 4 * grid.num_entries, "refs": 4 * grid.num_refs, "tris": 48 * n_tris,
-                       "traversal_image": image_b, "releasable_after_setup_traversal": cells_b + 4 * grid.num_entries, "rays": 32 * n_rays, "hits": 16 * n_rays, "pool_now": mem.usage(), "pool_peak": mem.max_usage(),
-                       "unit": "bytes", "reference": "main.cpp:523-533"},
         }
-        working_set = image_b + 48 * n_tris + 4 * grid.num_refs if args.image else cells_b + 4 * grid.num_entries + 4 * grid.num_refs + 48 * n_tris
-        if counters:
-            res, top, top_frac = binding_resources(counters, kernel_ms, working_set, traffic)
-            limiter, waiting = binding_limiter(res, top, top_frac)
-            out["roofline"]["binding"] = {"resource": top, "frac": top_frac, "limiter": limiter, "resources": res, "working_set_bytes": working_set,
-                                          "how": "counters per launch from separate rocprofv3 --pmc passes on these kernel sources (traffic_source), divided by this run's kernel time; "
-                                                 "`resource` = the most used throughput resource; `limiter` = memory_latency when the wavefronts wait for memory >= 60 % of their time and no "
-                                                 "throughput fraction reaches 0.95 (dependent gathers at the occupancy the kernel has: fewer fetches do not make such a launch faster)"}
-            if counters.get("TCP_TCC_READ_REQ_LATENCY_sum") and counters.get("TCP_TCC_READ_REQ_sum"):
-                # Little's law on the vector L1s' requests to L2: requests in flight = sum of their latencies / kernel time; against the rays that can have one in flight
-                lat_cycles = counters["TCP_TCC_READ_REQ_LATENCY_sum"] / counters["TCP_TCC_READ_REQ_sum"]
-                in_flight = counters["TCP_TCC_READ_REQ_LATENCY_sum"] / (kernel_ms * 1e-3 * SHADER_CLOCK_HZ)
-                out["roofline"]["binding"]["littles_law"] = {
-                    "l1_miss_latency_cycles": round(lat_cycles, 1), "l1_miss_latency_ns": round(lat_cycles / SHADER_CLOCK_HZ * 1e9, 1), "requests_in_flight": round(in_flight, 1),
-                    "requests_in_flight_per_cu": round(in_flight / NUM_CUS, 2),
-                    "request_rate_from_latency": round(in_flight / (lat_cycles / SHADER_CLOCK_HZ) / 1e9, 2), "request_rate_measured": round(counters["TCP_TCC_READ_REQ_sum"] / (kernel_ms * 1e-3) / 1e9, 2),
-                    "unit": "G requests/s", "what": "vector-L1 misses: average latency (TCP_TCC_READ_REQ_LATENCY / TCP_TCC_READ_REQ) and the number in flight (sum of latencies / kernel time); "
-                            "rate = in flight / latency by construction -- a launch whose rays each wait for ONE dependent gather at a time raises it only with more rays in flight "
-                            "(resident wavefronts x live lanes) or a shorter latency, not with fewer bytes"}
-            if critical_path:
-                critical_path["ms_per_step_over_critical_path"] = round(ms_per_step / critical_path["critical_path_ms"], 3) if critical_path["critical_path_ms"] > 0 else None
-                out["roofline"]["binding"]["critical_path"] = critical_path
-            out["roofline"]["bound"] = top if top in ("hbm_bytes",) else (f"{top} (not hbm bytes: see binding)" if limiter == top else
-                                                                         f"memory latency of dependent gathers (wavefronts wait {waiting:.2f} of their time; most used resource: {top} {top_frac:.2f}; see binding)")
-        else:
-            out["roofline"]["binding"] = {"resource": None, "why": traffic_source or "no counter file for this configuration and batch (tools/gpu_traffic_config.sh)"}
-            if critical_path:
-                critical_path["ms_per_step_over_critical_path"] = round(ms_per_step / critical_path["critical_path_ms"], 3) if critical_path["critical_path_ms"] > 0 else None
-                out["roofline"]["binding"]["critical_path"] = critical_path
-        # ---- CPU baseline + parity check: the oracle on the SAME grid, rank 0, N = 1 only ---------------------------------
-        if world == 1 and not args.no_cpu_baseline:
-            from oracle import oracle as O
-            d = grid.download()
-            G = O.Grid.from_arrays(d["entries"], d["ref_ids"], d["cells"], d["small_cells"], d["bbox_min"], d["bbox_max"], d["dims"], d["shift"], d["offsets"])
-            # all host cores: worker threads take 4096-ray chunks from a shared counter and are pinned (oracle/hagrid_oracle.c run_jobs_on) -- once to
-            # one hardware thread per physical core, once to every hardware thread; the better of the two is `value`
-            phys = O.physical_cpus(); allhw = sorted(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else list(range(os.cpu_count() or 1))
-            # the container may hold less CPU time than the cores it sees (cgroup quota): more threads than that only take turns
-            quota = None
-            try:
-                q, per = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-                quota = None if q == "max" else float(q) / float(per)
-            except Exception:
+        if args.full:
+            kernel_ms = kernel_ms_total / args.steps                   # average duration of a step on the launch stream (HIP events)
+            achieved = ab["B_ray"] / (kernel_ms * 1e6)                 # GB/s of algorithmic bytes (SURVEY formula), rank-0 kernel
+            achieved_img = ab["B_image"] / (kernel_ms * 1e6)           # GB/s of the bytes the image kernel gathers for the same walk
+            peak = mem.bandwidth_probe(1 << 30, 5)                     # measured in this process: float4 copy / triad over 1 GiB arrays
+            traffic = None; traffic_source = None; l2_hit = None
+            # HBM bytes per launch and the other counters of `binding`: collected in separate rocprofv3 --pmc passes of this very command
+            # (tools/gpu_traffic_config.sh) and committed as profiles/traffic_config<C>.json together with the hash of the kernel sources and the
+            # ray count of the launches it measured.  A file measured on other sources or another batch is refused: traffic = null, traffic_source says why.
+            from hagrid_amd import build as _build
+            src_hash = _build.source_hash()
+            # (a batch of another ray kind than the configuration's own -- `--config clustered --rays aimed` -- has a counter file of its own)
+            tpath = os.path.join(ROOT, "profiles", f"traffic_config{args.config}{'' if ray_kind == cfg['rays'] else '_' + ray_kind}.json")
+            counters = None
+            std_shape = (args.image == 2 and n_tris == cfg["tris"] and (ray_kind in ("incoherent", "aimed") or (width, height) == (cfg.get("width"), cfg.get("height")))
+                         and (top_density, snd_density, expansion, bool(compress)) == (cfg["params"].get("top_density", 0.12), cfg["params"].get("snd_density", 2.4), cfg["params"].get("expansion", 3), bool(cfg["params"].get("compress", False)))
+                         and not args.opts)
+            if os.path.exists(tpath) and world == 1 and std_shape:
                 try:
-                    q = float(open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us").read()); per = float(open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read())
-                    quota = q / per if q > 0 else None
+                    tj = json.load(open(tpath))
+                    if tj.get("source_hash") != src_hash:
+                        traffic_source = f"stale: {os.path.relpath(tpath, ROOT)} measured kernel sources {tj.get('source_hash', 'unknown')}, this run has {src_hash}"
+                    elif tj.get("rays", n_rays) != n_rays:
+                        traffic_source = f"other batch: {os.path.relpath(tpath, ROOT)} measured launches of {tj.get('rays')} rays, this run has {n_rays}"
+                    else:
+                        # fabric-side bytes: by request size where that pass exists; else FETCH_SIZE raw (+ WRITE_SIZE) for the gather kernels -- their L2 misses
+                        # fetch 64-byte sectors (52.8 / 62.8 bytes per miss in profiles/r4a) -- and the x2-corrected figure only in round 3's file
+                        traffic = tj.get("hbm_bytes_per_launch_by_request_size") or (tj.get("hbm_bytes_per_launch_raw") if "counters" in tj else tj.get("hbm_bytes_per_launch"))
+                        l2_hit = tj.get("l2_hit_rate"); counters = tj.get("counters")
+                        traffic_source = f"{os.path.relpath(tpath, ROOT)} (kernel sources {src_hash}, commit {tj.get('commit', '?')}): " + tj.get("source", "")
+                except Exception as e:
+                    traffic = None; traffic_source = f"unreadable: {e}"
+            fmt = mem.image_format(grid) if args.image else {}
+            tail = fmt.get("slim_id_bits") and "traverse.tail=0" not in args.opts and "traverse.variant" not in args.opts
+            kernel_name = ("traverse_kernel_tail" if tail else "traverse_kernel_img") if args.image else "traverse_kernel_v2"
+            # what the roofline is quoted on: with a traversal image the bytes the image kernel gathers for the walk (B_image: 48 per ray +
+            # record bytes per cell + 48 per test + 4 per id of a by-index list) -- `frac` then cannot exceed what a copy reaches; the
+            # SURVEY 8(d) formula on the CONSTRUCTION format (entries + cells + ids + triangles, which this kernel never reads) is
+            # carried next to it as `*_contract`.  Without an image the two are the same thing.
+            ach = achieved_img if args.image else achieved
+            head_achieved, head_frac, head_kind = roofline_headline(ach, traffic, kernel_ms)
+            cells_b = grid.num_cells * (16 if compressed else 32)
+            image_b = mem.image_bytes(grid)
+            out.update({
+                "setup_traversal_ms": round(setup_ms, 3),
+                "hit_fraction": round(tot_hits / total_rays, 4), "rays_entering_grid": round(tot_in / total_rays, 4),
+                # `achieved` / `frac`: measured HBM bytes per launch over the kernel time against the HBM peak (roofline_headline above); `binding` names what
+                # does bind, from the counters of this configuration measured on these kernel sources (tools/gpu_traffic_config.sh): every fraction there is
+                # against what the part delivers for that access pattern.
+                "roofline": {
+                    "bound": "hbm", "achieved": head_achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": head_frac, "frac_kind": head_kind,
+                    # the algorithmic figures next to it: what the kernel gathers (image records, triangles, ids of long lists) and the SURVEY.md 8(d) formula on the
+                    # construction format (entries + cells + ids + triangles, which this kernel never reads); neither is a bound for a cache-resident working set
+                    "achieved_image": round(ach, 1), "frac_image": round(ach / HBM_PEAK_GBPS, 4),
+                    "bytes": "B_image: what the traversal-image kernel gathers (DESIGN.md 4.2)" if args.image else "B_ray: SURVEY.md 8(d) on the construction format",
+                    "achieved_contract": round(achieved, 1), "frac_contract": round(achieved / HBM_PEAK_GBPS, 4),     # SURVEY.md 8(d) formula, construction format
+                    "traffic": traffic, "traffic_source": traffic_source,
+                    "binding": None,
+                    "hbm_measured": None if traffic is None else round(traffic / (kernel_ms * 1e6), 1),
+                    "hbm_measured_frac": None if traffic is None else round(traffic / (kernel_ms * 1e6) / HBM_PEAK_GBPS, 4),
+                    "l2_hit_rate": l2_hit,
+                    "peak_measured": {"copy": round(peak["copy_GBps"], 1), "triad": round(peak["triad_GBps"], 1), "unit": "GB/s",
+                                      "frac_of_copy": round(head_achieved / max(peak["copy_GBps"], 1e-9), 4)},
+                    "kernel": kernel_name, "kernel_ms": round(kernel_ms, 5), "kernel_sources": src_hash,
+                    "bytes_per_ray": round((ab["B_image"] if args.image else ab["B_ray"]) / n_rays, 1),
+                    "bytes_per_ray_contract": round(ab["B_ray"] / n_rays, 1),
+                    "walk_achieved": round(ab["B_walk"] / (kernel_ms * 1e6), 1),
+                    "walk_frac": round(ab["B_walk"] / (kernel_ms * 1e6) / HBM_PEAK_GBPS, 4),
+                    "walk_target": 0.40,
+                    "walk_achieved_image": round(ab["B_image_walk"] / (kernel_ms * 1e6), 1)},
+                "pipelined": pipelined,
+                "tile_order": tile_order,
+                "roofline_build": build_block,
+                "memory": {"cells": cells_b, "entries": 4 * grid.num_entries, "refs": 4 * grid.num_refs, "tris": 48 * n_tris,
+                           "traversal_image": image_b, "releasable_after_setup_traversal": cells_b + 4 * grid.num_entries, "rays": 32 * n_rays, "hits": 16 * n_rays, "pool_now": mem.usage(), "pool_peak": mem.max_usage(),
+                           "unit": "bytes", "reference": "main.cpp:523-533"},
+            })
+            working_set = image_b + 48 * n_tris + 4 * grid.num_refs if args.image else cells_b + 4 * grid.num_entries + 4 * grid.num_refs + 48 * n_tris
+            if counters:
+                res, top, top_frac = binding_resources(counters, kernel_ms, working_set, traffic)
+                limiter, waiting = binding_limiter(res, top, top_frac)
+                out["roofline"]["binding"] = {"resource": top, "frac": top_frac, "limiter": limiter, "resources": res, "working_set_bytes": working_set,
+                                              "how": "counters per launch from separate rocprofv3 --pmc passes on these kernel sources (traffic_source), divided by this run's kernel time; "
+                                                     "`resource` = the most used throughput resource; `limiter` = memory_latency when the wavefronts wait for memory >= 60 % of their time and no "
+                                                     "throughput fraction reaches 0.95 (dependent gathers at the occupancy the kernel has: fewer fetches do not make such a launch faster)"}
+                if counters.get("TCP_TCC_READ_REQ_LATENCY_sum") and counters.get("TCP_TCC_READ_REQ_sum"):
+                    # Little's law on the vector L1s' requests to L2: requests in flight = sum of their latencies / kernel time; against the rays that can have one in flight
+                    lat_cycles = counters["TCP_TCC_READ_REQ_LATENCY_sum"] / counters["TCP_TCC_READ_REQ_sum"]
+                    in_flight = counters["TCP_TCC_READ_REQ_LATENCY_sum"] / (kernel_ms * 1e-3 * SHADER_CLOCK_HZ)
+                    out["roofline"]["binding"]["littles_law"] = {
+                        "l1_miss_latency_cycles": round(lat_cycles, 1), "l1_miss_latency_ns": round(lat_cycles / SHADER_CLOCK_HZ * 1e9, 1), "requests_in_flight": round(in_flight, 1),
+                        "requests_in_flight_per_cu": round(in_flight / NUM_CUS, 2),
+                        "request_rate_from_latency": round(in_flight / (lat_cycles / SHADER_CLOCK_HZ) / 1e9, 2), "request_rate_measured": round(counters["TCP_TCC_READ_REQ_sum"] / (kernel_ms * 1e-3) / 1e9, 2),
+                        "unit": "G requests/s", "what": "vector-L1 misses: average latency (TCP_TCC_READ_REQ_LATENCY / TCP_TCC_READ_REQ) and the number in flight (sum of latencies / kernel time); "
+                                "rate = in flight / latency by construction -- a launch whose rays each wait for ONE dependent gather at a time raises it only with more rays in flight "
+                                "(resident wavefronts x live lanes) or a shorter latency, not with fewer bytes"}
+                if critical_path:
+                    critical_path["ms_per_step_over_critical_path"] = round(ms_per_step / critical_path["critical_path_ms"], 3) if critical_path["critical_path_ms"] > 0 else None
+                    out["roofline"]["binding"]["critical_path"] = critical_path
+                out["roofline"]["bound"] = top if top in ("hbm_bytes",) else (f"{top} (not hbm bytes: see binding)" if limiter == top else
+                                                                             f"memory latency of dependent gathers (wavefronts wait {waiting:.2f} of their time; most used resource: {top} {top_frac:.2f}; see binding)")
+            else:
+                out["roofline"]["binding"] = {"resource": None, "why": traffic_source or "no counter file for this configuration and batch (tools/gpu_traffic_config.sh)"}
+                if critical_path:
+                    critical_path["ms_per_step_over_critical_path"] = round(ms_per_step / critical_path["critical_path_ms"], 3) if critical_path["critical_path_ms"] > 0 else None
+                    out["roofline"]["binding"]["critical_path"] = critical_path
+            # ---- CPU baseline + parity check: the oracle on the SAME grid, rank 0, N = 1 only ---------------------------------
+            if world == 1 and not args.no_cpu_baseline:
+                from oracle import oracle as O
+                d = grid.download()
+                G = O.Grid.from_arrays(d["entries"], d["ref_ids"], d["cells"], d["small_cells"], d["bbox_min"], d["bbox_max"], d["dims"], d["shift"], d["offsets"])
+                # all host cores: worker threads take 4096-ray chunks from a shared counter and are pinned (oracle/hagrid_oracle.c run_jobs_on) -- once to
+                # one hardware thread per physical core, once to every hardware thread; the better of the two is `value`
+                phys = O.physical_cpus(); allhw = sorted(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else list(range(os.cpu_count() or 1))
+                # the container may hold less CPU time than the cores it sees (cgroup quota): more threads than that only take turns
+                quota = None
+                try:
+                    q, per = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+                    quota = None if q == "max" else float(q) / float(per)
                 except Exception:
-                    pass
-            if quota and quota < len(phys):
-                phys = phys[:max(1, int(quota + 0.999))]; allhw = allhw[:max(1, int(2 * quota + 0.999))]
-            cores = len(phys)
-            probe = min(65536, n_head)
-            t0 = time.perf_counter(); oh, _ = G.traverse(tris_host, rays_head[:probe], nthreads=cores, cpus=phys); t_probe = time.perf_counter() - t0
-            sample_n = int(min(n_head, max(probe, probe * 0.5 * args.cpu_seconds / max(t_probe, 1e-6))))
-            def timed(cpus):
-                t0 = time.perf_counter(); h, _ = G.traverse(tris_host, rays_head[:sample_n], nthreads=len(cpus), cpus=cpus); t = time.perf_counter() - t0
-                reps = 1
-                while t < 0.25 * args.cpu_seconds and reps < 512:        # the whole sample is too small: repeat it
-                    t0 = time.perf_counter(); G.traverse(tris_host, rays_head[:sample_n], nthreads=len(cpus), cpus=cpus); t += time.perf_counter() - t0; reps += 1
-                return h, sample_n * reps / t / 1e6, reps
-            oh, rate_phys, reps = timed(phys)
-            rate_all = None
-            if len(allhw) > len(phys):
-                _, rate_all, _ = timed(allhw)
-            same_id = bool((hits["id"][:sample_n] == oh["id"]).all())
-            same_t = bool((hits["t"][:sample_n].view(np.uint32) == oh["t"].view(np.uint32)).all())
-            # one thread: a bounded slice of the same rays (about a third of the all-cores budget)
-            one_n = int(min(sample_n, 16384))
-            t0 = time.perf_counter(); G.traverse(tris_host, rays_head[:one_n], nthreads=1); t1 = time.perf_counter() - t0
-            one_n = int(min(sample_n, max(one_n, one_n * 0.3 * args.cpu_seconds / max(t1, 1e-6))))
-            t0 = time.perf_counter(); G.traverse(tris_host, rays_head[:one_n], nthreads=1); t1 = time.perf_counter() - t0
-            rate_one = one_n / t1 / 1e6
-            best, used = (rate_all, len(allhw)) if rate_all and rate_all > rate_phys else (rate_phys, len(phys))
-            out["cpu_baseline"] = {"value": round(best, 4), "unit": "Mrays/s", "cores": used, "kind": "port",
-                                   "sample": f"first {sample_n} rays of the batch x{reps}, oracle traversal of the GPU-built grid, {used} pinned threads taking 4096-ray chunks from a shared counter",
-                                   "physical_cores": {"value": round(rate_phys, 4), "threads": len(phys), "scaling_vs_one_thread": round(rate_phys / rate_one, 1),
-                                                      "efficiency": round(rate_phys / rate_one / len(phys), 3)},
-                                   "all_hardware_threads": None if rate_all is None else {"value": round(rate_all, 4), "threads": len(allhw), "scaling_vs_one_thread": round(rate_all / rate_one, 1)},
-                                   "single_thread": {"value": round(rate_one, 4), "unit": "Mrays/s", "cores": 1, "sample": f"first {one_n} rays of the batch"},
-                                   "host": {"hardware_threads": os.cpu_count(), "physical_cores_visible": len(O.physical_cpus()), "cgroup_cpu_quota_cores": quota}}
-            if n_tris <= 1_000_000:      # CPU construction of the same grid, one core (the oracle's passes are scalar)
-                t0 = time.perf_counter()
-                Gc = O.Grid.full(tris_host, top_density, snd_density, args.alpha, expansion, compress)
-                out["cpu_baseline"]["cpu_build_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
-                out["cpu_baseline"]["cpu_build_matches_gpu"] = bool(Gc.summary() == grid.summary())
-            out["parity"] = {"rays_checked": sample_n, "ids_identical": same_id, "t_bit_identical": same_t}
+                    try:
+                        q = float(open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us").read()); per = float(open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read())
+                        quota = q / per if q > 0 else None
+                    except Exception:
+                        pass
+                if quota and quota < len(phys):
+                    phys = phys[:max(1, int(quota + 0.999))]; allhw = allhw[:max(1, int(2 * quota + 0.999))]
+                cores = len(phys)
+                probe = min(65536, n_head)
+                t0 = time.perf_counter(); oh, _ = G.traverse(tris_host, rays_head[:probe], nthreads=cores, cpus=phys); t_probe = time.perf_counter() - t0
+                sample_n = int(min(n_head, max(probe, probe * 0.5 * args.cpu_seconds / max(t_probe, 1e-6))))
+                def timed(cpus):
+                    t0 = time.perf_counter(); h, _ = G.traverse(tris_host, rays_head[:sample_n], nthreads=len(cpus), cpus=cpus); t = time.perf_counter() - t0
+                    reps = 1
+                    while t < 0.25 * args.cpu_seconds and reps < 512:        # the whole sample is too small: repeat it
+                        t0 = time.perf_counter(); G.traverse(tris_host, rays_head[:sample_n], nthreads=len(cpus), cpus=cpus); t += time.perf_counter() - t0; reps += 1
+                    return h, sample_n * reps / t / 1e6, reps
+                oh, rate_phys, reps = timed(phys)
+                rate_all = None
+                if len(allhw) > len(phys):
+                    _, rate_all, _ = timed(allhw)
+                same_id = bool((hits["id"][:sample_n] == oh["id"]).all())
+                same_t = bool((hits["t"][:sample_n].view(np.uint32) == oh["t"].view(np.uint32)).all())
+                # one thread: a bounded slice of the same rays (about a third of the all-cores budget)
+                one_n = int(min(sample_n, 16384))
+                t0 = time.perf_counter(); G.traverse(tris_host, rays_head[:one_n], nthreads=1); t1 = time.perf_counter() - t0
+                one_n = int(min(sample_n, max(one_n, one_n * 0.3 * args.cpu_seconds / max(t1, 1e-6))))
+                t0 = time.perf_counter(); G.traverse(tris_host, rays_head[:one_n], nthreads=1); t1 = time.perf_counter() - t0
+                rate_one = one_n / t1 / 1e6
+                best, used = (rate_all, len(allhw)) if rate_all and rate_all > rate_phys else (rate_phys, len(phys))
+                out["cpu_baseline"] = {"value": round(best, 4), "unit": "Mrays/s", "cores": used, "kind": "port",
+                                       "sample": f"first {sample_n} rays of the batch x{reps}, oracle traversal of the GPU-built grid, {used} pinned threads taking 4096-ray chunks from a shared counter",
+                                       "physical_cores": {"value": round(rate_phys, 4), "threads": len(phys), "scaling_vs_one_thread": round(rate_phys / rate_one, 1),
+                                                          "efficiency": round(rate_phys / rate_one / len(phys), 3)},
+                                       "all_hardware_threads": None if rate_all is None else {"value": round(rate_all, 4), "threads": len(allhw), "scaling_vs_one_thread": round(rate_all / rate_one, 1)},
+                                       "single_thread": {"value": round(rate_one, 4), "unit": "Mrays/s", "cores": 1, "sample": f"first {one_n} rays of the batch"},
+                                       "host": {"hardware_threads": os.cpu_count(), "physical_cores_visible": len(O.physical_cpus()), "cgroup_cpu_quota_cores": quota}}
+                if n_tris <= 1_000_000:      # CPU construction of the same grid, one core (the oracle's passes are scalar)
+                    t0 = time.perf_counter()
+                    Gc = O.Grid.full(tris_host, top_density, snd_density, args.alpha, expansion, compress)
+                    out["cpu_baseline"]["cpu_build_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+                    out["cpu_baseline"]["cpu_build_matches_gpu"] = bool(Gc.summary() == grid.summary())
+                out["parity"] = {"rays_checked": sample_n, "ids_identical": same_id, "t_bit_identical": same_t}
         print(json.dumps(out), flush=True)
     if multi:
         dist.barrier()

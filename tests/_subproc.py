@@ -1,5 +1,5 @@
 """Runs a front-end binary with a short time limit; a process that does not exit is diagnosed (kernel wait channel and
-stack of every thread, user stacks through rocgdb when present) and its whole process group killed, so a front-end fault
+stack of every thread) and its whole process group killed, so a front-end fault
 costs one test a minute instead of masking the kernel-parity tests behind it."""
 import os
 import signal
@@ -40,7 +40,7 @@ def _one_process(pid):
 
 def thread_report(pid):
     """Every process of the session `pid` leads (the front-end re-executes itself once per rank): command line, and per thread the kernel
-    wait channel; user stacks of the leader through rocgdb where ptrace is allowed."""
+    wait channel and stack."""
     lines = []
     pids = [pid]
     for d in os.listdir("/proc"):
@@ -52,17 +52,6 @@ def thread_report(pid):
                 pass
     for q in pids:
         lines += _one_process(q)
-    gdb = "/opt/rocm/bin/rocgdb"
-    if os.path.exists(gdb):
-        for q in pids[:3]:
-            try:
-                r = subprocess.run([gdb, "-p", str(q), "-batch", "-ex", "set pagination off", "-ex", "thread apply all bt 30"],
-                                   capture_output=True, text=True, timeout=120)
-                if "Operation not permitted" in r.stderr:
-                    lines.append("  rocgdb: ptrace not permitted here"); break
-                lines.append(r.stdout[-8000:])
-            except Exception as e:                               # diagnosis must never fail the caller
-                lines.append(f"  rocgdb: {e}")
     return "\n".join(lines) + "\n"
 
 

@@ -3,17 +3,18 @@
 tools/cli_report.h holds one function per report of the reference's main.cpp (:469 scene, :512-515 grid, :523-533 memory,
 :434-444 benchmark).  (1) A small program prints them for fixed numbers and the text must equal what the reference's statements
 print for those numbers (written out below from main.cpp's format strings; floating-point numbers go through operator<< with the
-default precision on both sides).  (2) Where the reference checkout exists, the string literals of those statements are taken
-from main.cpp itself and must appear, in order, in the output; the usage text must start with the reference's usage text."""
+default precision on both sides).  (2) The string literals of those statements, taken from main.cpp by
+tests/golden/make_golden_cli.py into tests/golden/cli_golden.json, must appear, in order, in the output; the usage text must
+start with the reference's usage text stored there."""
+import json
 import os
-import re
 import subprocess
 import tempfile
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MAIN = "/root/reference/src/main.cpp"
+GOLDEN = os.path.join(ROOT, "tests", "golden", "cli_golden.json")
 
 PROG = r'''
 #include <iostream>
@@ -60,36 +61,20 @@ def test_report_lines_for_fixed_numbers(report_text):
     assert report_text == EXPECTED
 
 
-def _cout_literals(text):
-    """The string literals of the std::cout statements in `text`, in order."""
-    out = []
-    for stmt in re.findall(r"std::cout\s*<<(.*?);", text, flags=re.S):
-        out += re.findall(r'"((?:[^"\\]|\\.)*)"', stmt)
-    return [s for s in out if s.strip()]
-
-
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="reference checkout not present")
 def test_literals_of_the_reference_statements_appear_in_order(report_text):
-    lines = open(REF_MAIN).read().split("\n")
-    pick = lambda a, b: "\n".join(lines[a - 1:b])
     # (the order of the calls in PROG: scene, grid, memory, timings)
-    lits = _cout_literals(pick(469, 469)) + _cout_literals(pick(512, 515)) + _cout_literals(pick(523, 533)) + _cout_literals(pick(439, 444))
+    lits = json.load(open(GOLDEN))["report_literals"]
     assert len(lits) >= 25, lits
     at = 0
     for lit in lits:
-        lit = lit.encode().decode("unicode_escape")
         found = report_text.find(lit, at)
         assert found >= 0, (lit, report_text[at:at + 200])
         at = found + len(lit)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="reference checkout not present")
 def test_usage_text_starts_with_the_reference_usage():
     import test_cpp_api as T
-    src = open(REF_MAIN).read()
-    body = src[src.index("static void usage()"):]
-    body = body[:body.index("<< std::endl")]
-    want = "".join(s.encode().decode("unicode_escape") for s in re.findall(r'"((?:[^"\\]|\\.)*)"', body))
+    want = json.load(open(GOLDEN))["usage"]
     assert want.startswith("Usage: hagrid [options] file\n") and want.count("\n") >= 20
     with tempfile.TemporaryDirectory() as d:
         exe = T._build_cli(d)

@@ -27,7 +27,7 @@ def free_port():
 def test_bench_two_ranks_share_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--tris", "100000", "--width", "512", "--height", "512", "--backend", "gloo", "--device", "0", "--build-iter", "1"]
+           "--tris", "100000", "--width", "512", "--height", "512", "--backend", "gloo", "--device", "0", "--build-iter", "1", "--full"]
     r = _subproc.run(cmd, timeout=300, cwd=ROOT)
     assert not r.timed_out, r.diagnosis
     assert r.returncode == 0, r.stderr[-3000:]
@@ -60,7 +60,7 @@ def test_bench_strong_scaling_two_ranks(config, extra):
     """bench.py --config 3/4/5 shards ONE batch over the ranks (strong scaling): the job total is the batch, not N batches."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", str(config),
-           "--tris", "100000", "--backend", "gloo", "--device", "0", "--build-iter", "1"] + extra
+           "--tris", "100000", "--backend", "gloo", "--device", "0", "--build-iter", "1", "--full"] + extra
     r = _subproc.run(cmd, timeout=300, cwd=ROOT)
     assert not r.timed_out, r.diagnosis
     assert r.returncode == 0, r.stderr[-3000:]
@@ -205,10 +205,10 @@ def test_bench_rccl_path_with_one_rank():
 
 
 def test_bench_single_gpu_line_carries_the_pipelined_block():
-    """The default (single process) bench line: `pipelined` = the same steps with two calls in flight over one shared traversal image,
+    """The single-process bench line with --full: `pipelined` = the same steps with two calls in flight over one shared traversal image,
     hits identical to the single-stream run; never part of `value`.  --inflight 0 leaves it out."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tris", "100000",
-            "--width", "512", "--height", "512", "--build-iter", "1", "--no-cpu-baseline"]
+            "--width", "512", "--height", "512", "--build-iter", "1", "--no-cpu-baseline", "--full"]
     r = _subproc.run(base, timeout=300, cwd=ROOT)
     assert not r.timed_out, r.diagnosis
     assert r.returncode == 0, r.stderr[-3000:]
@@ -220,6 +220,32 @@ def test_bench_single_gpu_line_carries_the_pipelined_block():
     assert not r.timed_out, r.diagnosis
     assert r.returncode == 0, r.stderr[-3000:]
     assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["pipelined"] is None
+
+
+def test_bench_plain_line_and_dumped_hits(tmp_path):
+    """A plain bench run (no --full) prints the headline line only, and --dump-outputs writes the hits of its last timed step: float64 ids and
+    float32 t / u / v of every ray, equal to the CPU oracle's on the same scene and rays."""
+    from oracle import oracle as O
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--tris", "100000",
+            "--width", "256", "--height", "256", "--build-iter", "1", "--dump-outputs", str(tmp_path)]
+    r = _subproc.run(base, timeout=300, cwd=ROOT)
+    assert not r.timed_out, r.diagnosis
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 4 and out["ms_per_step"] > 0 and out["value"] == pytest.approx(256 * 256 / (out["ms_per_step"] * 1e3), rel=1e-3)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "build_ms"):
+        assert k in out, k
+    for k in ("roofline", "cpu_baseline", "parity", "pipelined", "tile_order", "hit_fraction"):
+        assert k not in out, k
+    got = {n: np.load(str(tmp_path / f"{n}.npy")) for n in ("ray_index", "hits_id", "hits_t", "hits_u", "hits_v")}
+    assert got["ray_index"].dtype == np.float64 and got["hits_id"].dtype == np.float64 and got["hits_t"].dtype == np.float32
+    assert (got["ray_index"] == np.arange(256 * 256)).all()
+    tris = scene.make_soup(100000)
+    G = O.Grid.full(tris)
+    rays = scene.make_rays_primary(G.bbox_min, G.bbox_max, 256, 256)
+    oh, _ = G.traverse(tris, rays, nthreads=4)
+    assert (got["hits_id"] == oh["id"]).all() and (got["hits_t"].view(np.uint32) == oh["t"].view(np.uint32)).all()
+    assert (got["hits_id"] >= 0).sum() > 0.3 * rays.shape[0]
 
 
 @pytest.mark.parametrize("compress", [False, True])

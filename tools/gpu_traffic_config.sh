@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG/config$C$TRAFFIC_SUFFIX; mkdir -p $OUT        # (TRAFFIC_SUF
 export TMPDIR=/tmp
 ROOT=$PWD
 python -c "import __graft_entry__ as g; g.build()" || exit 1
-BENCH="python $ROOT/bench.py --gpus 1 --steps 5 --warmup 2 --build-iter 1 --no-cpu-baseline --inflight 0 --no-order-compare --config $C $*"
+BENCH="python $ROOT/bench.py --gpus 1 --steps 5 --warmup 2 --full --build-iter 1 --no-cpu-baseline --inflight 0 --no-order-compare --config $C $*"
 echo "$BENCH" > $OUT/command.txt
 # the un-profiled line first (its kernel_ms is what the counters are divided by when the stats pass is missing)
 timeout -k 5 ${PASS_LIMIT:-900} $BENCH > $OUT/bench.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench.json
