@@ -27,7 +27,7 @@ import os
 import numpy as np
 
 from . import lib as _lib
-from .lib import GridPOD, HagridError, TraversalStats
+from .lib import Camera, GridPOD, HagridError, TraversalStats
 from .scene import CELL_DTYPE, HIT_DTYPE, SMALL_CELL_DTYPE
 
 _current = None  # the most recently created MemManager (profile / setup_traversal take no manager)
@@ -346,6 +346,78 @@ def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: i
     return st.as_dict()
 
 
+# ---- frames on the device (include/hagrid_amd.h "frames on the device", include/hagrid/frame.h) ----------------------------
+
+SHADE_DEPTH, SHADE_GRAY, SHADE_HEAT = 0, 1, 2      # hagrid_shade_hits / hagrid_render_frame modes
+BOUNCE_REDRAW_MISSES = 1                           # hagrid_gen_bounce_rays flag
+
+
+def _camera(cam) -> Camera:
+    return cam if isinstance(cam, Camera) else Camera.from_scene(cam)
+
+
+def _f3(v):
+    return (C.c_float * 3)(float(v[0]), float(v[1]), float(v[2]))
+
+
+def gen_primary_rays(mem: MemManager, cam, clip: float, width: int, height: int, rays: int, first: int = 0, count: int | None = None):
+    """gen_rays (main.cpp:52-66) on the device: the rays of pixels first .. first+count-1 into `rays` (32 bytes each); the bits of
+    scene.make_rays_primary.  cam: a Camera or the tuple scene.camera returns."""
+    if count is None:
+        count = width * height - first
+    _check(mem, mem._L.hagrid_gen_primary_rays(mem._ctx, C.byref(_camera(cam)), float(clip), int(width), int(height), int(first), int(count), C.c_void_p(rays)), "gen_primary_rays")
+
+
+def gen_bounce_rays(mem: MemManager, tris: int, rays: int, hits: int, num_rays: int, seed: int, bbox_min, bbox_max, out_rays: int,
+                    first: int = 0, tmax: float = 3.4028234663852886e38, redraw_misses: bool = True):
+    """scene.make_rays_bounce on the device (same bits): from rays and their hits to diffuse-bounce rays in `out_rays`."""
+    _check(mem, mem._L.hagrid_gen_bounce_rays(mem._ctx, C.c_void_p(tris), C.c_void_p(rays), C.c_void_p(hits), int(num_rays), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              int(first), _f3(bbox_min), _f3(bbox_max), float(tmax), BOUNCE_REDRAW_MISSES if redraw_misses else 0, C.c_void_p(out_rays)), "gen_bounce_rays")
+
+
+def shade_hits(mem: MemManager, hits: int, num_hits: int, mode: int, clip: float, bgra: int):
+    """update_surface (main.cpp:90-111) on the device: 4 bytes per pixel (B G R A) into `bgra`; scene.shade_hits states the formulas."""
+    _check(mem, mem._L.hagrid_shade_hits(mem._ctx, C.c_void_p(hits), int(num_hits), int(mode), float(clip), C.c_void_p(bgra)), "shade_hits")
+
+
+def accumulate_occlusion(mem: MemManager, occlusion_hits: int, num_rays: int, counts: int):
+    """counts[i] += occlusion_hits[i].id >= 0 (int32 per ray)."""
+    _check(mem, mem._L.hagrid_accumulate_occlusion(mem._ctx, C.c_void_p(occlusion_hits), int(num_rays), C.c_void_p(counts)), "accumulate_occlusion")
+
+
+def shade_occlusion(mem: MemManager, hits: int, counts: int, num_rays: int, samples: int, bgra: int):
+    """The ambient-occlusion picture of primary hits and their occlusion counts (scene.shade_occlusion)."""
+    _check(mem, mem._L.hagrid_shade_occlusion(mem._ctx, C.c_void_p(hits), C.c_void_p(counts), int(num_rays), int(samples), C.c_void_p(bgra)), "shade_occlusion")
+
+
+def frame_workspace_bytes(width: int, height: int, ao_samples: int = 0) -> int:
+    return int(_lib.load().hagrid_frame_workspace_bytes(int(width), int(height), int(ao_samples)))
+
+
+def frame_workspace_layout(width: int, height: int, ao_samples: int = 0) -> dict:
+    """Byte offsets of the sections of a frame workspace, as include/hagrid_amd.h documents them: every section at the next multiple of 256."""
+    n = int(width) * int(height)
+    up = lambda v: (v + 255) // 256 * 256
+    lay = {"rays": 0, "hits": up(32 * n)}
+    total = lay["hits"] + up(16 * n)
+    if ao_samples > 0:
+        lay["bounce_rays"] = total
+        lay["occlusion_hits"] = lay["bounce_rays"] + up(32 * n)
+        lay["counts"] = lay["occlusion_hits"] + up(16 * n)
+        total = lay["counts"] + up(4 * n)
+    lay["total"] = total
+    return lay
+
+
+def render_frame(grid: Grid, tris: int, cam, clip: float, width: int, height: int, workspace: int, bgra: int, mode: int = SHADE_DEPTH,
+                 ao_samples: int = 0, ao_radius: float = 0.0, seed: int = 0):
+    """One frame on the manager's stream: primary rays -> traversal -> pixels (hagrid_render_frame); nothing is copied or waited for.
+    workspace: frame_workspace_bytes(...) bytes of device memory; bgra: 4 * width * height bytes (e.g. a torch.uint8 tensor's data_ptr())."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_render_frame(mem._ctx, C.byref(grid.pod), C.c_void_p(tris), C.byref(_camera(cam)), float(clip), int(width), int(height), int(mode),
+                                           int(ao_samples), float(ao_radius), int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(workspace), C.c_void_p(bgra)), "render_frame")
+
+
 def profile(fn, mem: MemManager | None = None) -> float:
     """Milliseconds between two events on the manager's stream around fn() (profile.cu:5-18)."""
     mem = mem or _current
@@ -394,4 +466,6 @@ def algorithmic_bytes(stats: dict, compressed: bool, record_bytes: int = 32) -> 
 
 __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "expand_grid", "compress_grid", "build_all",
            "setup_traversal", "traverse_grid", "traverse_grid_stats", "profile", "algorithmic_bytes", "build_algorithmic_bytes", "HagridError",
-           "HIT_DTYPE", "CELL_DTYPE", "SMALL_CELL_DTYPE"]
+           "HIT_DTYPE", "CELL_DTYPE", "SMALL_CELL_DTYPE",
+           "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
+           "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES"]

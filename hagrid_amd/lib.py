@@ -38,6 +38,20 @@ class TraversalStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Camera(C.Structure):
+    """struct hagrid_camera (include/hagrid_amd.h; the reference's Camera, main.cpp:19-24): eye, dir, right, up."""
+    _fields_ = [("eye", C.c_float * 3), ("dir", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3)]
+
+    @classmethod
+    def from_scene(cls, cam) -> "Camera":
+        """From the tuple scene.camera returns: (eye, dir, right, up[, clip])."""
+        c = cls()
+        for name, v in zip(("eye", "dir", "right", "up"), cam[:4]):
+            for i in range(3):
+                getattr(c, name)[i] = float(v[i])              # float32 -> double -> float32: exact
+        return c
+
+
 MAX_MERGE_PASSES = 96
 
 
@@ -118,6 +132,13 @@ SIGNATURES = {
     "hagrid_set_ray_binning": (_i32, [_vp, _i32]),
     "hagrid_set_option": (_i32, [_vp, C.c_char_p, _i32]),
     "hagrid_traversal_image_info": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(_i64)]),
+    "hagrid_gen_primary_rays": (_i32, [_vp, C.POINTER(Camera), _f32, _i32, _i32, _i64, _i32, _vp]),
+    "hagrid_gen_bounce_rays": (_i32, [_vp, _vp, _vp, _vp, _i32, C.c_uint64, C.c_uint64, C.POINTER(_f32), C.POINTER(_f32), _f32, C.c_uint32, _vp]),
+    "hagrid_shade_hits": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp]),
+    "hagrid_accumulate_occlusion": (_i32, [_vp, _vp, _i32, _vp]),
+    "hagrid_shade_occlusion": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "hagrid_frame_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "hagrid_render_frame": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(Camera), _f32, _i32, _i32, _i32, _i32, _f32, C.c_uint64, _vp, _vp]),
 }
 
 # libhagrid_amd_kat.so (hagrid_amd/csrc/kat/hagrid_amd_kat.h): known-answer hooks and diagnostic instantiations -- tests/ and tools/ only

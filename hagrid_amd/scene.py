@@ -316,14 +316,25 @@ def make_rays_primary(bbox_min, bbox_max, width: int, height: int, first: int = 
     return rays
 
 
+def make_rays_inactive(num_rays: int) -> np.ndarray:
+    """Rays with an empty interval (org = 0, dir = (0,0,1), tmin = 0, tmax = -1): traversal answers id -1, t -1."""
+    out = np.zeros((num_rays, 8), dtype=np.float32)
+    out[:, 6] = np.float32(1.0); out[:, 7] = np.float32(-1.0)
+    return out
+
+
 def make_rays_bounce(tris: np.ndarray, rays: np.ndarray, hits: np.ndarray, bbox_min, bbox_max, seed: int,
-                     first: int = 0) -> np.ndarray:
+                     first: int = 0, tmax: float = float(FLT_MAX), redraw_misses: bool = True) -> np.ndarray:
     """Diffuse-bounce rays (BASELINE config 5): from each hit, org = p + 1e-4 * n, cosine-weighted
-    direction about the ray-facing normal from two PRNG floats keyed by the ray index; misses are
-    re-drawn as incoherent rays."""
+    direction about the ray-facing normal from two PRNG floats keyed by the ray index, tmax as given; misses are
+    re-drawn as incoherent rays (tmax = FLT_MAX), or with redraw_misses=False become inactive rays (make_rays_inactive).
+    The device form is hagrid_gen_bounce_rays (include/hagrid/frame.h: bounce_ray), bit for bit."""
     n_rays = rays.shape[0]
     hid = hits["id"]
-    out = make_rays_incoherent(bbox_min, bbox_max, n_rays, seed ^ 0x6D69737300000000, first)
+    if redraw_misses:
+        out = make_rays_incoherent(bbox_min, bbox_max, n_rays, seed ^ 0x6D69737300000000, first)
+    else:
+        out = make_rays_inactive(n_rays)
     hit_mask = hid >= 0
     if not hit_mask.any():
         return out
@@ -357,9 +368,54 @@ def make_rays_bounce(tris: np.ndarray, rays: np.ndarray, hits: np.ndarray, bbox_
     b[:, 0:3] = p + np.float32(1e-4) * n
     b[:, 3] = np.float32(0.0)
     b[:, 4:7] = d
-    b[:, 7] = FLT_MAX
+    b[:, 7] = np.float32(tmax)
     out[hit_mask] = b
     return out.astype(np.float32)
+
+
+SHADE_DEPTH, SHADE_GRAY, SHADE_HEAT = 0, 1, 2
+_GRADIENT = np.float32([[0, 0, 255], [0, 255, 255], [0, 128, 0], [255, 255, 0], [255, 0, 0]])      # R G B (main.cpp:69-75)
+
+
+def shade_hits(hits: np.ndarray, mode: int, clip: float = 0.0) -> np.ndarray:
+    """update_surface (main.cpp:68-111) in float32: (n, 4) uint8, B G R A with A = 255.  The device form is hagrid_shade_hits.
+    DEPTH: uint8(min(255 * t / clip, 255)) (negative values give 0); GRAY: uint8(min(255, id)), so -1 wraps to 255 as the reference's
+    uint8_t does; HEAT: the five-colour gradient of min(100, max(id, 0)) / 100."""
+    n = hits.shape[0]
+    out = np.empty((n, 4), dtype=np.uint8)
+    out[:, 3] = 255
+    hid = hits["id"].astype(np.int32)
+    if mode == SHADE_DEPTH:
+        if not clip > 0:
+            raise ValueError("the depth picture needs clip > 0")
+        v = np.float32(255.0) * hits["t"].astype(np.float32) / np.float32(clip)
+        v = np.minimum(np.maximum(v, np.float32(0.0)), np.float32(255.0))
+        out[:, 0:3] = v.astype(np.uint8)[:, None]
+    elif mode == SHADE_GRAY:
+        out[:, 0:3] = (np.minimum(255, hid) & 255).astype(np.uint8)[:, None]
+    elif mode == SHADE_HEAT:
+        k = np.minimum(100, np.maximum(hid, 0)).astype(np.float32) / np.float32(100.0)
+        s = np.float32(1.0) / np.float32(5.0)
+        i = np.minimum(4, (k * np.float32(5.0)).astype(np.int32))
+        j = np.minimum(4, i + 1)
+        t = ((k - i.astype(np.float32) * s) / s).astype(np.float32)
+        c = (np.float32(1.0) - t)[:, None] * _GRADIENT[i] + t[:, None] * _GRADIENT[j]
+        out[:, 0] = c[:, 2].astype(np.uint8); out[:, 1] = c[:, 1].astype(np.uint8); out[:, 2] = c[:, 0].astype(np.uint8)
+    else:
+        raise ValueError(f"unknown shading mode {mode}")
+    return out
+
+
+def shade_occlusion(hits: np.ndarray, counts: np.ndarray, samples: int) -> np.ndarray:
+    """The ambient-occlusion picture: B=G=R = 255 * (samples - counts) // samples where the PRIMARY hit has id >= 0, else 0; A = 255.
+    counts: how many of a pixel's `samples` occlusion rays were blocked (clamped to 0 .. samples).  The device form is hagrid_shade_occlusion."""
+    if samples <= 0:
+        raise ValueError("samples must be positive")
+    c = np.clip(np.asarray(counts, np.int64), 0, samples)
+    v = np.where(hits["id"] >= 0, 255 * (samples - c) // samples, 0).astype(np.uint8)
+    out = np.empty((hits.shape[0], 4), dtype=np.uint8)
+    out[:, 0:3] = v[:, None]; out[:, 3] = 255
+    return out
 
 
 def generate_parallel(gen, first: int, count: int, chunk: int = 1 << 20, threads: int | None = None) -> np.ndarray:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -276,6 +276,53 @@ int hagrid_set_option(hagrid_ctx* ctx, const char* key, int value);
  * reference id of slim 16-byte records (0: 32-byte records), bytes per record }, *image_bytes = its size (table + blocks, both layouts); either
  * pointer may be NULL.  HAGRID_EINVAL when the context holds no image of this grid. */
 int hagrid_traversal_image_info(hagrid_ctx* ctx, const hagrid_grid* grid, int32_t* format4, int64_t* image_bytes);
+
+/* ---- frames on the device (the per-frame work of the reference's front-end, main.cpp:591-621: gen_rays, traverse_grid, update_surface) ---- */
+/* Camera in, pixels out, nothing crossing the bus.  Every pointer below except `cam`, `bbox_min`, `bbox_max` is a DEVICE pointer (16-byte
+ * aligned where it holds rays or hits, 4-byte aligned for pixels and counts); all work is enqueued on the context's stream; nothing here
+ * synchronises with the host or copies to it.  The arithmetic is float32 without contraction, operation for operation that of
+ * hagrid_amd/scene.py (make_rays_primary, make_rays_bounce, make_rays_incoherent, shade_hits, shade_occlusion): the same bits.  The per-ray
+ * functions are include/hagrid/frame.h, callable from host code too. */
+typedef struct hagrid_camera { float eye[3], dir[3], right[3], up[3]; } hagrid_camera;      /* main.cpp:19-24; gen_camera of main.cpp:42-50 fills it */
+
+/* gen_rays (main.cpp:52-66) for the pixels first .. first+count-1 of a width x height image (pixel = y * width + x), ray i = pixel first+i:
+ * kx = 2*x/float(w) - 1, ky = 1 - 2*y/float(h), dir = cam.dir + cam.right*kx + cam.up*ky, org = eye, tmin = 0, tmax = clip. */
+int hagrid_gen_primary_rays(hagrid_ctx* ctx, const hagrid_camera* cam, float clip, int width, int height,
+                            int64_t first, int count, void* rays);
+
+/* The diffuse-bounce rule of BASELINE configuration 5 (scene.make_rays_bounce); ray i draws its random numbers by its global index first+i.
+ * Rays with a hit (hits[i].id >= 0, a PRIMITIVE id -- not a step count of "traverse.id_is_steps"): org = p + 1e-4*n, a cosine-weighted
+ * direction about the normal that faces the ray, tmin = 0, tmax = `tmax`.  Rays without: with HAGRID_BOUNCE_REDRAW_MISSES an incoherent ray
+ * as scene.make_rays_incoherent draws it (origin uniform in the box, tmin = 0, tmax = FLT_MAX: configuration 5); else an INACTIVE ray:
+ * org = 0, dir = (0,0,1), tmin = 0, tmax = -1, for which traversal answers id -1, t -1.  out_rays must not be `rays`. */
+#define HAGRID_BOUNCE_REDRAW_MISSES 1u
+int hagrid_gen_bounce_rays(hagrid_ctx* ctx, const void* tris, const void* rays, const void* hits, int num_rays,
+                           uint64_t seed, uint64_t first, const float bbox_min[3], const float bbox_max[3],
+                           float tmax, uint32_t flags, void* out_rays);
+
+/* update_surface (main.cpp:68-111): 4 bytes per pixel, B G R A, A = 255.  mode:
+ *   HAGRID_SHADE_DEPTH  B=G=R = uint8(min(255.0f * t / clip, 255.0f))  (negative values give 0; clip <= 0 is HAGRID_EINVAL)
+ *   HAGRID_SHADE_GRAY   B=G=R = uint8(min(255, id))
+ *   HAGRID_SHADE_HEAT   the reference's five-colour gradient of min(100, max(id, 0)) / 100.0f
+ * GRAY and HEAT read Hit.id as it is; with "traverse.id_is_steps" = 1 they are the reference viewer's pictures. */
+enum { HAGRID_SHADE_DEPTH = 0, HAGRID_SHADE_GRAY = 1, HAGRID_SHADE_HEAT = 2 };
+int hagrid_shade_hits(hagrid_ctx* ctx, const void* hits, int num_hits, int mode, float clip, void* bgra);
+
+/* Ambient occlusion: counts[i] += occlusion_hits[i].id >= 0 (int32 per ray), and the picture B=G=R = hits[i].id >= 0 ?
+ * 255 * (samples - counts[i]) / samples : 0 in integer arithmetic (counts clamped to 0 .. samples), A = 255; `hits` are the PRIMARY hits there. */
+int hagrid_accumulate_occlusion(hagrid_ctx* ctx, const void* occlusion_hits, int num_rays, void* counts);
+int hagrid_shade_occlusion(hagrid_ctx* ctx, const void* hits, const void* counts, int num_rays, int samples, void* bgra);
+
+/* One frame, all on the stream: primary rays -> hagrid_traverse_grid_ex -> pixels.  ao_samples = 0: hagrid_shade_hits(mode).
+ * ao_samples = S > 0: counts = 0; for s in 0 .. S-1: bounce rays (seed + s, first 0, tmax = ao_radius, misses inactive) -> traversal with
+ * HAGRID_TRAVERSE_ANY_HIT -> accumulate; then hagrid_shade_occlusion (mode is ignored; refused while "traverse.id_is_steps" = 1, the bounce
+ * rays need primitive ids).  The caller owns the workspace (hagrid_frame_workspace_bytes, 16-byte aligned); its sections, each at the next
+ * multiple of 256 bytes: rays (32 B per pixel) at offset 0, the primary hits (16 B) behind them, and with ao_samples > 0 the bounce rays
+ * (32 B), the occlusion hits (16 B) and the counts (4 B) -- so a caller can read the hits of the frame it just rendered. */
+size_t hagrid_frame_workspace_bytes(int width, int height, int ao_samples);
+int hagrid_render_frame(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const hagrid_camera* cam, float clip,
+                        int width, int height, int mode, int ao_samples, float ao_radius, uint64_t seed,
+                        void* workspace, void* bgra);
 
 
 #ifdef __cplusplus

@@ -10,6 +10,10 @@
 // Extension: --gpus N runs one process per GPU (this program re-executes itself N times): rank 0 builds, the grid is broadcast
 // once with RCCL (ncclBroadcast from C++, include/hagrid/multi_gpu.h), every rank traces its contiguous share of the rays, the
 // report is the reference's with whole-job figures.  --save-grid / --load-grid write / read the grid blob.
+// Extension: the frame stays on the device (include/hagrid/frame.h).  The primary rays are generated there (each rank its own pixel range under
+// --gpus), and --ppm FILE writes the frame the way the reference's viewer would show it: traced and shaded by hagrid_render_frame, --display
+// depth | gray | heat (main.cpp:90-111; gray and heat colour by the traversal step count, as the viewer does), or with --ao N as ambient
+// occlusion from N short diffuse rays per pixel (--ao-radius R, default a tenth of the scene size).
 //
 //   g++ -std=c++11 -O2 -DHOST= -DDEVICE= -Iinclude tools/hagrid_cli.cpp -o hagrid_cli -Lhagrid_amd -lhagrid_amd -lamdhip64
 #include <algorithm>
@@ -31,6 +35,7 @@
 #include <unistd.h>
 
 #include "hagrid/build.h"
+#include "hagrid/frame.h"
 #include "hagrid/load_obj.h"
 #include "hagrid/mem_manager.h"
 #include "hagrid/multi_gpu.h"
@@ -43,8 +48,9 @@ using namespace hagrid;
 namespace {
 
 struct Options {
-    std::string scene, ray_file, out_image, steps_image, save_grid, load_grid;
-    int gpus = 0;
+    std::string scene, ray_file, out_image, steps_image, save_grid, load_grid, display = "depth", ppm_image;
+    int gpus = 0, ao_samples = 0;
+    float ao_radius = 0;
     float top_density = 0.12f, snd_density = 2.4f, alpha = 0.995f;
     int exp_iters = 3, width = 1024, height = 1024;
     float clip = 0, fov = 60;
@@ -82,6 +88,10 @@ bool parse(int argc, char** argv, Options& o, std::vector<OptDesc>& table) {
         {"-g", "--gpus", INT, &o.gpus, "(extension) one process per GPU: the grid is built once and broadcast (RCCL), the rays are sharded"},
         {"-sg", "--save-grid", STRING, &o.save_grid, "(extension) writes the finished grid (and the triangles) to a file"},
         {"-lg", "--load-grid", STRING, &o.load_grid, "(extension) reads grid and triangles from a file instead of building"},
+        {"-d", "--display", STRING, &o.display, "(extension) what --ppm shows: depth (default), gray or heat (the viewer's modes; gray and heat colour by step count)"},
+        {"-p", "--ppm", STRING, &o.ppm_image, "(extension) writes the frame, traced and shaded on the device, as a binary PPM (P6)"},
+        {"-ao", "--ao", INT, &o.ao_samples, "(extension) --ppm shows ambient occlusion from this many diffuse rays per pixel"},
+        {"-aor", "--ao-radius", FLOAT, &o.ao_radius, "(extension) length of the ambient-occlusion rays (default: 0.1 x the scene size)"},
     };
     bool have_scene = false;
     for (int i = 1; i < argc; i++) {
@@ -101,6 +111,8 @@ bool parse(int argc, char** argv, Options& o, std::vector<OptDesc>& table) {
         else if (d->kind == FLOAT) *static_cast<float*>(d->dst) = strtof(v, nullptr);
         else *static_cast<std::string*>(d->dst) = v;
     }
+    if (o.display != "depth" && o.display != "gray" && o.display != "heat") { std::cerr << "Unknown display mode: " << o.display << std::endl; return false; }
+    if (o.ao_samples < 0) { std::cerr << "Negative number of ambient-occlusion rays" << std::endl; return false; }
     if (!have_scene && !o.help && o.load_grid.empty()) { std::cerr << "No model specified" << std::endl; return false; }
     return true;
 }
@@ -121,10 +133,7 @@ Tri make_tri(const vec3& v0, const vec3& v1, const vec3& v2) {     // packing of
     return Tri(v0, n.x, e1, n.y, e2, n.z);
 }
 
-uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31);
-}
-float uniform01(uint64_t seed, uint64_t i) { return float(mix64(seed + (i + 1) * 0x9E3779B97F4A7C15ull) >> 40) * (1.0f / 16777216.0f); }
+using frame::uniform01;     // hagrid_amd/scene.py:uniform01
 
 void make_soup(int n, std::vector<Tri>& tris) {     // hagrid_amd/scene.py:make_soup, same bits
     const uint64_t seed = 0x48414752494400ull + uint64_t(n);
@@ -308,38 +317,38 @@ int main(int argc, char** argv) {
     if (opts.clip <= 0) opts.clip = scene_size;
 
     std::vector<Ray> host_rays;
-    if (!opts.ray_file.empty()) {
+    frame::Camera cam;
+    const bool frame_mode = opts.ray_file.empty();
+    if (!frame_mode) {
         if (root) std::cout << "Entering benchmark mode" << std::endl;
         if (!load_rays(opts.ray_file, host_rays, opts.tmin, opts.tmax)) { std::cerr << "Cannot load ray file" << std::endl; return 1; }
     } else {
-        // one frame of the viewer's initial view (main.cpp:572-579, :592-598): eye at the scene centre, looking down +z
+        // one frame of the viewer's initial view (main.cpp:572-579, :592-598): eye at the scene centre, looking down +z.  The camera vectors are
+        // this front-end's own (tanf of a float argument); the rays come from them on the device (gen_rays, main.cpp:52-66)
         if (root) std::cout << "Tracing one " << opts.width << "x" << opts.height << " frame (no interactive viewer in this front-end)" << std::endl;
+        if (opts.width <= 0 || opts.height <= 0) { std::cerr << "The viewport must have a positive width and height" << std::endl; return 1; }
         const vec3 eye = center, forward(0.0f, 0.0f, 1.0f), up(0.0f, 1.0f, 0.0f);
         const float f = tanf(float(M_PI) * opts.fov / 360.0f), ratio = float(opts.width) / float(opts.height);
         const vec3 dir = normalize((eye + forward * 100.0f) - eye), right = normalize(cross(dir, up)) * (f * ratio), cup = normalize(cross(right, dir)) * f;
-        host_rays.resize(size_t(opts.width) * opts.height);
-        for (int y = 0; y < opts.height; y++)
-            for (int x = 0; x < opts.width; x++) {
-                const float kx = 2 * x / float(opts.width) - 1, ky = 1 - 2 * y / float(opts.height);
-                host_rays[size_t(y) * opts.width + x] = Ray(eye, 0.0f, dir + right * kx + cup * ky, opts.clip);
-            }
+        cam.eye = eye; cam.dir = dir; cam.right = right; cam.up = cup;
     }
     // this rank's contiguous share of the batch (the whole batch without --gpus)
-    const size_t all_rays = host_rays.size();
+    const size_t all_rays = frame_mode ? size_t(opts.width) * size_t(opts.height) : host_rays.size();
     size_t first = 0, last = all_rays;
     shard_range(all_rays, rank, world, first, last);
-    if (world > 1) host_rays = std::vector<Ray>(host_rays.begin() + first, host_rays.begin() + last);
-    Ray* rays = mem.alloc<Ray>(host_rays.size());
-    Hit* hits = mem.alloc<Hit>(host_rays.size());
-    mem.copy<Copy::HST_TO_DEV>(rays, host_rays.data(), host_rays.size());
+    const size_t num_rays = last - first;
+    Ray* rays = mem.alloc<Ray>(num_rays);
+    Hit* hits = mem.alloc<Hit>(num_rays);
+    if (frame_mode) { if (num_rays) frame::gen_rays(cam, rays, opts.clip, opts.width, opts.height, int64_t(first), int(num_rays)); }
+    else mem.copy<Copy::HST_TO_DEV>(rays, host_rays.data() + first, num_rays);
     auto trace = [&] {
-        if (opts.any_hit) traverse_grid_any_hit(grid, tris, rays, hits, int(host_rays.size()));
-        else              traverse_grid(grid, tris, rays, hits, int(host_rays.size()));
+        if (opts.any_hit) traverse_grid_any_hit(grid, tris, rays, hits, int(num_rays));
+        else              traverse_grid(grid, tris, rays, hits, int(num_rays));
     };
     for (int i = 0; i < opts.bench_warmup; i++) trace();
     std::vector<float> timings;
     for (int i = 0; i < std::max(opts.bench_iter, 1); i++) timings.push_back(profile(trace));
-    std::vector<Hit> host_hits(host_rays.size());
+    std::vector<Hit> host_hits(num_rays);
     mem.copy<Copy::DEV_TO_HST>(host_hits.data(), hits, host_hits.size());
     int intr = 0;
     for (const auto& h : host_hits) intr += h.id >= 0;
@@ -359,15 +368,16 @@ int main(int argc, char** argv) {
     if (!opts.out_image.empty() && opts.ray_file.empty() && world == 1) {
         std::ofstream img(opts.out_image, std::ofstream::binary);
         img << "P5\n" << opts.width << " " << opts.height << "\n255\n";
-        for (const auto& h : host_hits) img.put(char(h.id >= 0 ? std::min(255.0f, 255.0f * h.t / opts.clip) : 255));
+        // (a miss is 255 by id.  The conversions go through unsigned char: char(255.0f) is out of range for a signed char, and the compiler had folded it to 127)
+        for (const auto& h : host_hits) img.put(char(h.id >= 0 ? (unsigned char)(std::min(255.0f, 255.0f * h.t / opts.clip)) : (unsigned char)(255)));
     }
     if (!opts.steps_image.empty() && opts.ray_file.empty() && world == 1) {
         // the picture the reference's viewer shows: its kernel returns the step count in Hit::id (traverse.cu:80,93) and
         // main.cpp:100-107 maps it to a colour; here the count comes from the statistics entry point
-        int* steps = mem.alloc<int>(host_rays.size());
+        int* steps = mem.alloc<int>(num_rays);
         hagrid_grid pod = detail::to_pod(grid);
-        detail::check(detail::current_ctx(), hagrid_traverse_grid_stats(detail::current_ctx(), &pod, tris, rays, hits, int(host_rays.size()), steps, nullptr));
-        std::vector<int> host_steps(host_rays.size());
+        detail::check(detail::current_ctx(), hagrid_traverse_grid_stats(detail::current_ctx(), &pod, tris, rays, hits, int(num_rays), steps, nullptr));
+        std::vector<int> host_steps(num_rays);
         mem.copy<Copy::DEV_TO_HST>(host_steps.data(), steps, host_steps.size());
         const int top = std::max(1, *std::max_element(host_steps.begin(), host_steps.end()));
         std::ofstream img(opts.steps_image, std::ofstream::binary);
@@ -375,6 +385,23 @@ int main(int argc, char** argv) {
         for (int v : host_steps) img.put(char(255 * v / top));
         std::cout << "Steps per ray: max " << top << ", mean " << std::accumulate(host_steps.begin(), host_steps.end(), 0.0) / host_steps.size() << std::endl;
         mem.free(steps);
+    }
+    if (!opts.ppm_image.empty() && frame_mode && world == 1) {
+        // the frame as the viewer shows it, without leaving the device until it is a picture: rays, traversal and shading on the stream
+        void* workspace = mem.alloc<char>(frame::frame_workspace_bytes(opts.width, opts.height, opts.ao_samples));
+        unsigned char* bgra = mem.alloc<unsigned char>(all_rays * 4);
+        const frame::ShadeMode mode = opts.display == "gray" ? frame::SHADE_GRAY : opts.display == "heat" ? frame::SHADE_HEAT : frame::SHADE_DEPTH;
+        const bool by_steps = opts.ao_samples == 0 && mode != frame::SHADE_DEPTH;      // the viewer's gray and heat pictures colour by step count
+        if (by_steps) detail::check(detail::current_ctx(), hagrid_set_option(detail::current_ctx(), "traverse.id_is_steps", 1));
+        frame::render_frame(grid, tris, cam, opts.clip, opts.width, opts.height, mode, opts.ao_samples,
+                            opts.ao_radius > 0 ? opts.ao_radius : 0.1f * scene_size, 0x414F, workspace, bgra);
+        if (by_steps) detail::check(detail::current_ctx(), hagrid_set_option(detail::current_ctx(), "traverse.id_is_steps", 0));
+        std::vector<unsigned char> px(all_rays * 4);
+        mem.copy<Copy::DEV_TO_HST>(px.data(), bgra, px.size());
+        std::ofstream img(opts.ppm_image, std::ofstream::binary);
+        img << "P6\n" << opts.width << " " << opts.height << "\n255\n";
+        for (size_t i = 0; i < all_rays; i++) { img.put(char(px[4 * i + 2])); img.put(char(px[4 * i + 1])); img.put(char(px[4 * i])); }
+        mem.free(workspace); mem.free(bgra);
     }
     // Everything the caller asked for is on stdout and in its files (the image outputs above are work, not teardown: they may take as
     // long as they take).  What follows returns device memory and takes the runtime down; a runtime that does not come back from that
