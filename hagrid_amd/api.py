@@ -338,6 +338,17 @@ def traverse_grid(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, fl
     _check(mem, mem._L.hagrid_traverse_grid_ex(mem._ctx, C.byref(grid.pod), C.c_void_p(tris), C.c_void_p(rays), C.c_void_p(hits), int(num_rays), int(flags)), "traverse_grid")
 
 
+MAX_HITS = 8             # HAGRID_MAX_HITS
+
+
+def traverse_grid_multi(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, k: int, flags: int = 0):
+    """Extension (hagrid_traverse_grid_multi): the k nearest intersections of every ray, sorted by (t, id), into hits[i * k .. i * k + k - 1]
+    (num_rays * k Hit records); unused slots are misses (id -1, t = tmax).  1 <= k <= MAX_HITS; flags: 0 | UVS.  Walks the construction
+    format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_traverse_grid_multi(mem._ctx, C.byref(grid.pod), C.c_void_p(tris), C.c_void_p(rays), C.c_void_p(hits), int(num_rays), int(k), int(flags)), "traverse_grid_multi")
+
+
 def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, steps: int = 0) -> dict:
     mem = grid.mem or _current
     st = TraversalStats()
@@ -378,6 +389,12 @@ def gen_bounce_rays(mem: MemManager, tris: int, rays: int, hits: int, num_rays: 
 def shade_hits(mem: MemManager, hits: int, num_hits: int, mode: int, clip: float, bgra: int):
     """update_surface (main.cpp:90-111) on the device: 4 bytes per pixel (B G R A) into `bgra`; scene.shade_hits states the formulas."""
     _check(mem, mem._L.hagrid_shade_hits(mem._ctx, C.c_void_p(hits), int(num_hits), int(mode), float(clip), C.c_void_p(bgra)), "shade_hits")
+
+
+def shade_layers(mem: MemManager, hits: int, num_rays: int, k: int, clip: float, opacity: float, bgra: int):
+    """The layered picture of the hit lists of traverse_grid_multi (k records per pixel) on the device: every surface a layer of the given
+    opacity in its depth colour, front to back over white; scene.shade_layers states the formula."""
+    _check(mem, mem._L.hagrid_shade_layers(mem._ctx, C.c_void_p(hits), int(num_rays), int(k), float(clip), float(opacity), C.c_void_p(bgra)), "shade_layers")
 
 
 def accumulate_occlusion(mem: MemManager, occlusion_hits: int, num_rays: int, counts: int):
@@ -468,4 +485,5 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "setup_traversal", "traverse_grid", "traverse_grid_stats", "profile", "algorithmic_bytes", "build_algorithmic_bytes", "HagridError",
            "HIT_DTYPE", "CELL_DTYPE", "SMALL_CELL_DTYPE",
            "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
-           "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES"]
+           "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
+           "traverse_grid_multi", "shade_layers", "MAX_HITS"]

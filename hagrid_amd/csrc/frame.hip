@@ -70,6 +70,13 @@ __global__ void __launch_bounds__(kBlock) frame_shade_occlusion_kernel(const flo
     bgra[i] = hf::shade_occlusion(__float_as_int(hits[i].x), counts[i], samples);
 }
 
+// k Hit records per pixel, read where they lie (the list of pixel i starts at hits[i * k])
+__global__ void __launch_bounds__(kBlock) frame_shade_layers_kernel(const Hit* __restrict__ hits, int n, int k, float clip, float opacity, uint32_t* __restrict__ bgra) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    bgra[i] = hf::shade_layers(hits + size_t(i) * size_t(k), k, clip, opacity);
+}
+
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -137,6 +144,22 @@ extern "C" int hagrid_shade_hits(hagrid_ctx* ctx, const void* hits, int num_hits
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_hits) * 4);
     frame_shade_hits_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_hits, mode, clip, static_cast<uint32_t*>(bgra));
+    HG_DBG(ctx);
+    HG_HIP(ctx, hipGetLastError());
+    return HAGRID_OK;
+}
+
+extern "C" int hagrid_shade_layers(hagrid_ctx* ctx, const void* hits, int num_rays, int k, float clip, float opacity, void* bgra) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (!hits || !bgra) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: null hit or pixel buffer");
+    if (!aligned(hits, 16) || !aligned(bgra, 4)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: hits must be 16-byte aligned, pixels 4-byte aligned");
+    if (num_rays <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: num_rays must be positive");
+    if (k < 1 || k > HAGRID_MAX_HITS) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: k must be 1 .. HAGRID_MAX_HITS");
+    if (!(clip > 0.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: the depth colours need clip > 0");
+    if (!(opacity > 0.0f && opacity <= 1.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: opacity must be in (0, 1]");
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+    trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
+    frame_shade_layers_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const Hit*>(hits), num_rays, k, clip, opacity, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

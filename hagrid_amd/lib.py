@@ -129,12 +129,14 @@ SIGNATURES = {
     "hagrid_traverse_grid": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32]),
     "hagrid_traverse_grid_ex": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, C.c_uint32]),
     "hagrid_traverse_grid_stats": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _vp, C.POINTER(TraversalStats)]),
+    "hagrid_traverse_grid_multi": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _i32, C.c_uint32]),
     "hagrid_set_ray_binning": (_i32, [_vp, _i32]),
     "hagrid_set_option": (_i32, [_vp, C.c_char_p, _i32]),
     "hagrid_traversal_image_info": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(_i64)]),
     "hagrid_gen_primary_rays": (_i32, [_vp, C.POINTER(Camera), _f32, _i32, _i32, _i64, _i32, _vp]),
     "hagrid_gen_bounce_rays": (_i32, [_vp, _vp, _vp, _vp, _i32, C.c_uint64, C.c_uint64, C.POINTER(_f32), C.POINTER(_f32), _f32, C.c_uint32, _vp]),
     "hagrid_shade_hits": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp]),
+    "hagrid_shade_layers": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
     "hagrid_accumulate_occlusion": (_i32, [_vp, _vp, _i32, _vp]),
     "hagrid_shade_occlusion": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "hagrid_frame_workspace_bytes": (_sz, [_i32, _i32, _i32]),

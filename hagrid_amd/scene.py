@@ -406,6 +406,32 @@ def shade_hits(hits: np.ndarray, mode: int, clip: float = 0.0) -> np.ndarray:
     return out
 
 
+def shade_layers(hits: np.ndarray, k: int, clip: float, opacity: float) -> np.ndarray:
+    """The picture of sorted hit lists (traverse_grid_multi: hits of shape (n, k) or (n * k,), HIT_DTYPE) in float32: every slot with id >= 0
+    is a layer of the given opacity in its depth colour min(max(255 * t / clip, 0), 255), composited front to back over white:
+    acc = 0, T = 1; per layer acc = acc + (T * opacity) * c, T = T * (1 - opacity); then acc = acc + T * 255; B = G = R = uint8(min(acc, 255)),
+    A = 255.  The device form is hagrid_shade_layers, the per-pixel function shade_layers of include/hagrid/frame.h."""
+    if not clip > 0:
+        raise ValueError("the depth colours need clip > 0")
+    if not 0 < opacity <= 1:
+        raise ValueError("opacity must be in (0, 1]")
+    h = np.asarray(hits).reshape(-1, k)
+    op = np.float32(opacity)
+    acc = np.zeros(h.shape[0], dtype=np.float32); T = np.ones(h.shape[0], dtype=np.float32)
+    for j in range(k):
+        on = h["id"][:, j] >= 0
+        with np.errstate(over="ignore"):          # an unused slot holds tmax, often FLT_MAX: its colour is computed and not used
+            c = np.float32(255.0) * h["t"][:, j].astype(np.float32) / np.float32(clip)
+        c = np.minimum(np.maximum(c, np.float32(0.0)), np.float32(255.0))
+        acc = np.where(on, acc + (T * op) * c, acc).astype(np.float32)
+        T = np.where(on, T * (np.float32(1.0) - op), T).astype(np.float32)
+    acc = acc + T * np.float32(255.0)
+    out = np.empty((h.shape[0], 4), dtype=np.uint8)
+    out[:, 0:3] = np.minimum(acc, np.float32(255.0)).astype(np.uint8)[:, None]
+    out[:, 3] = 255
+    return out
+
+
 def shade_occlusion(hits: np.ndarray, counts: np.ndarray, samples: int) -> np.ndarray:
     """The ambient-occlusion picture: B=G=R = 255 * (samples - counts) // samples where the PRIMARY hit has id >= 0, else 0; A = 255.
     counts: how many of a pixel's `samples` occlusion rays were blocked (clamped to 0 .. samples).  The device form is hagrid_shade_occlusion."""

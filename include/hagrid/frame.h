@@ -137,6 +137,21 @@ HOST DEVICE inline uint32_t shade_hit(const Hit& hit, int mode, float clip) {
     return gradient(float(min(100, max(hit.id, 0))) / 100.0f);
 }
 
+/// the pixel of a ray's sorted hit list (k records, hagrid_traverse_grid_multi): every surface a layer of the given opacity in its
+/// depth colour (shade_hit's depth mode), composited front to back over white; every sum in the order written (scene.shade_layers)
+HOST DEVICE inline uint32_t shade_layers(const Hit* hits, int k, float clip, float opacity) {
+    float acc = 0.0f, T = 1.0f;
+    for (int j = 0; j < k; j++) {
+        if (hits[j].id < 0) continue;
+        const float c = min(max(255.0f * hits[j].t / clip, 0.0f), 255.0f);
+        acc = acc + (T * opacity) * c;
+        T = T * (1.0f - opacity);
+    }
+    acc = acc + T * 255.0f;
+    const uint32_t g = uint32_t(min(acc, 255.0f));
+    return pack_bgra(g, g, g);
+}
+
 /// the ambient-occlusion pixel of a primary hit whose `samples` occlusion rays were blocked `count` times
 HOST DEVICE inline uint32_t shade_occlusion(int primary_id, int count, int samples) {
     const int c = primary_id >= 0 ? 255 * (samples - min(max(count, 0), samples)) / samples : 0;
@@ -171,6 +186,11 @@ inline void gen_bounce_rays(const Tri* tris, const Ray* rays, const Hit* hits, i
 /// update_surface (main.cpp:90-111) into a device buffer of 4 bytes per pixel (B G R A)
 inline void shade_hits(const Hit* hits, int num_hits, ShadeMode mode, float clip, void* bgra) {
     hagrid::detail::check(hagrid::detail::current_ctx(), hagrid_shade_hits(hagrid::detail::current_ctx(), hits, num_hits, int(mode), clip, bgra));
+}
+
+/// the layered picture of num_rays hit lists of k records each (traverse_grid_multi) into a device buffer of 4 bytes per pixel
+inline void shade_layers(const Hit* hits, int num_rays, int k, float clip, float opacity, void* bgra) {
+    hagrid::detail::check(hagrid::detail::current_ctx(), hagrid_shade_layers(hagrid::detail::current_ctx(), hits, num_rays, k, clip, opacity, bgra));
 }
 
 inline size_t frame_workspace_bytes(int w, int h, int ao_samples) { return hagrid_frame_workspace_bytes(w, h, ao_samples); }

@@ -36,6 +36,13 @@ inline void traverse_grid_with_uvs(const Grid& grid, const Tri* tris, const Ray*
     detail::check(detail::current_ctx(), hagrid_traverse_grid_ex(detail::current_ctx(), &p, tris, rays, hits, num_rays, HAGRID_TRAVERSE_UVS));
 }
 
+/// Extension: the k nearest intersections of every ray, sorted by (t, id), in hits[i * k .. i * k + k - 1]; unused slots are misses
+/// (id -1, t = tmax).  1 <= k <= HAGRID_MAX_HITS; the semantics are in multi_hit.h and hagrid_amd.h (hagrid_traverse_grid_multi).
+inline void traverse_grid_multi(const Grid& grid, const Tri* tris, const Ray* rays, Hit* hits, int num_rays, int k, bool with_uvs = false) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_traverse_grid_multi(detail::current_ctx(), &p, tris, rays, hits, num_rays, k, with_uvs ? HAGRID_TRAVERSE_UVS : 0u));
+}
+
 /// Extension: independent batches in flight.  Every MemManager is a context with a stream of its own (hagrid_ctx_set_stream on
 /// mem.context()); `share_traversal(dst, src)` lets `dst` traverse with the traversal image setup_traversal built in `src`, and the
 /// overload below traverses on a named manager instead of the current one.  Two 1M-ray batches in flight take 0.118 ms each

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -237,6 +237,28 @@ int hagrid_traverse_grid_stats(hagrid_ctx* ctx, const hagrid_grid* grid, const v
                                const void* rays, void* hits, int num_rays,
                                void* steps, hagrid_traversal_stats* stats);
 
+/* Extension (no reference counterpart): MULTI-HIT traversal -- the first k surfaces along every ray, sorted (transparency, x-ray
+ * pictures, thickness and inside / outside queries).  An INTERSECTION of ray i with triangle j exists exactly when
+ * intersect_prim_ray(tri[j], Ray(org, tmin, dir, tmax), j, h) of include/hagrid/prims.h accepts it with the ray's own, unshrunk tmin
+ * and tmax; its value is h.t (with HAGRID_TRAVERSE_UVS also h.u, h.v).  hits holds num_rays * k 16-byte Hit records: hits[i*k ..
+ * i*k + k-1] are the min(k, number of intersections) intersections of ray i that are smallest in the order (t ascending, then id
+ * ascending), in that order; unused slots hold id = -1, t = tmax, u = v = 0 (a miss of hagrid_traverse_grid); an inactive ray
+ * (tmax = -1) gets k such slots.  So:
+ *   - the list for k is a prefix of the list for k + 1;
+ *   - k = 1 is NOT promised to equal hagrid_traverse_grid bit for bit: the nearest-hit walk shrinks tmax in its scaled comparison and
+ *     breaks ties in t by list order (the two differ in a ray or two of ten thousand on a mesh);
+ *   - calling hagrid_traverse_grid k times with tmin = nextafter(t) is NOT this query: intersect_prim_ray compares t with
+ *     abs_det * tmin in the scaled domain, so the triangle just found is accepted again.
+ * flags: 0 or HAGRID_TRAVERSE_UVS.  Asynchronous on the context's stream.  One launch walks the CONSTRUCTION format in buffer order
+ * with the list in registers (hagrid_amd/csrc/trav_multi.hip): the traversal image, hagrid_set_ray_binning, tile packets and the
+ * learned tile order are not applied, and the hints kept for the nearest-hit path stay untouched.  HAGRID_EINVAL: k < 1 or
+ * k > HAGRID_MAX_HITS; any flag other than HAGRID_TRAVERSE_UVS (HAGRID_TRAVERSE_ANY_HIT contradicts k hits); a grid released by
+ * hagrid_grid_release_for_traversal; a context with "traverse.id_is_steps" = 1.  HAGRID_ERANGE: num_rays * k beyond 2^31 - 1.
+ * num_rays = 0 is HAGRID_OK. */
+#define HAGRID_MAX_HITS 8
+int hagrid_traverse_grid_multi(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
+                               const void* rays, void* hits, int num_rays, int k, uint32_t flags);
+
 /* Extension (no reference counterpart): spatial binning of the ray batch before traversal.  mode 0 (default): rays
  * are traversed in buffer order, as the reference does.  mode 1: each hagrid_traverse_grid call first bins the rays by
  * the position where they enter the grid (512 Morton-ordered bins, counting sort on the device) and traverses them in
@@ -307,6 +329,14 @@ int hagrid_gen_bounce_rays(hagrid_ctx* ctx, const void* tris, const void* rays, 
  * GRAY and HEAT read Hit.id as it is; with "traverse.id_is_steps" = 1 they are the reference viewer's pictures. */
 enum { HAGRID_SHADE_DEPTH = 0, HAGRID_SHADE_GRAY = 1, HAGRID_SHADE_HEAT = 2 };
 int hagrid_shade_hits(hagrid_ctx* ctx, const void* hits, int num_hits, int mode, float clip, void* bgra);
+
+/* The picture of the hit lists of hagrid_traverse_grid_multi (k records per pixel): every surface a layer of the given opacity in its
+ * depth colour, composited front to back over white, in float32, operation for operation (scene.shade_layers):
+ *   acc = 0, T = 1; for each slot j < k with id >= 0: c = min(max(255.0f * t_j / clip, 0.0f), 255.0f), acc = acc + (T * opacity) * c,
+ *   T = T * (1.0f - opacity); then acc = acc + T * 255.0f; B = G = R = uint8(min(acc, 255.0f)), A = 255.
+ * With opacity = 1 a pixel that hit is the HAGRID_SHADE_DEPTH pixel of its first slot.  HAGRID_EINVAL: clip <= 0, opacity outside (0, 1],
+ * k outside 1 .. HAGRID_MAX_HITS. */
+int hagrid_shade_layers(hagrid_ctx* ctx, const void* hits, int num_rays, int k, float clip, float opacity, void* bgra);
 
 /* Ambient occlusion: counts[i] += occlusion_hits[i].id >= 0 (int32 per ray), and the picture B=G=R = hits[i].id >= 0 ?
  * 255 * (samples - counts[i]) / samples : 0 in integer arithmetic (counts clamped to 0 .. samples), A = 255; `hits` are the PRIMARY hits there. */
