@@ -435,6 +435,65 @@ def render_frame(grid: Grid, tris: int, cam, clip: float, width: int, height: in
                                            int(ao_samples), float(ao_radius), int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(workspace), C.c_void_p(bgra)), "render_frame")
 
 
+# ---- scenes on the device (include/hagrid_amd.h "scenes on the device", include/hagrid/assemble.h) -------------------------
+
+class MeshScene:
+    """A scene of indexed meshes and instances whose Tri array is assembled ON THE DEVICE (hagrid_scene_create / hagrid_scene_assemble): what comes
+    before build_grid in a frame loop.  meshes: a list of (vertices_ptr, num_vertices, indices_ptr_or_0, num_tris[, stride = 12]) -- vertices are
+    float32 x, y, z records `stride` bytes apart, indices int32 triples (0: triangle p uses vertices 3p, 3p+1, 3p+2).  instance_mesh: the mesh every
+    instance places (None: one instance per mesh, in order).  scene.assemble_tris states the result in numpy, bit for bit.
+
+    Addresses are plain integers, like everywhere in this module: a torch tensor goes in as t.data_ptr().  The scene keeps the ADDRESSES, not
+    copies -- the buffers are read at every assemble(), so a simulation may rewrite the vertices in place between frames -- which means the tensors
+    must stay alive (and must not be reallocated) for as long as the scene is used.  The launch runs on the manager's stream:
+    mem.use_stream(torch.cuda.current_stream().cuda_stream) orders it after the torch work that wrote the tensors."""
+
+    def __init__(self, mem: MemManager, meshes, instance_mesh=None):
+        self.mem = mem
+        self._scene = None
+        recs = (_lib.Mesh * max(len(meshes), 1))()
+        for r, m in zip(recs, meshes):
+            r.vertices, r.num_vertices, r.indices, r.num_tris = (m[0] or None), int(m[1]), (m[2] or None), int(m[3])
+            r.vertex_stride = int(m[4]) if len(m) > 4 else 12
+        if instance_mesh is None:
+            inst, n_inst = None, len(meshes)
+        else:
+            n_inst = len(instance_mesh)
+            inst = (C.c_int32 * max(n_inst, 1))(*[int(k) for k in instance_mesh])
+        h = C.c_void_p()
+        _check(mem, mem._L.hagrid_scene_create(mem._ctx, recs, len(meshes), inst, n_inst, C.byref(h)), "scene_create")
+        self._scene = h
+        self.num_instances = n_inst
+        self.num_tris = self.first_tri(n_inst)
+
+    def first_tri(self, instance: int) -> int:
+        """First output triangle of an instance; instance = num_instances gives the total."""
+        return _check(self.mem, self.mem._L.hagrid_scene_first_tri(self._scene, int(instance)), "scene_first_tri")
+
+    def assemble(self, transforms: int, tris: int, origins: int = 0):
+        """One launch on the manager's stream: transforms (12 float32 per instance, or 0) and the meshes' buffers in, num_tris Tri records (48 bytes
+        each, 16-byte aligned) out; origins (or 0): int32 pairs (instance, triangle within its mesh) per output triangle."""
+        _check(self.mem, self.mem._L.hagrid_scene_assemble(self.mem._ctx, self._scene, C.c_void_p(transforms or 0), C.c_void_p(tris or 0), C.c_void_p(origins or 0)), "scene_assemble")
+
+    def bad_indices(self) -> int:
+        """Output triangles of the assemble() calls since the last query that named a vertex outside their mesh (each became the degenerate
+        triangle on vertex 0); waits for the stream and resets the count."""
+        n = C.c_int64(0)
+        _check(self.mem, self.mem._L.hagrid_scene_bad_indices(self.mem._ctx, self._scene, C.byref(n)), "scene_bad_indices")
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_scene", None) and getattr(self.mem, "_ctx", None):
+            self.mem._L.hagrid_scene_destroy(self.mem._ctx, self._scene)
+        self._scene = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def profile(fn, mem: MemManager | None = None) -> float:
     """Milliseconds between two events on the manager's stream around fn() (profile.cu:5-18)."""
     mem = mem or _current
@@ -486,4 +545,4 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "HIT_DTYPE", "CELL_DTYPE", "SMALL_CELL_DTYPE",
            "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
-           "traverse_grid_multi", "shade_layers", "MAX_HITS"]
+           "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene"]

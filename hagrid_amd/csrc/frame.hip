@@ -1,6 +1,6 @@
 // frame.hip -- a frame on the device: primary rays, bounce rays, shading, ambient occlusion (include/hagrid_amd.h "frames on the device").
 //
-// Five streaming kernels, one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
+// Five streaming kernels (four for the frame -- the two ambient-occlusion steps are one, with a mode argument -- and the layered picture of multi-hit lists), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
 // host program calls); the kernels only move the records: a Ray is two float4 and a Hit one, loaded and stored as such (16-byte accesses,
 // what the traversal kernels read: rays[2 * i], rays[2 * i + 1]), a pixel is one 32-bit word.  Mode, miss rule and flags are kernel
 // arguments, not template parameters: one kernel each.  hagrid_render_frame strings them together with hagrid_traverse_grid_ex on the
@@ -58,16 +58,14 @@ __global__ void __launch_bounds__(kBlock) frame_shade_hits_kernel(const float4* 
     bgra[i] = hf::shade_hit(Hit(__float_as_int(hv.x), hv.y, hv.z, hv.w), mode, clip);
 }
 
-__global__ void __launch_bounds__(kBlock) frame_accumulate_occlusion_kernel(const float4* __restrict__ occ_hits, int n, int* __restrict__ counts) {
+// The two ambient-occlusion steps share one kernel (the product library's kernel budget): `samples` is launch-uniform.
+// samples == 0: counts[i] += hits[i].id >= 0 (`hits` are occlusion hits, bgra is not touched); samples > 0: the pixel of primary hit i and counts[i].
+__global__ void __launch_bounds__(kBlock) frame_occlusion_kernel(const float4* __restrict__ hits, int* __restrict__ counts, int n, int samples, uint32_t* __restrict__ bgra) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    counts[i] += __float_as_int(occ_hits[i].x) >= 0 ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(kBlock) frame_shade_occlusion_kernel(const float4* __restrict__ hits, const int* __restrict__ counts, int n, int samples, uint32_t* __restrict__ bgra) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    bgra[i] = hf::shade_occlusion(__float_as_int(hits[i].x), counts[i], samples);
+    const int id = __float_as_int(hits[i].x);
+    if (samples == 0) counts[i] += id >= 0 ? 1 : 0;
+    else bgra[i] = hf::shade_occlusion(id, counts[i], samples);
 }
 
 // k Hit records per pixel, read where they lie (the list of pixel i starts at hits[i * k])
@@ -172,7 +170,7 @@ extern "C" int hagrid_accumulate_occlusion(hagrid_ctx* ctx, const void* occlusio
     if (num_rays <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "accumulate_occlusion: num_rays must be positive");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, counts, size_t(num_rays) * 4);
-    frame_accumulate_occlusion_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(occlusion_hits), num_rays, static_cast<int*>(counts));
+    frame_occlusion_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(occlusion_hits), static_cast<int*>(counts), num_rays, 0, nullptr);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -185,7 +183,7 @@ extern "C" int hagrid_shade_occlusion(hagrid_ctx* ctx, const void* hits, const v
     if (num_rays <= 0 || samples <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "shade_occlusion: num_rays and samples must be positive");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
-    frame_shade_occlusion_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), static_cast<const int*>(counts), num_rays, samples, static_cast<uint32_t*>(bgra));
+    frame_occlusion_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), static_cast<int*>(const_cast<void*>(counts)), num_rays, samples, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

@@ -52,6 +52,12 @@ class Camera(C.Structure):
         return c
 
 
+class Mesh(C.Structure):
+    """struct hagrid_mesh (include/hagrid_amd.h): one triangle mesh of a scene; vertices and indices are DEVICE addresses."""
+    _fields_ = [("vertices", C.c_void_p), ("indices", C.c_void_p), ("num_vertices", C.c_int32), ("num_tris", C.c_int32),
+                ("vertex_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
 MAX_MERGE_PASSES = 96
 
 
@@ -141,6 +147,11 @@ SIGNATURES = {
     "hagrid_shade_occlusion": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "hagrid_frame_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "hagrid_render_frame": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(Camera), _f32, _i32, _i32, _i32, _i32, _f32, C.c_uint64, _vp, _vp]),
+    "hagrid_scene_create": (_i32, [_vp, C.POINTER(Mesh), _i32, C.POINTER(C.c_int32), _i32, C.POINTER(_vp)]),
+    "hagrid_scene_destroy": (None, [_vp, _vp]),
+    "hagrid_scene_first_tri": (_i32, [_vp, _i32]),
+    "hagrid_scene_assemble": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "hagrid_scene_bad_indices": (_i32, [_vp, _vp, C.POINTER(_i64)]),
 }
 
 # libhagrid_amd_kat.so (hagrid_amd/csrc/kat/hagrid_amd_kat.h): known-answer hooks and diagnostic instantiations -- tests/ and tools/ only

@@ -197,6 +197,48 @@ def tris_from_mesh(verts: np.ndarray, faces: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(tris_from_vertices(verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]))
 
 
+def transform_points(M: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """Points v (n, 3) under the 3 x 4 matrix M (12 floats, row-major, last column = translation) in float32, one rounding per operation, in
+    the order include/hagrid/assemble.h writes it: x' = ((M[0]*x + M[1]*y) + M[2]*z) + M[3], rows 1 and 2 likewise with M[4..7], M[8..11]."""
+    M = np.asarray(M, dtype=np.float32).reshape(12)
+    v = np.asarray(v, dtype=np.float32)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    return np.stack([((M[4 * r] * x + M[4 * r + 1] * y) + M[4 * r + 2] * z) + M[4 * r + 3] for r in range(3)], axis=1).astype(np.float32)
+
+
+def assemble_tris(meshes, instance_mesh=None, transforms=None) -> tuple[np.ndarray, np.ndarray, int]:
+    """The Tri array of a scene of indexed meshes and instances -- the numpy statement of hagrid_scene_assemble (include/hagrid_amd.h), bit for bit.
+    meshes: a list of (vertices, faces): vertices float32 (V, >= 3) (columns beyond the third are padding: a stride of 16 bytes is a (V, 4)
+    array), faces int32 (F, 3), or None for F = V // 3 triangles on the vertices 3p, 3p+1, 3p+2 -- or (vertices, None, F) to say F.
+    instance_mesh: the mesh every instance places (None: one instance per mesh, in order).  transforms: (I, 12) or (I, 3, 4) float32, or None (the
+    vertices as they are).  Instances are laid out in order, each with its mesh's triangles in mesh order.  A triangle that names a vertex
+    outside its mesh becomes the degenerate triangle on the mesh's vertex 0 and is counted.
+    Returns (tris (N, 12) float32, origins (N, 2) int32 = (instance, triangle within its mesh), number of such triangles)."""
+    if instance_mesh is None:
+        instance_mesh = range(len(meshes))
+    instance_mesh = [int(k) for k in instance_mesh]
+    if transforms is not None:
+        transforms = np.asarray(transforms, dtype=np.float32).reshape(len(instance_mesh), 12)
+    tris, origins, bad = [np.empty((0, 12), np.float32)], [np.empty((0, 2), np.int32)], 0
+    for i, k in enumerate(instance_mesh):
+        verts = np.asarray(meshes[k][0], dtype=np.float32)[:, 0:3]
+        faces = meshes[k][1]
+        if faces is None:
+            count = int(meshes[k][2]) if len(meshes[k]) > 2 else verts.shape[0] // 3
+            faces = np.arange(3 * count, dtype=np.int64).reshape(count, 3)
+        faces = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+        if faces.shape[0] == 0:
+            continue
+        wrong = ((faces < 0) | (faces >= verts.shape[0])).any(axis=1)
+        faces = np.where(wrong[:, None], 0, faces)
+        bad += int(wrong.sum())
+        if transforms is not None:
+            verts = transform_points(transforms[i], verts)
+        tris.append(tris_from_vertices(verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]))
+        origins.append(np.stack([np.full(faces.shape[0], i), np.arange(faces.shape[0])], axis=1).astype(np.int32))
+    return np.ascontiguousarray(np.concatenate(tris), np.float32), np.ascontiguousarray(np.concatenate(origins), np.int32), bad
+
+
 def make_stadium(detail: float = 1.0) -> np.ndarray:
     """the triangles of make_stadium_mesh(), in face order"""
     return tris_from_mesh(*make_stadium_mesh(detail))

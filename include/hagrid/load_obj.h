@@ -20,7 +20,7 @@
 //   * errors do not stop the reading, but load_obj returns false if there was any (:238) and the front-end then refuses
 //     the scene (main.cpp:249-250).
 // Deviation: a vertex index beyond the end of the list is an error here (the reference stores it and reads out of bounds
-// later, main.cpp:256).  load_mtl (load_obj.cpp:241-361) is pinned the same way: tests/golden/mtl_golden.npz.
+// later, main.cpp:256).  load_obj_indexed gives the same scene as vertices + index triples (for assemble.h).  load_mtl (load_obj.cpp:241-361) is pinned the same way: tests/golden/mtl_golden.npz.
 #ifndef HAGRID_LOAD_OBJ_H
 #define HAGRID_LOAD_OBJ_H
 
@@ -330,6 +330,25 @@ inline bool load_obj_triangles(const std::string& file_name, std::vector<Tri>& t
                     tris.push_back(Tri(v0, n.x, e1, n.y, e2, n.z));
                 }
             }
+    return true;
+}
+
+/// The same scene as an INDEXED mesh: the file's vertex array (without the loader's dummy element 0, so indices are zero-based) and one
+/// index triple per triangle of the fan above, in the same order -- what hagrid::assemble::mesh_tri (assemble.h) or
+/// hagrid_scene_assemble turns into exactly the records load_obj_triangles makes: 12 bytes per vertex + 12 per triangle instead of 48.
+inline bool load_obj_indexed(const std::string& file_name, std::vector<vec3>& vertices, std::vector<int>& indices) {
+    ObjLoader::File obj;
+    ObjLoader::MaterialLib materials;
+    if (!ObjLoader::load_scene(file_name, obj, materials)) return false;
+    vertices.assign(obj.vertices.begin() + 1, obj.vertices.end());
+    for (const auto& object : obj.objects)
+        for (const auto& group : object.groups)
+            for (const auto& face : group.faces)
+                for (int i = 1; i + 1 < face.index_count; i++) {
+                    indices.push_back(face.indices[0].v - 1);
+                    indices.push_back(face.indices[i].v - 1);
+                    indices.push_back(face.indices[i + 1].v - 1);
+                }
     return true;
 }
 

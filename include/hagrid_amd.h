@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -353,6 +353,51 @@ size_t hagrid_frame_workspace_bytes(int width, int height, int ao_samples);
 int hagrid_render_frame(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const hagrid_camera* cam, float clip,
                         int width, int height, int mode, int ao_samples, float ao_radius, uint64_t seed,
                         void* workspace, void* bgra);
+
+/* ---- scenes on the device: indexed meshes and instance transforms -> the Tri array (the reference packs it on the host, main.cpp:246-275) ---- */
+/* Extension: what comes BEFORE hagrid_build_grid in a frame loop.  A scene is a list of triangle meshes (vertex buffer + index triples, both
+ * already on the device -- e.g. torch tensors a simulation or a skinning step rewrites every frame) and a list of instances, each placing one
+ * mesh by a 3 x 4 matrix.  hagrid_scene_assemble turns it into the 48-byte Tri records hagrid_build_grid takes, in ONE launch on the
+ * context's stream, without a host round trip: 12 bytes per index triple in, 48 bytes per triangle out, nothing crossing the bus.  The
+ * arithmetic is float32 without contraction, operation for operation (include/hagrid/assemble.h, callable from host code too;
+ * hagrid_amd/scene.py: assemble_tris states it in numpy -- the same bits):
+ *   - with a transform M (12 floats, row-major, last column = translation): x' = ((M[0]*x + M[1]*y) + M[2]*z) + M[3], rows 1 and 2
+ *     likewise with M[4..7], M[8..11]; with transforms == NULL the vertices are used as they are (not multiplied by an identity: -0 stays -0);
+ *   - then main.cpp:259-267 on the three (transformed) vertices: e1 = v0 - v1, e2 = v2 - v0, n = cross(e1, e2), record = v0, n.x, e1, n.y, e2, n.z.
+ * A triangle that names a vertex outside 0 .. num_vertices-1 is NEVER read out of bounds: it becomes the degenerate triangle on its mesh's
+ * vertex 0 (transformed; e1 = e2 = n = 0: no ray hits it and it stays inside the scene's box) and is counted for hagrid_scene_bad_indices. */
+typedef struct hagrid_mesh {        /* one triangle mesh; the two pointers are DEVICE pointers */
+    const void* vertices;           /* float32 x, y, z per vertex, vertex_stride bytes apart; 4-byte aligned */
+    const void* indices;            /* int32 triples (4-byte aligned), or NULL: triangle p uses vertices 3p, 3p+1, 3p+2 */
+    int32_t num_vertices, num_tris;
+    int32_t vertex_stride;          /* >= 12, a multiple of 4 (12: a [V,3] tensor, 16: [V,4]) */
+    int32_t reserved;               /* 0 */
+} hagrid_mesh;                      /* 32 bytes */
+typedef struct hagrid_scene hagrid_scene;
+
+/* meshes, instance_mesh: HOST arrays, read during the call.  instance_mesh[i] = the mesh instance i places; NULL = one instance per mesh,
+ * in order (num_instances must then be num_meshes).  The scene keeps ADDRESSES, not copies: what the vertex and index buffers hold is read at
+ * every hagrid_scene_assemble, so a caller may rewrite vertices between frames (and must keep the buffers alive).  Its small tables (mesh
+ * records, instance -> mesh, first triangle of every instance) live in a pool buffer of ctx; hagrid_scene_destroy returns it.  A scene is used
+ * with the context it was created in: hagrid_scene_assemble / _bad_indices with another context are HAGRID_EINVAL, _destroy with another one
+ * (or after that context was destroyed) releases the handle only.
+ * HAGRID_EINVAL (and *out = NULL): a null `out`, null `meshes` with num_meshes > 0, negative counts, a mesh with a stride below 12 or not a
+ * multiple of 4, a non-zero `reserved`, num_vertices == 0 with num_tris > 0, a null or misaligned vertex buffer of a mesh that has triangles, a
+ * misaligned index buffer, indices == NULL with 3 * num_tris beyond 2^31 - 1, instance_mesh[i] outside 0 .. num_meshes-1, instance_mesh ==
+ * NULL with num_instances != num_meshes.  HAGRID_ERANGE: more than 2^31 - 1 output triangles.  A scene without triangles is HAGRID_OK. */
+int hagrid_scene_create(hagrid_ctx* ctx, const hagrid_mesh* meshes, int num_meshes,
+                        const int32_t* instance_mesh, int num_instances, hagrid_scene** out);
+void hagrid_scene_destroy(hagrid_ctx* ctx, hagrid_scene* scene);
+/* First output triangle of instance i; i = num_instances gives the total.  Instances are laid out in order, each with its mesh's triangles
+ * in mesh order.  HAGRID_EINVAL for a null scene or an instance outside 0 .. num_instances. */
+int hagrid_scene_first_tri(const hagrid_scene* scene, int instance);
+/* transforms: DEVICE, 12 float32 per instance (4-byte aligned), or NULL.  tris: DEVICE, 48 bytes per output triangle, 16-byte aligned.
+ * origins: DEVICE int32 pairs (instance, triangle within its mesh) per output triangle (4-byte aligned), or NULL.  Asynchronous on the
+ * context's stream.  A scene without triangles launches nothing and accepts tris == NULL. */
+int hagrid_scene_assemble(hagrid_ctx* ctx, hagrid_scene* scene, const void* transforms, void* tris, void* origins);
+/* Synchronous: how many output triangles of the hagrid_scene_assemble calls since the last query named a vertex outside
+ * 0 .. num_vertices-1; resets the count. */
+int hagrid_scene_bad_indices(hagrid_ctx* ctx, hagrid_scene* scene, int64_t* count);
 
 
 #ifdef __cplusplus

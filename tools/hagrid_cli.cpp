@@ -14,6 +14,9 @@
 // --gpus), and --ppm FILE writes the frame the way the reference's viewer would show it: traced and shaded by hagrid_render_frame, --display
 // depth | gray | heat (main.cpp:90-111; gray and heat colour by the traversal step count, as the viewer does), or with --ao N as ambient
 // occlusion from N short diffuse rays per pixel (--ao-radius R, default a tenth of the scene size).
+// Extension: --device-tris uploads the scene as an indexed mesh -- the OBJ file's vertex array and the index triples of the fan (12 bytes per
+// vertex + 12 per triangle instead of 48 per triangle; soup:N: its vertices, no indices) -- and assembles the Tri array on the device
+// (include/hagrid/assemble.h: hagrid_scene_assemble); the records, and everything after them, are the same.
 //
 //   g++ -std=c++11 -O2 -DHOST= -DDEVICE= -Iinclude tools/hagrid_cli.cpp -o hagrid_cli -Lhagrid_amd -lhagrid_amd -lamdhip64
 #include <algorithm>
@@ -34,6 +37,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include "hagrid/assemble.h"
 #include "hagrid/build.h"
 #include "hagrid/frame.h"
 #include "hagrid/load_obj.h"
@@ -56,7 +60,7 @@ struct Options {
     float clip = 0, fov = 60;
     int build_iter = 1, build_warmup = 0, bench_iter = 1, bench_warmup = 0;
     float tmin = 0, tmax = FLT_MAX;
-    bool keep_alive = false, compress = false, help = false, any_hit = false;
+    bool keep_alive = false, compress = false, help = false, any_hit = false, device_tris = false;
 };
 
 enum Kind { FLAG, INT, FLOAT, STRING };
@@ -92,6 +96,7 @@ bool parse(int argc, char** argv, Options& o, std::vector<OptDesc>& table) {
         {"-p", "--ppm", STRING, &o.ppm_image, "(extension) writes the frame, traced and shaded on the device, as a binary PPM (P6)"},
         {"-ao", "--ao", INT, &o.ao_samples, "(extension) --ppm shows ambient occlusion from this many diffuse rays per pixel"},
         {"-aor", "--ao-radius", FLOAT, &o.ao_radius, "(extension) length of the ambient-occlusion rays (default: 0.1 x the scene size)"},
+        {"-dt", "--device-tris", FLAG, &o.device_tris, "(extension) uploads vertices and index triples and assembles the triangle records on the device"},
     };
     bool have_scene = false;
     for (int i = 1; i < argc; i++) {
@@ -128,24 +133,27 @@ void usage(const std::vector<OptDesc>& table) {
     std::cout << std::endl;
 }
 
-Tri make_tri(const vec3& v0, const vec3& v1, const vec3& v2) {     // packing of main.cpp:259-267
-    const vec3 e1 = v0 - v1, e2 = v2 - v0, n = cross(e1, e2);
-    return Tri(v0, n.x, e1, n.y, e2, n.z);
-}
-
+using assemble::make_tri;   // packing of main.cpp:259-267
 using frame::uniform01;     // hagrid_amd/scene.py:uniform01
 
-void make_soup(int n, std::vector<Tri>& tris) {     // hagrid_amd/scene.py:make_soup, same bits
+void make_soup_vertices(int n, std::vector<vec3>& verts) {     // the three vertices of every triangle of hagrid_amd/scene.py:make_soup, same bits
     const uint64_t seed = 0x48414752494400ull + uint64_t(n);
     const float s = float(std::pow(double(n), -1.0 / 3.0));
-    tris.resize(size_t(n));
+    verts.resize(3 * size_t(n > 0 ? n : 0));
     for (int i = 0; i < n; i++) {
         float u[9];
         for (int j = 0; j < 9; j++) u[j] = uniform01(seed, uint64_t(i) * 9 + j);
         const vec3 c(u[0], u[1], u[2]);
         const vec3 a = (2.0f * vec3(u[3], u[4], u[5]) - vec3(1.0f)) * s, b = (2.0f * vec3(u[6], u[7], u[8]) - vec3(1.0f)) * s;
-        tris[i] = make_tri(c, c + a, c + b);
+        verts[3 * size_t(i)] = c; verts[3 * size_t(i) + 1] = c + a; verts[3 * size_t(i) + 2] = c + b;
     }
+}
+
+void make_soup(int n, std::vector<Tri>& tris) {
+    std::vector<vec3> verts;
+    make_soup_vertices(n, verts);
+    tris.resize(verts.size() / 3);
+    for (size_t i = 0; i < tris.size(); i++) tris[i] = make_tri(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2]);
 }
 
 bool load_rays(const std::string& name, std::vector<Ray>& rays, float tmin, float tmax) {   // main.cpp:277-300 format
@@ -266,7 +274,33 @@ int main(int argc, char** argv) {
     Grid grid;
     grid.entries = nullptr; grid.cells = nullptr; grid.ref_ids = nullptr; grid.small_cells = nullptr;
     const bool build_here = root && opts.load_grid.empty();
-    if (build_here) {
+    if (build_here && opts.device_tris) {
+        // the scene as an indexed mesh: vertices (and index triples) up, the Tri records made where build_grid reads them
+        std::vector<vec3> verts;
+        std::vector<int> indices;
+        const bool soup = opts.scene.compare(0, 5, "soup:") == 0;
+        if (soup) make_soup_vertices(atoi(opts.scene.c_str() + 5), verts);
+        else if (!load_obj_indexed(opts.scene, verts, indices)) {
+            std::cerr << "Scene cannot be loaded (file not present or contains errors)" << std::endl;
+            return 1;
+        }
+        num_tris = int(soup ? verts.size() / 3 : indices.size() / 3);
+        hagrid_cli::report_scene(std::cout, size_t(num_tris));
+        vec3* d_verts = mem.alloc<vec3>(verts.size());
+        int* d_indices = soup ? nullptr : mem.alloc<int>(indices.size());
+        mem.copy<Copy::HST_TO_DEV>(d_verts, verts.data(), verts.size());
+        if (d_indices) mem.copy<Copy::HST_TO_DEV>(d_indices, indices.data(), indices.size());
+        tris = mem.alloc<Tri>(size_t(num_tris));
+        hagrid_mesh mesh = hagrid_mesh();
+        mesh.vertices = d_verts; mesh.indices = d_indices; mesh.num_vertices = int(verts.size()); mesh.num_tris = num_tris; mesh.vertex_stride = int(sizeof(vec3));
+        {
+            assemble::MeshScene scene(mem, std::vector<hagrid_mesh>(1, mesh));
+            scene.assemble(nullptr, tris);
+            if (scene.bad_indices() != 0) { std::cerr << "Scene names vertices it does not have" << std::endl; return 1; }     // (the loader refuses such files: not reached)
+        }
+        mem.free(d_verts);
+        if (d_indices) mem.free(d_indices);
+    } else if (build_here) {
         if (opts.scene.compare(0, 5, "soup:") == 0) make_soup(atoi(opts.scene.c_str() + 5), host_tris);
         else if (!load_obj_triangles(opts.scene, host_tris)) {
             std::cerr << "Scene cannot be loaded (file not present or contains errors)" << std::endl;
