@@ -28,7 +28,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import Camera, GridPOD, HagridError, TraversalStats
-from .scene import CELL_DTYPE, HIT_DTYPE, SMALL_CELL_DTYPE
+from .scene import CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, POINT_QUERY_DTYPE, SMALL_CELL_DTYPE
 
 _current = None  # the most recently created MemManager (profile / setup_traversal take no manager)
 
@@ -349,6 +349,17 @@ def traverse_grid_multi(grid: Grid, tris: int, rays: int, hits: int, num_rays: i
     _check(mem, mem._L.hagrid_traverse_grid_multi(mem._ctx, C.byref(grid.pod), C.c_void_p(tris), C.c_void_p(rays), C.c_void_p(hits), int(num_rays), int(k), int(flags)), "traverse_grid_multi")
 
 
+def closest_points(grid: Grid, tris: int, points: int, results: int, n: int, counters: int = 0):
+    """Extension (hagrid_closest_points): for each of n points (16 bytes: x, y, z, r -- POINT_QUERY_DTYPE) the nearest triangle within r: 32 bytes
+    per query into `results` (CLOSEST_DTYPE: q, d2, id, feature, side); nothing within r: id -1, d2 = r * r, q = p.  counters: 0, or a device int64[4]
+    the batch totals are added to (queries, cells visited, triangles tested, sub-blocks pruned).  All arguments are device addresses (a torch tensor
+    passes as t.data_ptr()); asynchronous on the manager's stream.  scene.closest_points states the results in numpy, bit for bit.  Walks the
+    construction format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_closest_points(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(points or 0), C.c_void_p(results or 0), int(n),
+                                             C.c_void_p(counters or 0), 0), "closest_points")
+
+
 def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, steps: int = 0) -> dict:
     mem = grid.mem or _current
     st = TraversalStats()
@@ -545,4 +556,5 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "HIT_DTYPE", "CELL_DTYPE", "SMALL_CELL_DTYPE",
            "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
-           "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene"]
+           "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE"]

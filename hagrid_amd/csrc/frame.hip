@@ -1,6 +1,6 @@
 // frame.hip -- a frame on the device: primary rays, bounce rays, shading, ambient occlusion (include/hagrid_amd.h "frames on the device").
 //
-// Five streaming kernels (four for the frame -- the two ambient-occlusion steps are one, with a mode argument -- and the layered picture of multi-hit lists), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
+// Four streaming kernels (the two ambient-occlusion steps are one, with a mode argument; so are the picture of hits and the layered picture of multi-hit lists), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
 // host program calls); the kernels only move the records: a Ray is two float4 and a Hit one, loaded and stored as such (16-byte accesses,
 // what the traversal kernels read: rays[2 * i], rays[2 * i + 1]), a pixel is one 32-bit word.  Mode, miss rule and flags are kernel
 // arguments, not template parameters: one kernel each.  hagrid_render_frame strings them together with hagrid_traverse_grid_ex on the
@@ -51,11 +51,18 @@ __global__ void __launch_bounds__(kBlock) frame_bounce_rays_kernel(const float* 
     store_ray(out, i, r);
 }
 
-__global__ void __launch_bounds__(kBlock) frame_shade_hits_kernel(const float4* __restrict__ hits, int n, int mode, float clip, uint32_t* __restrict__ bgra) {
+// The two shading entry points share one kernel (the product library's kernel budget): `k` is launch-uniform.
+// k == 0: the pixel of hit i (hagrid_shade_hits); k > 0: the layered picture of the k Hit records of pixel i, read where they lie (the list of
+// pixel i starts at hits[i * k]: hagrid_shade_layers; mode is not used).
+__global__ void __launch_bounds__(kBlock) frame_shade_hits_kernel(const float4* __restrict__ hits, int n, int mode, float clip, int k, float opacity, uint32_t* __restrict__ bgra) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const float4 hv = hits[i];
-    bgra[i] = hf::shade_hit(Hit(__float_as_int(hv.x), hv.y, hv.z, hv.w), mode, clip);
+    if (k == 0) {
+        const float4 hv = hits[i];
+        bgra[i] = hf::shade_hit(Hit(__float_as_int(hv.x), hv.y, hv.z, hv.w), mode, clip);
+    } else {
+        bgra[i] = hf::shade_layers(reinterpret_cast<const Hit*>(hits) + size_t(i) * size_t(k), k, clip, opacity);
+    }
 }
 
 // The two ambient-occlusion steps share one kernel (the product library's kernel budget): `samples` is launch-uniform.
@@ -66,13 +73,6 @@ __global__ void __launch_bounds__(kBlock) frame_occlusion_kernel(const float4* _
     const int id = __float_as_int(hits[i].x);
     if (samples == 0) counts[i] += id >= 0 ? 1 : 0;
     else bgra[i] = hf::shade_occlusion(id, counts[i], samples);
-}
-
-// k Hit records per pixel, read where they lie (the list of pixel i starts at hits[i * k])
-__global__ void __launch_bounds__(kBlock) frame_shade_layers_kernel(const Hit* __restrict__ hits, int n, int k, float clip, float opacity, uint32_t* __restrict__ bgra) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    bgra[i] = hf::shade_layers(hits + size_t(i) * size_t(k), k, clip, opacity);
 }
 
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
@@ -141,7 +141,7 @@ extern "C" int hagrid_shade_hits(hagrid_ctx* ctx, const void* hits, int num_hits
     if (mode == HAGRID_SHADE_DEPTH && !(clip > 0.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_hits: the depth picture needs clip > 0");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_hits) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_hits, mode, clip, static_cast<uint32_t*>(bgra));
+    frame_shade_hits_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_hits, mode, clip, 0, 0.0f, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -157,7 +157,7 @@ extern "C" int hagrid_shade_layers(hagrid_ctx* ctx, const void* hits, int num_ra
     if (!(opacity > 0.0f && opacity <= 1.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: opacity must be in (0, 1]");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
-    frame_shade_layers_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const Hit*>(hits), num_rays, k, clip, opacity, static_cast<uint32_t*>(bgra));
+    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_rays, 0, clip, k, opacity, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

@@ -136,6 +136,7 @@ SIGNATURES = {
     "hagrid_traverse_grid_ex": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, C.c_uint32]),
     "hagrid_traverse_grid_stats": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _vp, C.POINTER(TraversalStats)]),
     "hagrid_traverse_grid_multi": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _i32, C.c_uint32]),
+    "hagrid_closest_points": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _vp, C.c_uint32]),
     "hagrid_set_ray_binning": (_i32, [_vp, _i32]),
     "hagrid_set_option": (_i32, [_vp, C.c_char_p, _i32]),
     "hagrid_traversal_image_info": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(_i64)]),

@@ -17,6 +17,9 @@ import numpy as np
 HIT_DTYPE = np.dtype([("id", "<i4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
 CELL_DTYPE = np.dtype([("min", "<i4", 3), ("begin", "<i4"), ("max", "<i4", 3), ("end", "<i4")])
 SMALL_CELL_DTYPE = np.dtype([("min", "<u2", 3), ("max", "<u2", 3), ("begin", "<i4")])
+# nearest-surface queries (hagrid_closest_points): 16 bytes in, 32 bytes out per query
+POINT_QUERY_DTYPE = np.dtype([("p", "<f4", 3), ("r", "<f4")])
+CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("d2", "<f4"), ("id", "<i4"), ("feature", "<i4"), ("side", "<f4"), ("zero", "<i4")])
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 
@@ -483,6 +486,159 @@ def shade_occlusion(hits: np.ndarray, counts: np.ndarray, samples: int) -> np.nd
     v = np.where(hits["id"] >= 0, 255 * (samples - c) // samples, 0).astype(np.uint8)
     out = np.empty((hits.shape[0], 4), dtype=np.uint8)
     out[:, 0:3] = v[:, None]; out[:, 3] = 255
+    return out
+
+
+# ---- point batches for nearest-surface queries (counter-based like the ray generators: no libm, the same bits everywhere) ---------------
+
+def _uniform_rows(seed: int, count: int, width: int) -> np.ndarray:
+    idx = np.arange(count, dtype=np.uint64)[:, None] * np.uint64(width) + np.arange(width, dtype=np.uint64)[None, :]
+    return uniform01(seed, idx)
+
+
+def bbox_diagonal(bbox_min, bbox_max) -> np.float32:
+    e = (np.asarray(bbox_max, np.float32) - np.asarray(bbox_min, np.float32)).astype(np.float32)
+    return np.float32(np.sqrt(np.float32(np.float32(e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])))
+
+
+def make_points_surface(tris: np.ndarray, count: int, seed: int) -> tuple[np.ndarray, np.ndarray]:
+    """(points on triangles, their triangle): the triangle uniform by index, barycentrics folded into the triangle; float32, operations in the order written"""
+    u = _uniform_rows(seed, count, 3)
+    j = np.minimum((u[:, 0] * np.float32(tris.shape[0])).astype(np.int64), tris.shape[0] - 1)
+    a, b = u[:, 1], u[:, 2]
+    fold = a + b > np.float32(1.0)
+    a = np.where(fold, np.float32(1.0) - a, a); b = np.where(fold, np.float32(1.0) - b, b)
+    t = tris[j]
+    p = t[:, 0:3] - t[:, 4:7] * a[:, None] + t[:, 8:11] * b[:, None]          # v0 + a (v1 - v0) + b (v2 - v0)
+    return p.astype(np.float32), j
+
+
+def make_gaussian3(seed: int, count: int) -> np.ndarray:
+    """(count, 3) float32, close to N(0, 1): the sum of twelve uniforms minus six"""
+    u = _uniform_rows(seed, count * 3, 12)
+    s = u[:, 0]
+    for k in range(1, 12):
+        s = s + u[:, k]
+    return (s - np.float32(6.0)).reshape(count, 3).astype(np.float32)
+
+
+def make_points_uniform(bbox_min, bbox_max, count: int, seed: int, enlarge: float = 0.1) -> np.ndarray:
+    """uniform in the box enlarged by `enlarge` of its extents (half on every side)"""
+    lo = np.asarray(bbox_min, np.float32); hi = np.asarray(bbox_max, np.float32)
+    ext = hi - lo
+    a = lo - np.float32(0.5 * enlarge) * ext; e = ext * np.float32(1.0 + enlarge)
+    return (a + _uniform_rows(seed, count, 3) * e).astype(np.float32)
+
+
+def make_points_near_surface(tris: np.ndarray, bbox_min, bbox_max, count: int, seed: int, sigma: float = 0.01) -> np.ndarray:
+    """surface samples moved by a Gaussian of `sigma` box diagonals per axis"""
+    p, _ = make_points_surface(tris, count, seed)
+    return (p + make_gaussian3(seed ^ 0x67617573, count) * (np.float32(sigma) * bbox_diagonal(bbox_min, bbox_max))).astype(np.float32)
+
+
+# ---- nearest-surface queries: the numpy statement of include/hagrid/closest.h (same operations, same order, same bits) ------------------
+
+def _dot3(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _cross3(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _sub3(a, b):
+    return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+
+
+def _segment_d2(p, a, ab):
+    """segment_d2 of closest.h: (d2, q)"""
+    zero, one = np.float32(0.0), np.float32(1.0)
+    t = _dot3(_sub3(p, a), ab) / _dot3(ab, ab)
+    t = np.where(t > zero, t, zero)
+    t = np.where(t < one, t, one)
+    q = (a[0] + ab[0] * t, a[1] + ab[1] * t, a[2] + ab[2] * t)
+    d = _sub3(p, q)
+    return _dot3(d, d), q
+
+
+def _point_tri(p, T, want_q: bool):
+    """point_tri (and tri_side) of closest.h on broadcastable float32 arrays: p = (x, y, z), T = the 12 columns of the Tri records.
+    Returns valid, d2 and -- with want_q -- q (three arrays), feature, side."""
+    zero = np.float32(0.0)
+    v0, e1, e2, n = (T[0], T[1], T[2]), (T[4], T[5], T[6]), (T[8], T[9], T[10]), (T[3], T[7], T[11])
+    valid = ~((n[0] == zero) & (n[1] == zero) & (n[2] == zero))
+    v1 = _sub3(v0, e1); v2 = (v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2])
+    u1 = (-e1[0], -e1[1], -e1[2]); u2 = _sub3(v2, v1)
+    d2, q = _segment_d2(p, v0, u1)
+    f = np.ones(np.shape(d2), dtype=np.int32)
+    for k, (a, ab) in ((2, (v1, u2)), (3, (v0, e2))):
+        dk, qk = _segment_d2(p, a, ab)
+        less = dk < d2
+        d2 = np.where(less, dk, d2)
+        if want_q:
+            q = tuple(np.where(less, qk[i], q[i]) for i in range(3)); f = np.where(less, np.int32(k), f)
+    d0 = _sub3(p, v0); d1 = _sub3(p, v1)
+    nn = _dot3(n, n)
+    s1 = _dot3(_cross3(e1, d0), n); s2 = _dot3(_cross3(d1, u2), n); s3 = _dot3(_cross3(e2, d0), n)
+    inside = (s1 >= zero) & (s2 >= zero) & (s3 >= zero) & (nn > zero)
+    h = _dot3(d0, n)
+    df = h * h / nn
+    face = inside & (df <= d2)
+    d2 = np.where(face, df, d2)
+    if not want_q:
+        return valid, d2
+    hn = h / nn
+    q = tuple(np.where(face, p[i] - n[i] * hn, q[i]) for i in range(3))
+    f = np.where(face, np.int32(0), f)
+    s = _dot3(_sub3(p, q), n)
+    side = np.where(s > zero, np.int32(1), np.where(s < zero, np.int32(-1), np.int32(0)))
+    return valid, d2, q, f, side
+
+
+def closest_pairs(tris: np.ndarray, points: np.ndarray) -> dict:
+    """Triangle i against point i (points: (n, 3+) float32): valid (the triangle has a surface), d2, q (n, 3), feature, side -- the per-pair values
+    of include/hagrid/closest.h (point_tri, tri_side), bit for bit."""
+    T = np.ascontiguousarray(tris, dtype=np.float32); P = np.ascontiguousarray(points, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        valid, d2, q, f, side = _point_tri((P[:, 0], P[:, 1], P[:, 2]), [T[:, i] for i in range(12)], True)
+    return {"valid": valid, "d2": d2.astype(np.float32), "q": np.stack(q, axis=1).astype(np.float32), "feature": f.astype(np.int32), "side": side.astype(np.int32)}
+
+
+def closest_points(tris: np.ndarray, points: np.ndarray, chunk_pairs: int = 1 << 21) -> np.ndarray:
+    """The definition of hagrid_closest_points by brute force: points (n, 4) float32 x, y, z, r (or POINT_QUERY_DTYPE) -> CLOSEST_DTYPE records.
+    Among the triangles with a surface (stored normal != 0) and d2 <= r * r the smallest by (d2, id); none: id -1, d2 = r * r, q = p, feature =
+    side = 0; r < 0: an inactive query, id -1 and d2 = -1; a NaN coordinate: id -1.  Every point against every triangle, a chunk of points at a time."""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    P = np.ascontiguousarray(points).view(np.float32).reshape(-1, 4)
+    n, N = P.shape[0], T.shape[0]
+    out = np.zeros(n, dtype=CLOSEST_DTYPE)
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    inf = np.float32(np.inf)
+    with np.errstate(all="ignore"):
+        for o in range(0, n, m):
+            p = P[o:o + m]
+            r2 = p[:, 3] * p[:, 3]
+            res = out[o:o + m]
+            res["q"] = p[:, 0:3]; res["d2"] = r2; res["id"] = -1
+            if N:
+                valid, d2 = _point_tri((p[:, 0:1], p[:, 1:2], p[:, 2:3]), cols, False)
+                mask = valid & (d2 <= r2[:, None]) & (p[:, 3:4] >= np.float32(0.0))
+                d2m = np.where(mask, d2, inf)
+                mn = d2m.min(axis=1)
+                cand = mask & (d2 == mn[:, None])
+                has = cand.any(axis=1)
+                win = cand.argmax(axis=1)                          # the first of the tied triangles: the smallest id
+                Tw = T[win]
+                _, d2w, q, f, side = _point_tri((p[:, 0], p[:, 1], p[:, 2]), [Tw[:, i] for i in range(12)], True)
+                assert (d2w[has].view(np.uint32) == mn[has].view(np.uint32)).all()
+                res["id"] = np.where(has, win, -1)
+                res["d2"] = np.where(has, d2w, r2)
+                res["q"] = np.where(has[:, None], np.stack(q, axis=1), p[:, 0:3])
+                res["feature"] = np.where(has, f, 0)
+                res["side"] = np.where(has, side, 0).astype(np.float32)
+            res["d2"] = np.where(p[:, 3] < np.float32(0.0), np.float32(-1.0), res["d2"])
+            out[o:o + m] = res
     return out
 
 

@@ -1,0 +1,325 @@
+// hagrid/closest.h -- nearest-surface queries (hagrid_amd.h: hagrid_closest_points): for a point p and a radius r, the triangle
+// nearest to p within r, the squared distance, the closest point on it, the feature that holds it and the side of the face p is on.
+// No counterpart in the reference, which answers questions about rays only.
+//
+// Everything is float32 without contraction (-ffp-contract=off), every sum in the order written.  The same functions serve the gfx950
+// kernel (hagrid_amd/csrc/closest.hip) and host programs (tests/cpp/closest_host.cpp); hagrid_amd/scene.py (closest_pairs,
+// closest_points) states the same operations in numpy and gives the same bits.
+//
+// ---- one point, one triangle ----------------------------------------------------------------------------------------------------
+// The Tri record holds v0, e1 = v0 - v1, e2 = v2 - v0 and n = cross(e1, e2).  With v1 = v0 - e1, v2 = v0 + e2 (what Tri::bbox uses):
+//   * three segments, in this order: 1: a = v0, ab = -e1 (to v1);  2: a = v1, ab = v2 - v1;  3: a = v0, ab = e2 (to v2).  For each:
+//     t = dot(p - a, ab) / dot(ab, ab), clamped to [0, 1] by `t > 0 ? t : 0` then `t < 1 ? t : 1` (NaN -> 0: a segment of no length is
+//     its start), q = a + ab * t, d2 = dot(p - q, p - q).  d2_edge is the smallest, an earlier segment winning a tie (strict <);
+//   * p projects inside when dot(cross(e1, p - v0), n) >= 0, dot(cross(p - v1, v2 - v1), n) >= 0, dot(cross(e2, p - v0), n) >= 0 and
+//     dot(n, n) > 0.  Then with h = dot(p - v0, n) the face candidate h * h / dot(n, n) wins when it is <= d2_edge, with
+//     q = p - n * (h / dot(n, n)) and feature 0;
+//   * side = sign(dot(p - q, n)) as +1, -1 or 0: the sign of the FACE normal, not a robust inside / outside at edges and vertices.
+// This is the plane-and-segments form.  The barycentric-region form of the textbooks (products d1*d4 - d3*d2) loses the distance
+// to cancellation on meshes; this form does not (DESIGN.md 4.6 has the figures).
+// A triangle whose stored normal is (0, 0, 0) has no surface and is skipped (no ray hits it either); a candidate whose d2 is NaN is
+// never accepted.
+//
+// ---- the query ------------------------------------------------------------------------------------------------------------------
+// r2 = r * r (+inf allowed).  Among all triangles j with d2_j <= r2 the answer is the smallest in the order (d2 ascending, id
+// ascending).  None: id -1, d2 = r2, q = p, feature = side = 0.  r < 0 is an inactive query (id -1, d2 = -1); a NaN coordinate or a
+// NaN radius gives id -1.
+//
+// ---- the walk -------------------------------------------------------------------------------------------------------------------
+// closest_query walks the construction format (entries -> cells | small_cells -> ref_ids) and returns exactly what the definition
+// above gives over all triangles; pruning only ever skips triangles that cannot win.  Why it is sound:
+//   (a) a cell's reference list holds every triangle that meets the cell's box: the build puts a triangle into every voxel it
+//       overlaps, merging unites lists, and expansion grows a cell only over neighbours whose lists are subsets of its own (or,
+//       in the precise mode, whose extra triangles miss the grown region);
+//   (b) every triangle lies inside the grid box, so nothing lies beyond a face of the grid;
+//   (c) a triangle's distance to p is at least the distance from p to any box that contains the part of it in question.
+// So: the walk tests the list of the cell that holds p (p clamped into the grid); if the ball (p, sqrt(best)) stays inside that
+// cell's box (faces on the grid boundary do not count, by (b)) it is done.  Otherwise it visits the top-level cells in rings
+// (Chebyshev distance 0, 1, 2, ... from p's top-level cell), descends each one's sub-blocks while the box of the sub-block is not
+// farther than the best so far, and tests the cells of the leaves it reaches.  A ring's lower bound is the distance from p to the
+// nearest face of the cube of rings before it that still lies inside the grid; when that exceeds the best so far -- which starts as
+// r2, so a query that has found nothing stops at its radius -- or no such face is left, the walk is over.
+//
+// THE MARGIN.  Every pruning comparison has the form `lower bound > best`.  The lower bound is made of float differences between p
+// and face coordinates `float(corner) * cell_size + grid_min`; each is first reduced by eps = 2^-16 * (largest |coordinate| of the
+// grid box) and clamped at 0, and the comparison is lower^2 > best * (1 + 2^-10).  eps is 128 ulp of the largest coordinate: the face
+// coordinate and the difference are off by at most 2 ulp of it, the build's own overlap decisions (SAT in float, truncating casts of
+// compute_range) by a few more, and a triangle's computed distance differs from its true one by a few ulp of the coordinates plus a
+// relative 2^-20 or so (three-term dot products, one division) -- all far inside eps on the left and 2^-10 on the right.  A triangle
+// that ties with the best (same d2, smaller id) is never pruned: equality does not satisfy `>`.
+//
+// A cell reached through several leaves may be tested again; offering a triangle twice changes nothing.  The cell of p and the cell
+// tested last are recognised and skipped.  Three counts per query: cells visited, triangles tested, sub-blocks / top-level cells pruned.
+#ifndef HAGRID_CLOSEST_H
+#define HAGRID_CLOSEST_H
+
+#include "grid.h"
+#include "prims.h"
+#include "vec.h"
+
+namespace hagrid {
+namespace closest {
+
+struct Pair { float d2; vec3 q; int feature; };
+
+/// squared distance from p to the segment a + ab * t, t in [0, 1]; q = the closest point
+HOST DEVICE inline float segment_d2(const vec3& p, const vec3& a, const vec3& ab, vec3& q) {
+    const vec3 ap = p - a;
+    float t = dot(ap, ab) / dot(ab, ab);
+    t = t > 0.0f ? t : 0.0f;
+    t = t < 1.0f ? t : 1.0f;
+    q = a + ab * t;
+    const vec3 d = p - q;
+    return dot(d, d);
+}
+
+/// false: the triangle has no surface (stored normal 0) and takes no part
+HOST DEVICE inline bool point_tri(const Tri& tri, const vec3& p, Pair& r) {
+    const vec3 n = tri.normal();
+    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return false;
+    const vec3 v0 = tri.v0, v1 = v0 - tri.e1, v2 = v0 + tri.e2;
+    const vec3 u1(-tri.e1.x, -tri.e1.y, -tri.e1.z), u2 = v2 - v1;
+    vec3 q, qk;
+    float d2 = segment_d2(p, v0, u1, q);
+    int f = 1;
+    float dk = segment_d2(p, v1, u2, qk);
+    if (dk < d2) { d2 = dk; q = qk; f = 2; }
+    dk = segment_d2(p, v0, tri.e2, qk);
+    if (dk < d2) { d2 = dk; q = qk; f = 3; }
+    const vec3 d0 = p - v0, d1 = p - v1;
+    const float nn = dot(n, n);
+    const float s1 = dot(cross(tri.e1, d0), n), s2 = dot(cross(d1, u2), n), s3 = dot(cross(tri.e2, d0), n);
+    if (s1 >= 0.0f && s2 >= 0.0f && s3 >= 0.0f && nn > 0.0f) {
+        const float h = dot(d0, n);
+        const float df = h * h / nn;
+        if (df <= d2) { d2 = df; q = p - n * (h / nn); f = 0; }
+    }
+    r.d2 = d2; r.q = q; r.feature = f;
+    return true;
+}
+
+/// +1, -1 or 0: the side of the triangle's plane (by its stored normal) p lies on, seen from the closest point q
+HOST DEVICE inline int tri_side(const Tri& tri, const vec3& p, const vec3& q) {
+    const float s = dot(p - q, tri.normal());
+    return s > 0.0f ? 1 : (s < 0.0f ? -1 : 0);
+}
+
+struct Best {
+    int id; float d2; vec3 q; int feature, side;
+    HOST DEVICE void init(const vec3& p, float r2) { id = -1; d2 = r2; q = p; feature = 0; side = 0; }
+    /// would (c_d2, c_id) replace the answer so far?  NaN never does.
+    HOST DEVICE bool takes(float c_d2, int c_id) const { return id < 0 ? c_d2 <= d2 : (c_d2 < d2 || (c_d2 == d2 && c_id < id)); }
+    HOST DEVICE void offer(const Tri& tri, int ref, const vec3& p) {
+        Pair r;
+        if (point_tri(tri, p, r) && takes(r.d2, ref)) { id = ref; d2 = r.d2; q = r.q; feature = r.feature; side = tri_side(tri, p, r.q); }
+    }
+};
+
+/// is the query answered without looking at a triangle?  (inactive, NaN)
+HOST DEVICE inline bool trivial_query(const vec3& p, float r, Best& b) {
+    const float r2 = r * r;
+    b.init(p, r2);
+    if (r < 0.0f) { b.d2 = -1.0f; return true; }
+    return !(p.x == p.x) || !(p.y == p.y) || !(p.z == p.z) || !(r2 == r2);
+}
+
+/// the definition: every triangle, in order.  tri_at(j) -> Tri
+template <typename F>
+HOST DEVICE inline void brute_force(F tri_at, int num_tris, const vec3& p, float r, Best& b) {
+    if (trivial_query(p, r, b)) return;
+    for (int j = 0; j < num_tris; j++) b.offer(tri_at(j), j, p);
+}
+
+// ---- the walk ------------------------------------------------------------------------------------------------------------------
+
+struct GridConsts {
+    ivec3 top, dims;        ///< top-level and virtual resolution
+    int shift;
+    vec3 lo, cs, inv;       ///< grid box minimum, cell size, 1 / cell size (as dims / extents)
+    float eps;              ///< the absolute margin
+    /// the constants hagrid_amd/csrc/traverse.hip make_args computes, and the margin
+    HOST DEVICE void set(const ivec3& top_, int shift_, const vec3& lo_, const vec3& hi) {
+        top = top_; shift = shift_; dims = top_ << shift_; lo = lo_;
+        const vec3 ext = hi - lo_;
+        inv = vec3(dims) / ext; cs = ext / vec3(dims);
+        eps = abs_margin(lo_, hi);
+    }
+    HOST DEVICE static float abs_margin(const vec3& lo_, const vec3& hi) {
+        float m = detail::fabs1(lo_.x);
+        m = max(m, detail::fabs1(lo_.y)); m = max(m, detail::fabs1(lo_.z));
+        m = max(m, detail::fabs1(hi.x)); m = max(m, detail::fabs1(hi.y)); m = max(m, detail::fabs1(hi.z));
+        return m * 1.52587890625e-05f;      // 2^-16
+    }
+};
+
+struct CellRec { int lx, ly, lz, hx, hy, hz, begin, end; };   ///< end: past-the-end reference, INT_MAX for a SmallCell (sentinel-terminated); begin < 0: empty
+struct Counts { int cells, tris, pruned; };
+
+/// a distance reduced by the absolute margin, not below 0
+HOST DEVICE inline float shrink(float d, float eps) { const float m = d - eps; return m > 0.0f ? m : 0.0f; }
+/// lower bound (squared, already shrunk) certainly above the best so far?
+HOST DEVICE inline bool beyond(float lower2, float best_d2) { return lower2 > best_d2 * 1.0009765625f; }   // 1 + 2^-10
+/// face coordinate of an integer corner along one axis
+HOST DEVICE inline float face(int corner, float cs, float lo) { return float(corner) * cs + lo; }
+/// shrunk distance from p to the interval [lo corner, hi corner] along one axis
+HOST DEVICE inline float axis_gap(float p, int lc, int hc, float cs, float lo, float eps) {
+    const float a = face(lc, cs, lo) - p, b = p - face(hc, cs, lo);
+    return shrink(a > b ? a : b, eps);
+}
+HOST DEVICE inline float box_lower2(const GridConsts& c, const vec3& p, int lx, int ly, int lz, int hx, int hy, int hz) {
+    const float dx = axis_gap(p.x, lx, hx, c.cs.x, c.lo.x, c.eps), dy = axis_gap(p.y, ly, hy, c.cs.y, c.lo.y, c.eps), dz = axis_gap(p.z, lz, hz, c.cs.z, c.lo.z, c.eps);
+    return dx * dx + dy * dy + dz * dz;
+}
+
+/// A host-side stack for the descent (a run-time indexed array: fine on the host; the kernel keeps its stack in LDS)
+template <int LEVELS>
+struct ArrayStack {
+    uint32_t w_[LEVELS], i_[LEVELS];
+    void set(int level, uint32_t w, uint32_t i) { w_[level] = w; i_[level] = i; }
+    void set_i(int level, uint32_t i) { i_[level] = i; }
+    uint32_t w(int level) const { return w_[level]; }
+    uint32_t i(int level) const { return i_[level]; }
+};
+constexpr int kMaxLevels = 16;     ///< every level of the voxel map consumes at least one of the `shift` <= 15 bits
+
+/// the list of one cell.  G: c (GridConsts), word(i), cell(i) -> CellRec, ref(i), tri(id)
+template <typename G>
+HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, Best& b, Counts& n) {
+    const CellRec c = g.cell(index);
+    n.cells++;
+    if (c.begin >= 0) {
+        for (int i = c.begin; i < c.end; i++) {
+            const int ref = g.ref(i);
+            if (ref < 0) break;
+            n.tris++;
+            b.offer(g.tri(ref), ref, p);
+        }
+    }
+    return c;
+}
+
+/// one top-level cell: descend its sub-blocks while their boxes are not beyond the best so far
+template <typename G, typename S>
+HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& p, int tx, int ty, int tz, uint32_t first_cell, uint32_t& last_cell, Best& b, Counts& n) {
+    const GridConsts& c = g.c;
+    int rs = c.shift;                                   // the current node covers 2^rs voxels per axis from (ox, oy, oz)
+    int ox = tx << rs, oy = ty << rs, oz = tz << rs;
+    if (beyond(box_lower2(c, p, ox, oy, oz, ox + (1 << rs), oy + (1 << rs), oz + (1 << rs)), b.d2)) { n.pruned++; return; }
+    const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
+    if (!(top_w & 3u)) {
+        const uint32_t ci = top_w >> 2;
+        if (ci != first_cell && ci != last_cell) { last_cell = ci; test_cell(g, p, ci, b, n); }
+        return;
+    }
+    int level = 0;
+    st.set(0, top_w, 0u);
+    while (level >= 0) {
+        const uint32_t nw = st.w(level), idx = st.i(level);
+        const int l = int(nw & 3u);
+        if (idx >= (1u << (3 * l))) {                   // this node is done: back to its parent
+            level--;
+            if (level >= 0) {
+                rs += int(st.w(level) & 3u);
+                const int keep = ~((1 << rs) - 1);
+                ox &= keep; oy &= keep; oz &= keep;
+            }
+            continue;
+        }
+        st.set_i(level, idx + 1u);
+        const int m = (1 << l) - 1, s = rs - l;
+        if (s < 0) continue;                            // not a valid voxel map
+        const int cx = ox + ((int(idx) & m) << s), cy = oy + (((int(idx) >> l) & m) << s), cz = oz + ((int(idx) >> (2 * l)) << s);
+        if (beyond(box_lower2(c, p, cx, cy, cz, cx + (1 << s), cy + (1 << s), cz + (1 << s)), b.d2)) { n.pruned++; continue; }
+        const uint32_t cw = g.word((nw >> 2) + idx);
+        if (!(cw & 3u)) {
+            const uint32_t ci = cw >> 2;
+            if (ci != first_cell && ci != last_cell) { last_cell = ci; test_cell(g, p, ci, b, n); }
+        } else if (level + 1 < kMaxLevels) {
+            level++;
+            st.set(level, cw, 0u);
+            rs = s; ox = cx; oy = cy; oz = cz;
+        }
+    }
+}
+
+/// the answer for (p, r) over the grid g: equal, bit for bit, to brute_force over all triangles
+template <typename G, typename S>
+HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r, Best& b, Counts& n) {
+    const GridConsts& c = g.c;
+    n.cells = 0; n.tris = 0; n.pruned = 0;
+    if (trivial_query(p, r, b)) return;
+
+    // the voxel of p, p clamped into the grid
+    const vec3 f = (p - c.lo) * c.inv;
+    float fx = f.x > 0.0f ? f.x : 0.0f, fy = f.y > 0.0f ? f.y : 0.0f, fz = f.z > 0.0f ? f.z : 0.0f;
+    fx = fx < float(c.dims.x - 1) ? fx : float(c.dims.x - 1);
+    fy = fy < float(c.dims.y - 1) ? fy : float(c.dims.y - 1);
+    fz = fz < float(c.dims.z - 1) ? fz : float(c.dims.z - 1);
+    const int vx = int(fx), vy = int(fy), vz = int(fz);
+    const int tx = vx >> c.shift, ty = vy >> c.shift, tz = vz >> c.shift;
+
+    // its cell
+    uint32_t w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
+    int depth = 0;
+    while (w & 3u) {
+        const int k = int(w & 3u);
+        depth += k;
+        const int s = c.shift - depth, m = (1 << k) - 1;
+        w = g.word((w >> 2) + uint32_t(((vx >> s) & m) + ((((vy >> s) & m) + (((vz >> s) & m) << k)) << k)));
+    }
+    const uint32_t first_cell = w >> 2;
+    const CellRec c0 = test_cell(g, p, first_cell, b, n);
+
+    // does the ball (p, sqrt(best)) stay inside the cell's box?  faces on the grid boundary have nothing behind them
+    {
+        const float big = 3.4028234663852886e38f;
+        float m = big;
+        if (c0.lx > 0)        m = min(m, p.x - face(c0.lx, c.cs.x, c.lo.x));
+        if (c0.hx < c.dims.x) m = min(m, face(c0.hx, c.cs.x, c.lo.x) - p.x);
+        if (c0.ly > 0)        m = min(m, p.y - face(c0.ly, c.cs.y, c.lo.y));
+        if (c0.hy < c.dims.y) m = min(m, face(c0.hy, c.cs.y, c.lo.y) - p.y);
+        if (c0.lz > 0)        m = min(m, p.z - face(c0.lz, c.cs.z, c.lo.z));
+        if (c0.hz < c.dims.z) m = min(m, face(c0.hz, c.cs.z, c.lo.z) - p.z);
+        if (m == big) return;                           // the cell is the whole grid
+        const float ms = shrink(m, c.eps);
+        if (beyond(ms * ms, b.d2)) return;
+    }
+
+    // rings of top-level cells around (tx, ty, tz)
+    uint32_t last_cell = first_cell;
+    visit_top(g, st, p, tx, ty, tz, first_cell, last_cell, b, n);
+    for (int k = 1;; k++) {
+        // lower bound of ring k: the nearest face of the cube of rings 0 .. k-1 that still has grid behind it
+        const float big = 3.4028234663852886e38f;
+        float m = big;
+        if (tx - k + 1 > 0)   m = min(m, p.x - face((tx - k + 1) << c.shift, c.cs.x, c.lo.x));
+        if (tx + k < c.top.x) m = min(m, face((tx + k) << c.shift, c.cs.x, c.lo.x) - p.x);
+        if (ty - k + 1 > 0)   m = min(m, p.y - face((ty - k + 1) << c.shift, c.cs.y, c.lo.y));
+        if (ty + k < c.top.y) m = min(m, face((ty + k) << c.shift, c.cs.y, c.lo.y) - p.y);
+        if (tz - k + 1 > 0)   m = min(m, p.z - face((tz - k + 1) << c.shift, c.cs.z, c.lo.z));
+        if (tz + k < c.top.z) m = min(m, face((tz + k) << c.shift, c.cs.z, c.lo.z) - p.z);
+        if (m == big) break;                            // the rings have left the grid
+        const float ms = shrink(m, c.eps);
+        if (beyond(ms * ms, b.d2)) break;
+
+        const int z0 = max(tz - k, 0), z1 = min(tz + k, c.top.z - 1);
+        const int y0 = max(ty - k, 0), y1 = min(ty + k, c.top.y - 1);
+        for (int z = z0; z <= z1; z++) {
+            const bool zface = z == tz - k || z == tz + k;
+            for (int y = y0; y <= y1; y++) {
+                const bool shell = zface || y == ty - k || y == ty + k;     // the whole row belongs to the ring, else its two ends
+                const int xa = shell ? max(tx - k, 0) : tx - k, xb = shell ? min(tx + k, c.top.x - 1) : tx + k;
+                const int step = shell ? 1 : 2 * k;
+                for (int x = xa; x <= xb; x += step) {
+                    if (x < 0 || x >= c.top.x) continue;
+                    visit_top(g, st, p, x, y, z, first_cell, last_cell, b, n);
+                }
+            }
+        }
+    }
+}
+
+} // namespace closest
+} // namespace hagrid
+
+#endif // HAGRID_CLOSEST_H

@@ -43,6 +43,14 @@ inline void traverse_grid_multi(const Grid& grid, const Tri* tris, const Ray* ra
     detail::check(detail::current_ctx(), hagrid_traverse_grid_multi(detail::current_ctx(), &p, tris, rays, hits, num_rays, k, with_uvs ? HAGRID_TRAVERSE_UVS : 0u));
 }
 
+/// Extension: nearest-surface queries (hagrid_amd.h: hagrid_closest_points; the arithmetic and the walk: closest.h).  points: num_points records of
+/// 16 bytes (x, y, z, r), results: 32 bytes each ({qx, qy, qz, d2}, {int id, int feature, float side, 0}), counters: nullptr or int64[4] -- all DEVICE
+/// pointers, 16-byte aligned.  Asynchronous on the context's stream.
+inline void closest_points(const Grid& grid, const Tri* tris, const void* points, void* results, int num_points, void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_closest_points(detail::current_ctx(), &p, tris, points, results, num_points, counters, 0u));
+}
+
 /// Extension: independent batches in flight.  Every MemManager is a context with a stream of its own (hagrid_ctx_set_stream on
 /// mem.context()); `share_traversal(dst, src)` lets `dst` traverse with the traversal image setup_traversal built in `src`, and the
 /// overload below traverses on a named manager instead of the current one.  Two 1M-ray batches in flight take 0.118 ms each

@@ -259,6 +259,26 @@ int hagrid_traverse_grid_stats(hagrid_ctx* ctx, const hagrid_grid* grid, const v
 int hagrid_traverse_grid_multi(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
                                const void* rays, void* hits, int num_rays, int k, uint32_t flags);
 
+/* Extension (no reference counterpart): NEAREST-SURFACE queries -- for every point of a batch the triangle nearest to it, how far it is and where
+ * on it (distance fields, contact and collision in simulation loops, snapping points to a surface; Embree's rtcPointQuery, Open3D's
+ * compute_closest_points).  points holds 16 bytes per query: float32 x, y, z, r.  results holds 32 bytes per query:
+ *   {float32 qx, qy, qz, d2}, {int32 id, int32 feature, float32 side, 0}.
+ * The squared distance d2_j from p to triangle j, the closest point q, the feature that holds it (0 face, 1 / 2 / 3 edge v0v1 / v1v2 / v2v0, end
+ * points included) and side = sign(dot(p - q, n)) as +1, -1 or 0 are what point_tri and tri_side of include/hagrid/closest.h compute: float32
+ * without contraction, operation for operation (hagrid_amd/scene.py: closest_points states the same in numpy -- the same bits).  side is the sign
+ * of the FACE normal of the winning triangle, not a robust inside / outside at edges and vertices.  A triangle whose stored normal is (0, 0, 0)
+ * has no surface and takes no part (the degenerate triangles hagrid_scene_assemble makes for bad indices are such); a NaN d2 is never accepted.
+ * With r2 = r * r (+inf allowed) the answer is, among all triangles with d2_j <= r2, the smallest in the order (d2 ascending, id ascending);
+ * if there is none: id -1, d2 = r2, q = p, feature = side = 0.  r < 0 is an INACTIVE query (id -1, d2 = -1); a NaN coordinate gives id -1.
+ * One launch walks the CONSTRUCTION format from the cell that holds p outwards and prunes only what cannot win, so the results are those of the
+ * brute force over all triangles, bit for bit (the argument: include/hagrid/closest.h).  The traversal image, ray binning and
+ * the hints kept for the nearest-hit path are neither used nor touched.  counters: NULL, or DEVICE int64[4] to which the batch totals are ADDED
+ * (queries, cells visited, triangles tested, sub-blocks pruned): clear it first.  Asynchronous on the context's stream.
+ * HAGRID_EINVAL: a null grid, null or misaligned (16 bytes; counters 8) buffers, flags != 0, num_points < 0, a grid released by
+ * hagrid_grid_release_for_traversal.  num_points = 0 is HAGRID_OK (null buffers are then fine). */
+int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, void* results,
+                          int num_points, void* counters, uint32_t flags);
+
 /* Extension (no reference counterpart): spatial binning of the ray batch before traversal.  mode 0 (default): rays
  * are traversed in buffer order, as the reference does.  mode 1: each hagrid_traverse_grid call first bins the rays by
  * the position where they enter the grid (512 Morton-ordered bins, counting sort on the device) and traverses them in

@@ -1,0 +1,243 @@
+"""What the nearest-surface tests and the fixture generator (tests/golden/make_golden_closest.py) share: the scenes and queries of the fixture
+tests/golden/closest.npz (regenerated, not stored: counter-based generators of hagrid_amd/scene.py), the host program tests/cpp/closest_host.cpp
+as callables (per-pair values, the brute-force definition, the walk over grid arrays), and an independently written float64 evaluation."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+
+from hagrid_amd import scene
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INC = os.path.join(ROOT, "include")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "closest.npz")
+SCENES = ("soup", "mesh")
+NUM_QUERIES = 4096
+# the sections of the 4096 queries of a scene
+NEAR, UNIFORM, RADIUS, SURFACE, VERTEX, SPECIAL = slice(0, 2048), slice(2048, 3072), slice(3072, 3584), slice(3584, 3840), slice(3840, 4032), slice(4032, 4096)
+QUERY_SEED = 0x636C6F73657374            # "closest"
+
+
+def make_tris(name: str) -> np.ndarray:
+    return scene.make_soup(20000, seed=7) if name == "soup" else scene.make_stadium(0.05)
+
+
+diagonal = scene.bbox_diagonal
+_u = scene._uniform_rows
+surface_samples = scene.make_points_surface
+uniform_points = scene.make_points_uniform
+near_surface_points = scene.make_points_near_surface
+
+
+def fixture_queries(tris: np.ndarray) -> np.ndarray:
+    """the 4096 queries (x, y, z, r) of a scene: 2048 near the surface (surface samples moved by a Gaussian of 1 % of the diagonal), 1024 uniform in
+    the box enlarged by 10 %, r = inf; the first 512 of those again with r = 2 % of the diagonal; 256 exactly on surface samples; 192 exactly on
+    vertices; 64 special cases: 16 just outside the box, 16 far outside, 8 vertices with r = 0, 8 uniform points with r = 0, 8 with r < 0, 8 with a
+    NaN coordinate"""
+    lo, hi = scene.tris_bbox(tris)
+    diag = diagonal(lo, hi)
+    q = np.empty((NUM_QUERIES, 4), dtype=np.float32)
+    q[:, 3] = np.float32(np.inf)
+    q[NEAR, 0:3] = near_surface_points(tris, lo, hi, 2048, QUERY_SEED + 1)
+    uni = uniform_points(lo, hi, 1024, QUERY_SEED + 2)
+    q[UNIFORM, 0:3] = uni
+    q[RADIUS, 0:3] = uni[:512]; q[RADIUS, 3] = np.float32(0.02) * diag
+    q[SURFACE, 0:3] = surface_samples(tris, 256, QUERY_SEED + 3)[0]
+    u = _u(QUERY_SEED + 4, 200, 2)
+    j = np.minimum((u[:, 0] * np.float32(tris.shape[0])).astype(np.int64), tris.shape[0] - 1)
+    which = np.minimum((u[:, 1] * np.float32(3.0)).astype(np.int64), 2)
+    t = tris[j]
+    verts = np.where((which == 0)[:, None], t[:, 0:3], np.where((which == 1)[:, None], t[:, 0:3] - t[:, 4:7], t[:, 0:3] + t[:, 8:11])).astype(np.float32)
+    q[VERTEX, 0:3] = verts[:192]
+    s = np.empty((64, 4), dtype=np.float32); s[:, 3] = np.float32(np.inf)
+    d = np.float32(2.0) * _u(QUERY_SEED + 5, 64, 3) - np.float32(1.0)                      # directions in [-1, 1)^3
+    centre = (lo + hi) * np.float32(0.5)
+    out = uniform_points(lo, hi, 16, QUERY_SEED + 6, enlarge=0.0)
+    axis = np.arange(16) % 3; up = (np.arange(16) // 3) % 2 == 0
+    out[np.arange(16), axis] = np.where(up, hi[axis] + np.float32(0.05) * diag, lo[axis] - np.float32(0.05) * diag)   # beyond one face of the box
+    s[0:16, 0:3] = out
+    s[16:32, 0:3] = centre + d[16:32] * (np.float32(100.0) * diag)
+    s[32:40, 0:3] = verts[192:200]; s[32:40, 3] = 0.0
+    s[40:48, 0:3] = uniform_points(lo, hi, 8, QUERY_SEED + 7); s[40:48, 3] = 0.0
+    s[48:56, 0:3] = uniform_points(lo, hi, 8, QUERY_SEED + 8); s[48:56, 3] = np.float32([-1.0, -0.5, -1e-30, -np.inf, -2.0, -1.0, -3.0, -1.0])
+    s[56:64, 0:3] = uniform_points(lo, hi, 8, QUERY_SEED + 9); s[np.arange(56, 64), np.arange(8) % 3] = np.float32(np.nan)
+    q[SPECIAL] = s
+    return q
+
+
+def bits(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_results_equal(got: np.ndarray, want: np.ndarray, what: str):
+    """CLOSEST_DTYPE records: id, feature, side equal, d2 and q bit-equal (so the whole 32 bytes), no query excepted"""
+    g = np.ascontiguousarray(got).view(np.uint32).reshape(-1, 8); w = np.ascontiguousarray(want).view(np.uint32).reshape(-1, 8)
+    assert g.shape == w.shape, f"{what}: {g.shape} against {w.shape}"
+    bad = (g != w).any(axis=1)
+    assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} queries differ, first at {np.flatnonzero(bad)[:5]}: got {got[bad][:2]}, want {want[bad][:2]}"
+
+
+# ---- tests/cpp/closest_host.cpp ------------------------------------------------------------------------------------------------
+
+def build_host(directory) -> str:
+    """tests/cpp/closest_host.cpp with the flags tests/_multi_hit.py uses for multi_hit_host.cpp"""
+    exe = os.path.join(str(directory), "closest_host")
+    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
+                    os.path.join(ROOT, "tests", "cpp", "closest_host.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def _put(directory, name, arr) -> str:
+    path = os.path.join(str(directory), name + ".bin")
+    np.ascontiguousarray(arr).tofile(path)
+    return path
+
+
+def host_pairs(exe: str, directory, tris: np.ndarray, points: np.ndarray) -> dict:
+    """triangle i against point i through point_tri / tri_side of include/hagrid/closest.h"""
+    n = tris.shape[0]
+    pts = np.zeros((n, 4), dtype=np.float32); pts[:, 0:3] = points[:, 0:3]
+    par = os.path.join(str(directory), "pairs_params.bin")
+    with open(par, "wb") as f:
+        f.write(struct.pack("<i", n))
+    out = os.path.join(str(directory), "pairs_out.bin")
+    subprocess.run([exe, "pairs", par, _put(directory, "pairs_tris", tris.astype(np.float32)), _put(directory, "pairs_points", pts), out], check=True, timeout=600)
+    w = np.fromfile(out, dtype=np.uint32).reshape(n, 8)
+    return {"valid": w[:, 0] != 0, "d2": w[:, 1].view(np.float32), "q": np.ascontiguousarray(w[:, 2:5]).view(np.float32), "feature": w[:, 5].view(np.int32), "side": w[:, 6].view(np.int32)}
+
+
+def host_brute(exe: str, directory, tris: np.ndarray, points: np.ndarray) -> np.ndarray:
+    """brute_force of include/hagrid/closest.h: every point against all triangles"""
+    n = points.shape[0]
+    par = os.path.join(str(directory), "brute_params.bin")
+    with open(par, "wb") as f:
+        f.write(struct.pack("<i", n))
+    out = os.path.join(str(directory), "brute_out.bin")
+    subprocess.run([exe, "brute", par, _put(directory, "brute_tris", tris.astype(np.float32)), _put(directory, "brute_points", points.astype(np.float32)), out], check=True, timeout=1200)
+    return np.fromfile(out, dtype=scene.CLOSEST_DTYPE)
+
+
+def host_walk(exe: str, directory, grid: dict, tris: np.ndarray, points: np.ndarray):
+    """closest_query of include/hagrid/closest.h over grid arrays (keys entries, ref_ids, cells | small_cells, bbox_min, bbox_max, dims, shift: what
+    api.Grid.download returns): (CLOSEST_DTYPE records, per-query counts (n, 3) int32: cells visited, triangles tested, pruned)"""
+    d = str(directory)
+    small = grid.get("small_cells") is not None
+    n = points.shape[0]
+    par = os.path.join(d, "walk_params.bin")
+    with open(par, "wb") as f:
+        f.write(struct.pack("<i3ii3f3fi", 1 if small else 0, *[int(v) for v in grid["dims"]], int(grid["shift"]),
+                            *[float(v) for v in grid["bbox_min"]], *[float(v) for v in grid["bbox_max"]], n))
+    out, counts = os.path.join(d, "walk_out.bin"), os.path.join(d, "walk_counts.bin")
+    subprocess.run([exe, "walk", par, _put(d, "entries", grid["entries"]), _put(d, "cells", grid["small_cells"] if small else grid["cells"]),
+                    _put(d, "refs", grid["ref_ids"]), _put(d, "tris", np.ascontiguousarray(tris, dtype=np.float32)),
+                    _put(d, "points", np.ascontiguousarray(points, dtype=np.float32)), out, counts], check=True, timeout=1200)
+    return np.fromfile(out, dtype=scene.CLOSEST_DTYPE), np.fromfile(counts, dtype=np.int32).reshape(n, 3)
+
+
+def oracle_grid_arrays(G) -> dict:
+    """the arrays of an oracle.Grid in the shape host_walk takes"""
+    return {"entries": np.array(G.entries), "ref_ids": np.array(G.ref_ids), "cells": None if G.cells is None else np.array(G.cells),
+            "small_cells": None if G.small_cells is None else np.array(G.small_cells),
+            "bbox_min": G.bbox_min, "bbox_max": G.bbox_max, "dims": G.dims, "shift": G.shift}
+
+
+def oracle_grid(tris: np.ndarray, compress: bool, subset_only: bool):
+    """the construction sequence of the CPU oracle with either expansion mode"""
+    from oracle import oracle as O
+    G = O.Grid.build(tris).merge().flatten().expand(tris, 3, subset_only=subset_only)
+    if compress:
+        G.compress()
+    return G
+
+
+# ---- float64, written independently: the projection onto the plane, clamped into the triangle region by region ---------------------
+
+def _closest_f64(p, a, b, c):
+    """closest points of triangles (a, b, c) to points p, all (m, 3) float64: the projection of p, moved to the vertex or edge whose region holds it"""
+    ab = b - a; ac = c - a; ap = p - a
+    d1 = (ab * ap).sum(1); d2 = (ac * ap).sum(1)
+    bp = p - b; d3 = (ab * bp).sum(1); d4 = (ac * bp).sum(1)
+    cp = p - c; d5 = (ab * cp).sum(1); d6 = (ac * cp).sum(1)
+    vc = d1 * d4 - d3 * d2; vb = d5 * d2 - d1 * d6; va = d3 * d6 - d5 * d4
+    with np.errstate(all="ignore"):
+        den = va + vb + vc
+        v = vb / den; w = vc / den
+        q = a + ab * v[:, None] + ac * w[:, None]                                # inside the face
+        t_ab = d1 / (d1 - d3); t_ac = d2 / (d2 - d6); t_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+    done = np.zeros(p.shape[0], dtype=bool)
+
+    def put(mask, val):
+        nonlocal q, done
+        m = mask & ~done
+        q = np.where(m[:, None], val, q); done |= m
+
+    put((d1 <= 0) & (d2 <= 0), a)
+    put((d3 >= 0) & (d4 <= d3), b)
+    put((vc <= 0) & (d1 >= 0) & (d3 <= 0), a + ab * np.nan_to_num(t_ab)[:, None])
+    put((d6 >= 0) & (d5 <= d6), c)
+    put((vb <= 0) & (d2 >= 0) & (d6 <= 0), a + ac * np.nan_to_num(t_ac)[:, None])
+    put((va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0), b + (c - b) * np.nan_to_num(t_bc)[:, None])
+    # a triangle without area: the region tests above are all that is left of it; a face projection would divide by zero
+    flat = ~done & ~(np.abs(den) > 0)
+    q = np.where(flat[:, None], a, q)
+    return q
+
+
+def distance_f64(tris: np.ndarray, points: np.ndarray, ids=None) -> np.ndarray:
+    """float64 distances.  ids given: from point i to triangle ids[i].  ids None: from point i to the nearest triangle with a surface (stored normal
+    != 0), found among the triangles whose bounding sphere can reach below the nearest first vertex."""
+    T = np.asarray(tris, np.float64); P = np.asarray(points, np.float64)[:, 0:3]
+    A = T[:, 0:3]; B = A - T[:, 4:7]; Cc = A + T[:, 8:11]
+    if ids is not None:
+        q = _closest_f64(P, A[ids], B[ids], Cc[ids])
+        return np.sqrt(((P - q) ** 2).sum(1))
+    ok = ~((tris[:, 3] == 0) & (tris[:, 7] == 0) & (tris[:, 11] == 0))
+    A, B, Cc = A[ok], B[ok], Cc[ok]
+    cen = (A + B + Cc) / 3.0
+    rad = np.sqrt(np.maximum(((A - cen) ** 2).sum(1), np.maximum(((B - cen) ** 2).sum(1), ((Cc - cen) ** 2).sum(1)))) * (1 + 1e-12)
+    out = np.empty(P.shape[0])
+    for o in range(0, P.shape[0], 128):
+        p = P[o:o + 128]
+        dc = np.sqrt(((p[:, None, :] - cen[None, :, :]) ** 2).sum(2))
+        upper = np.sqrt(((p[:, None, :] - A[None, :, :]) ** 2).sum(2)).min(1)
+        qi, tj = np.nonzero(dc - rad[None, :] <= upper[:, None])
+        q = _closest_f64(p[qi], A[tj], B[tj], Cc[tj])
+        d = np.sqrt(((p[qi] - q) ** 2).sum(1))
+        best = np.full(p.shape[0], np.inf)
+        np.minimum.at(best, qi, d)
+        out[o:o + 128] = best
+    return out
+
+
+def fixture_results(fixture, name: str) -> np.ndarray:
+    """the answers of one scene of the fixture as CLOSEST_DTYPE records"""
+    r = np.zeros(NUM_QUERIES, dtype=scene.CLOSEST_DTYPE)
+    r["id"] = fixture[name + "_id"]; r["feature"] = fixture[name + "_feature"]; r["side"] = fixture[name + "_side"].astype(np.float32)
+    r["d2"] = fixture[name + "_d2"]; r["q"] = fixture[name + "_q"]
+    return r
+
+
+def deviations_f64(tris: np.ndarray, queries: np.ndarray, res: np.ndarray) -> dict:
+    """The float32 answers against float64, over the queries that have a distance (r >= 0, no NaN coordinate).  The unit is the box diagonal or,
+    for a query farther away than that, its float64 distance (float32 cannot hold a distance finer than 6e-8 of itself):
+    excess   = how much farther (float64) the float32 winner is than the float64 nearest triangle (queries that found a triangle);
+    error    = |sqrt(d2) - float64 distance to the nearest triangle| (queries that found a triangle);
+    inside   = for queries that found none: how far the float64 nearest triangle lies INSIDE the radius (<= 0: it is outside, as answered);
+    outside  = for queries that found one: how far the float64 nearest triangle lies OUTSIDE the radius (<= 0: it is inside, as answered)."""
+    lo, hi = scene.tris_bbox(tris)
+    diag = float(diagonal(lo, hi))
+    q = np.asarray(queries, np.float32)
+    real = (q[:, 3] >= 0) & ~np.isnan(q[:, 0:3]).any(axis=1)
+    found = real & (res["id"] >= 0)
+    none = real & (res["id"] < 0)
+    truth = np.full(q.shape[0], np.nan)
+    truth[real] = distance_f64(tris, q[real])
+    unit = np.maximum(truth, diag)
+    win = distance_f64(tris, q[found], res["id"][found])
+    r = q[:, 3].astype(np.float64)
+    return {"diag": diag, "found": int(found.sum()), "none": int(none.sum()), "real": int(real.sum()),
+            "excess": float(((win - truth[found]) / unit[found]).max()),
+            "error": float((np.abs(np.sqrt(res["d2"][found].astype(np.float64)) - truth[found]) / unit[found]).max()),
+            "inside": float(((r[none] - truth[none]) / unit[none]).max()) if none.any() else -np.inf,
+            "outside": float(((truth[found] - r[found]) / unit[found]).max())}
