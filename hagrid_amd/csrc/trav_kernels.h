@@ -33,9 +33,12 @@ __global__ void __launch_bounds__(64, 8) traverse_kernel_img(const TraverseArgs 
     const int id = perm ? perm[slot] : slot;
 
     const float4 r0 = nt_load4(a.rays + 2 * size_t(id)), r1 = nt_load4(a.rays + 2 * size_t(id) + 1);
-    const vec3 org(r0.x, r0.y, r0.z), dir(r1.x, r1.y, r1.z);
+    const vec3 org(r0.x, r0.y, r0.z);
+    vec3 dir(r1.x, r1.y, r1.z);
     const float tmin = r0.w, tmax = r1.w;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);          // an inadmissible ray is a miss: no cell walk
     const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));          // for the cell walk: no exit through planes of an axis the ray does not move along
     const vec3 gmin(a.min_x, a.min_y, a.min_z), gmax(a.max_x, a.max_y, a.max_z);
     const vec3 csize(a.cs_x, a.cs_y, a.cs_z), ginv(a.inv_x, a.inv_y, a.inv_z);
     const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
@@ -47,7 +50,7 @@ __global__ void __launch_bounds__(64, 8) traverse_kernel_img(const TraverseArgs 
 
     Hit hit(-1, tmax, 0.0f, 0.0f);
 
-    if (!(tstart > tend)) {
+    if (admitted && !(tstart > tend)) {
         const vec3 fv = (tstart * dir + org - gmin) * ginv;
         int vx = min(max(int(fv.x), 0), a.dims_x - 1);
         int vy = min(max(int(fv.y), 0), a.dims_y - 1);
@@ -125,7 +128,7 @@ __global__ void __launch_bounds__(64, 8) traverse_kernel_img(const TraverseArgs 
                     wide_begin = wr.w;
                 }
             }
-            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * inv_dir;
+            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * walk_inv;
             const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
             const vec3 ev = (texit * dir + org - gmin) * ginv;
             const int nx = texit == tcell.x ? cx + bx : int(ev.x);
@@ -342,6 +345,7 @@ __global__ void __launch_bounds__(64, MAILBOX ? 7 : (GENERAL ? HG_GENERAL_WAVES 
     vec3 org(r0.x, r0.y, r0.z), dir(r1.x, r1.y, r1.z);
     float tmin = r0.w;
     const float tmax = r1.w;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);          // an inadmissible ray is a miss: no cell walk (dir keeps its +0 zeros through both phases)
     const vec3 gmin(a.min_x, a.min_y, a.min_z), gmax(a.max_x, a.max_y, a.max_z);
     const vec3 csize(a.cs_x, a.cs_y, a.cs_z), ginv(a.inv_x, a.inv_y, a.inv_z);
     float hit_t = tmax;
@@ -354,7 +358,7 @@ __global__ void __launch_bounds__(64, MAILBOX ? 7 : (GENERAL ? HG_GENERAL_WAVES 
         const vec3 t0 = min(ta, tb), t1 = max(ta, tb);
         const float tstart = detail::fmax2(detail::fmax2(t0.x, detail::fmax2(t0.y, t0.z)), tmin);
         const float tend = detail::fmin2(detail::fmin2(t1.x, detail::fmin2(t1.y, t1.z)), tmax);
-        if (valid && !(tstart > tend)) {
+        if (valid && admitted && !(tstart > tend)) {
             const vec3 fv = (tstart * dir + org - gmin) * ginv;
             vx = min(max(int(fv.x), 0), a.dims_x - 1);
             vy = min(max(int(fv.y), 0), a.dims_y - 1);
@@ -553,7 +557,7 @@ __global__ void __launch_bounds__(64, MAILBOX ? 7 : (GENERAL ? HG_GENERAL_WAVES 
     else {
     // ---- phase 1: one ray per lane, while the wavefront holds more than kTailRays live rays -------------------------------
     {
-        vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+        vec3 inv_dir(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));          // (the cell walk's reciprocals: common.h)
         while (__popcll(live) > kTailRays) {
             if (alive) {
                 const uint4 na = cell_step(ca, inv_dir);
@@ -599,7 +603,7 @@ __global__ void __launch_bounds__(64, MAILBOX ? 7 : (GENERAL ? HG_GENERAL_WAVES 
 
     // ---- phase 2: four lanes per ray ------------------------------------------------------------------------------------------
     {
-        const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+        const vec3 inv_dir(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));
         // The cell step is split over the lanes of a group instead of being repeated by them.  Lane s owns axis
         // min(s, 2) (lane 3 doubles z): it computes its axis' exit plane, the exit parameter is the minimum over the group, the lane
         // finds its own coordinate of the next voxel and its share of the record's address, and the shares are added over the group

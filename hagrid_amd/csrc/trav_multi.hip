@@ -38,9 +38,12 @@ __global__ void __launch_bounds__(64) traverse_multi_kernel(const TraverseArgs a
     if (id >= a.num_rays) return;
 
     const float4 r0 = nt_load4(a.rays + 2 * size_t(id)), r1 = nt_load4(a.rays + 2 * size_t(id) + 1);
-    const vec3 org(r0.x, r0.y, r0.z), dir(r1.x, r1.y, r1.z);
+    const vec3 org(r0.x, r0.y, r0.z);
+    vec3 dir(r1.x, r1.y, r1.z);
     const float tmin = r0.w, tmax = r1.w;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);          // an inadmissible ray is a miss: no cell walk
     const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));          // for the cell walk: no exit through planes of an axis the ray does not move along
     const vec3 gmin(a.min_x, a.min_y, a.min_z), gmax(a.max_x, a.max_y, a.max_z);
     const vec3 csize(a.cs_x, a.cs_y, a.cs_z), ginv(a.inv_x, a.inv_y, a.inv_z);
     const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
@@ -54,7 +57,7 @@ __global__ void __launch_bounds__(64) traverse_multi_kernel(const TraverseArgs a
     list.init(k, tmax);
     const Ray ray(org, tmin, dir, tmax);          // the window every triangle is tested against
 
-    if (!(tstart > tend)) {
+    if (admitted && !(tstart > tend)) {
         const vec3 fv = (tstart * dir + org - gmin) * ginv;
         int vx = min(max(int(fv.x), 0), a.dims_x - 1);
         int vy = min(max(int(fv.y), 0), a.dims_y - 1);
@@ -78,7 +81,7 @@ __global__ void __launch_bounds__(64) traverse_multi_kernel(const TraverseArgs a
 
         for (;;) {
             const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
-            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * inv_dir;
+            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * walk_inv;
             const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
             const vec3 ev = (texit * dir + org - gmin) * ginv;
             const int nx = texit == tcell.x ? cx + (px ? 0 : -1) : int(ev.x);

@@ -20,9 +20,12 @@ __global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
     if (id >= a.num_rays) return;
 
     const float4 r0 = a.rays[2 * size_t(id)], r1 = a.rays[2 * size_t(id) + 1];
-    const vec3 org(r0.x, r0.y, r0.z), dir(r1.x, r1.y, r1.z);
+    const vec3 org(r0.x, r0.y, r0.z);
+    vec3 dir(r1.x, r1.y, r1.z);
     const float tmin = r0.w, tmax = r1.w;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);          // an inadmissible ray is a miss: no cell walk
     const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));          // for the cell walk: no exit through planes of an axis the ray does not move along
     const vec3 gmin(a.min_x, a.min_y, a.min_z), gmax(a.max_x, a.max_y, a.max_z);
     const vec3 csize(a.cs_x, a.cs_y, a.cs_z), ginv(a.inv_x, a.inv_y, a.inv_z);
     const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
@@ -37,7 +40,7 @@ __global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
     int steps = 0;
     unsigned n_cells = 0, n_words = 0, n_refs = 0, n_sent = 0, n_long = 0;
 
-    if (!(tstart > tend)) {
+    if (admitted && !(tstart > tend)) {
         const vec3 fv = (tstart * dir + org - gmin) * ginv;
         int vx = min(max(int(fv.x), 0), a.dims_x - 1);
         int vy = min(max(int(fv.y), 0), a.dims_y - 1);
@@ -59,7 +62,7 @@ __global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
 
             // exit plane of the cell along the ray
             const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
-            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * inv_dir;
+            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * walk_inv;
             const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
 
             // next voxel, never moving backwards
@@ -109,7 +112,7 @@ __global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
         if (a.steps) a.steps[id] = steps;
         if (a.stats) {
             atomicAdd(a.stats + 0, 1ull);
-            atomicAdd(a.stats + 1, (unsigned long long)(!(tstart > tend)));
+            atomicAdd(a.stats + 1, (unsigned long long)(admitted && !(tstart > tend)));
             atomicAdd(a.stats + 2, (unsigned long long)n_cells);
             atomicAdd(a.stats + 3, (unsigned long long)n_words);
             atomicAdd(a.stats + 4, (unsigned long long)n_refs);
@@ -145,9 +148,12 @@ __global__ void __launch_bounds__(BLOCK, 8) traverse_kernel_v2(const TraverseArg
     const int id = perm ? perm[slot] : slot;
 
     const float4 r0 = nt_load4(a.rays + 2 * size_t(id)), r1 = nt_load4(a.rays + 2 * size_t(id) + 1);
-    const vec3 org(r0.x, r0.y, r0.z), dir(r1.x, r1.y, r1.z);
+    const vec3 org(r0.x, r0.y, r0.z);
+    vec3 dir(r1.x, r1.y, r1.z);
     const float tmin = r0.w, tmax = r1.w;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);          // an inadmissible ray is a miss: no cell walk
     const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));          // for the cell walk: no exit through planes of an axis the ray does not move along
     const vec3 gmin(a.min_x, a.min_y, a.min_z), gmax(a.max_x, a.max_y, a.max_z);
     const vec3 csize(a.cs_x, a.cs_y, a.cs_z), ginv(a.inv_x, a.inv_y, a.inv_z);
     const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
@@ -159,7 +165,7 @@ __global__ void __launch_bounds__(BLOCK, 8) traverse_kernel_v2(const TraverseArg
 
     Hit hit(-1, tmax, 0.0f, 0.0f);
 
-    if (!(tstart > tend)) {
+    if (admitted && !(tstart > tend)) {
         const vec3 fv = (tstart * dir + org - gmin) * ginv;
         int vx = min(max(int(fv.x), 0), a.dims_x - 1);
         int vy = min(max(int(fv.y), 0), a.dims_y - 1);
@@ -216,7 +222,7 @@ __global__ void __launch_bounds__(BLOCK, 8) traverse_kernel_v2(const TraverseArg
 
         for (;;) {
             const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
-            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * inv_dir;
+            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * walk_inv;
             const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
             const vec3 ev = (texit * dir + org - gmin) * ginv;
             const int nx = texit == tcell.x ? cx + (px ? 0 : -1) : int(ev.x);

@@ -58,6 +58,15 @@ HOST DEVICE inline float safe_rcp(float x) {
     return as<float>(0x7f800000u | (as<uint32_t>(x) & 0x80000000u));
 }
 
+/// The reciprocal the cell walk multiplies plane distances with: safe_rcp(x), but NaN where that is infinite (x is +-0, or so small that 1/x
+/// overflows).  A ray does not cross the planes of such an axis, and (plane - org) * inf is +inf only for a plane ahead of the origin: it is NaN for a
+/// plane the origin lies on and -inf -- an exit parameter no cell has -- for a plane that the rounding of the voxel coordinate left behind the origin.
+/// NaN takes the axis out of every fmin (which returns the other operand) and out of `texit == tcell`; the box test keeps safe_rcp.
+HOST DEVICE inline float walk_rcp(float x) {
+    const float r = safe_rcp(x);
+    return (as<uint32_t>(r) & 0x7fffffffu) == 0x7f800000u ? as<float>(0x7fc00000u) : r;
+}
+
 /// x with its sign flipped when y is negative (reference: common.h:45-47).
 HOST DEVICE inline float prodsign(float x, float y) {
     return as<float>(as<uint32_t>(x) ^ (as<uint32_t>(y) & 0x80000000u));

@@ -217,7 +217,11 @@ int hagrid_grid_release_for_traversal(hagrid_ctx* ctx, hagrid_grid* grid);
  * (profiles/dev_r2_inflight.txt). */
 int hagrid_share_traversal(hagrid_ctx* dst, hagrid_ctx* src);
 /* traverse_grid (traverse.cu:111-117): rays 32-byte Ray records, hits 16-byte Hit records.
- * hits[i].id = primitive id or -1, hits[i].t = distance (tmax on a miss), u = v = 0.  Asynchronous. */
+ * hits[i].id = primitive id or -1, hits[i].t = distance (tmax on a miss), u = v = 0.  Asynchronous.
+ * Rays are taken as they are.  A ray with a NaN or infinite org / dir component, a NaN tmin / tmax, or a dir with no component whose float32 reciprocal is finite
+ * ((+-0, +-0, +-0), or every component below about 2.94e-39) is a MISS that takes no
+ * cell step: id -1, t = the bits of its tmax, u = v = 0 (multi-hit: k such records), whatever else the batch holds; +-inf are valid tmin / tmax; the
+ * sign of a zero dir component changes no result (include/hagrid/ray.h admit_ray). */
 int hagrid_traverse_grid(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
                          const void* rays, void* hits, int num_rays);
 /* Variants of the same walk (no separate entry point in the reference).  flags:

@@ -1060,9 +1060,71 @@ static __thread int* g_trace_ids = NULL;
 static __thread short* g_trace_vox = NULL;        /* dev analysis: the voxel of every look-up, 3 shorts per step (same capacity as g_trace) */
 static __thread int g_trace_ids_cap = 0, g_trace_ids_len = 0;
 
-static void traverse_one(const TravConsts* k, const OGrid* g, const OTri* tris, const ORay* rp, OHit* out, int* steps_out, OStats* st) {
+/* Checker switches of the walk (orc_set_walk_mode; process-wide, read by every traversing thread):
+ *   ORC_WALK_DEVICE_F2I     the walk's float-to-int conversions as the gfx950 conversion instruction performs them -- NaN gives 0, a value out
+ *                           of range saturates to INT_MAX / INT_MIN -- where the C cast on x86 gives INT_MIN for all of these.  (Read from the
+ *                           ISA description, not measured on a device.)  Rays the contract admits never convert such a value, so both modes
+ *                           must give the same records: tests/test_hostile_rays_cpu.py.
+ *   ORC_WALK_NO_ADMISSION   the prologue as the reference has it (traverse.cu:33-45): no classification, the caller's zero signs kept.  For
+ *                           tests that show what the classification is for; with it the step cap below is what ends some walks. */
+static unsigned g_walk_mode = 0;
+void orc_set_walk_mode(unsigned mode) { __atomic_store_n(&g_walk_mode, mode, __ATOMIC_RELAXED); }
+unsigned orc_get_walk_mode(void) { return __atomic_load_n(&g_walk_mode, __ATOMIC_RELAXED); }
+
+static inline int f2i(float x, unsigned mode) {
+    if (mode & ORC_WALK_DEVICE_F2I) {
+        if (x != x) return 0;
+        if (x >= 2147483648.0f) return INT32_MAX;
+        if (x <= -2147483648.0f) return INT32_MIN;
+    }
+    return (int)x;
+}
+
+/* Step cap (oracle only; the product's loops carry none): a walk that has made dims.x + dims.y + dims.z + 1 cell steps of the virtual
+ * resolution is ended and its ray reported -- DESIGN.md section 4.2 shows that an admissible ray stays below.  orc_walk_capped returns the number
+ * of rays ended that way since the last reset and the smallest of their indices within their batches. */
+static int64_t g_capped = 0, g_capped_first = -1;
+static void note_capped(int64_t ray_index) {
+    __atomic_fetch_add(&g_capped, 1, __ATOMIC_RELAXED);
+    int64_t cur = __atomic_load_n(&g_capped_first, __ATOMIC_RELAXED);
+    while ((cur < 0 || ray_index < cur) && !__atomic_compare_exchange_n(&g_capped_first, &cur, ray_index, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
+int64_t orc_walk_capped(int64_t* first_ray, int reset) {
+    int64_t n = __atomic_load_n(&g_capped, __ATOMIC_RELAXED);
+    if (first_ray) *first_ray = __atomic_load_n(&g_capped_first, __ATOMIC_RELAXED);
+    if (reset) { __atomic_store_n(&g_capped, 0, __ATOMIC_RELAXED); __atomic_store_n(&g_capped_first, -1, __ATOMIC_RELAXED); }
+    return n;
+}
+
+/* admit_ray of include/hagrid/ray.h, restated: zeros of dir made +0; admissible = org and dir finite, a component of dir with a finite reciprocal, tmin / tmax not NaN */
+static inline int admit_ray(ORay* r) {
+    const uint32_t e = 0x7f800000u, m = 0x7fffffffu;
+    if (r->dir.x == 0.0f) r->dir.x = 0.0f;
+    if (r->dir.y == 0.0f) r->dir.y = 0.0f;
+    if (r->dir.z == 0.0f) r->dir.z = 0.0f;
+    int finite = ((f2u(r->org.x) & e) != e) & ((f2u(r->org.y) & e) != e) & ((f2u(r->org.z) & e) != e) &
+                 ((f2u(r->dir.x) & e) != e) & ((f2u(r->dir.y) & e) != e) & ((f2u(r->dir.z) & e) != e);
+    int moves = isfinite(orc_safe_rcp(r->dir.x)) | isfinite(orc_safe_rcp(r->dir.y)) | isfinite(orc_safe_rcp(r->dir.z));   /* a finite walk reciprocal (dir is finite here) */
+    int window = ((f2u(r->tmin) & m) <= e) & ((f2u(r->tmax) & m) <= e);
+    return finite & moves & window;
+}
+
+/* returns 1 when the step cap ended the walk */
+static int traverse_one(const TravConsts* k, const OGrid* g, const OTri* tris, const ORay* rp, OHit* out, int* steps_out, OStats* st) {
     ORay ray = *rp;
+    const unsigned wm = orc_get_walk_mode();
+    const int admitted = (wm & ORC_WALK_NO_ADMISSION) ? 1 : admit_ray(&ray);
+    const int64_t cell_cap = (int64_t)k->dims.x + k->dims.y + k->dims.z + 1;
+    int64_t cells_done = 0;
+    int capped = 0;
     ovec3 inv_dir = v3(orc_safe_rcp(ray.dir.x), orc_safe_rcp(ray.dir.y), orc_safe_rcp(ray.dir.z));
+    /* walk_rcp of include/hagrid/common.h, restated: an infinite reciprocal is NaN for the cell walk (the box test keeps the infinity) */
+    ovec3 walk_inv = inv_dir;
+    if (!(wm & ORC_WALK_NO_ADMISSION)) {
+        if (isinf(walk_inv.x)) walk_inv.x = u2f(0x7fc00000u);
+        if (isinf(walk_inv.y)) walk_inv.y = u2f(0x7fc00000u);
+        if (isinf(walk_inv.z)) walk_inv.z = u2f(0x7fc00000u);
+    }
     /* intersect_ray_box traverse.cu:14-21 */
     ovec3 tmn = v3_mul(v3_sub(k->gmin, ray.org), inv_dir);
     ovec3 tmx = v3_mul(v3_sub(k->gmax, ray.org), inv_dir);
@@ -1074,10 +1136,10 @@ static void traverse_one(const TravConsts* k, const OGrid* g, const OTri* tris, 
     OHit hit = { -1, ray.tmax, 0, 0 };
     int steps = 0;
     if (st) st->rays++;
-    if (!(tstart > tend)) {
+    if (admitted && !(tstart > tend)) {
         if (st) st->rays_hit_grid++;
         ovec3 fv = compute_voxel(k, ray.org, ray.dir, tstart);
-        oivec3 voxel = iv3(clampi((int)fv.x, 0, k->dims.x - 1), clampi((int)fv.y, 0, k->dims.y - 1), clampi((int)fv.z, 0, k->dims.z - 1));
+        oivec3 voxel = iv3(clampi(f2i(fv.x, wm), 0, k->dims.x - 1), clampi(f2i(fv.y, wm), 0, k->dims.y - 1), clampi(f2i(fv.z, wm), 0, k->dims.z - 1));
         for (;;) {
             int words = 0;
             uint32_t entry = orc_lookup_entry(g->entries, k->shift, &k->top, &voxel, &words);
@@ -1092,11 +1154,11 @@ static void traverse_one(const TravConsts* k, const OGrid* g, const OTri* tris, 
             }
             /* traverse.cu:63-68 */
             oivec3 cp = iv3(ray.dir.x >= 0.0f ? cmax.x : cmin.x, ray.dir.y >= 0.0f ? cmax.y : cmin.y, ray.dir.z >= 0.0f ? cmax.z : cmin.z);
-            ovec3 tcell = v3_mul(v3_sub(v3_add(v3_mul(v3_from_i(cp), k->cell_size), k->gmin), ray.org), inv_dir);
+            ovec3 tcell = v3_mul(v3_sub(v3_add(v3_mul(v3_from_i(cp), k->cell_size), k->gmin), ray.org), walk_inv);
             float texit = fminf(tcell.x, fminf(tcell.y, tcell.z));
             /* traverse.cu:70-77 */
             ovec3 ev = compute_voxel(k, ray.org, ray.dir, texit);
-            oivec3 ep = iv3((int)ev.x, (int)ev.y, (int)ev.z);
+            oivec3 ep = iv3(f2i(ev.x, wm), f2i(ev.y, wm), f2i(ev.z, wm));
             oivec3 nv = iv3(texit == tcell.x ? cp.x + (ray.dir.x >= 0.0f ? 0 : -1) : ep.x,
                             texit == tcell.y ? cp.y + (ray.dir.y >= 0.0f ? 0 : -1) : ep.y,
                             texit == tcell.z ? cp.z + (ray.dir.z >= 0.0f ? 0 : -1) : ep.z);
@@ -1137,17 +1199,19 @@ static void traverse_one(const TravConsts* k, const OGrid* g, const OTri* tris, 
             if (found_any || hit.t <= texit ||
                 ((voxel.x < 0) | (voxel.x >= k->dims.x) | (voxel.y < 0) | (voxel.y >= k->dims.y) | (voxel.z < 0) | (voxel.z >= k->dims.z)))
                 break;
+            if (++cells_done >= cell_cap) { capped = 1; break; }
         }
     }
     if (st && hit.id >= 0) st->hits++;
     *out = hit;                 /* D4: id stays the primitive id */
     if (steps_out) *steps_out = steps;
+    return capped;
 }
 
 void orc_traverse_grid(const OGrid* grid, const OTri* tris, const ORay* rays, OHit* hits, int64_t n, int* steps, OStats* stats) {
     TravConsts k; setup_consts(grid, &k);
     if (stats) memset(stats, 0, sizeof(*stats));
-    for (int64_t i = 0; i < n; i++) traverse_one(&k, grid, tris, &rays[i], &hits[i], steps ? &steps[i] : NULL, stats);
+    for (int64_t i = 0; i < n; i++) if (traverse_one(&k, grid, tris, &rays[i], &hits[i], steps ? &steps[i] : NULL, stats)) note_capped(i);
 }
 
 /* dev analysis: as orc_traverse_trace, plus vox[(i * cap + s) * 3 ..] = the voxel of the s-th look-up of ray i */
@@ -1156,7 +1220,7 @@ void orc_traverse_trace_voxels(const OGrid* grid, const OTri* tris, const ORay* 
     for (int64_t i = 0; i < n; i++) {
         OHit hit;
         g_trace = lens + i * cap; g_trace_cap = cap; g_trace_len = 0; g_trace_vox = vox + i * cap * 3;
-        traverse_one(&k, grid, tris, &rays[i], &hit, NULL, NULL);
+        if (traverse_one(&k, grid, tris, &rays[i], &hit, NULL, NULL)) note_capped(i);
         num_cells[i] = g_trace_len;
     }
     g_trace = NULL; g_trace_vox = NULL;
@@ -1169,7 +1233,7 @@ void orc_traverse_trace(const OGrid* grid, const OTri* tris, const ORay* rays, i
         OHit hit;
         g_trace = lens + i * cap; g_trace_cap = cap; g_trace_len = 0;
         g_trace_ids = ids ? ids + i * ids_cap : NULL; g_trace_ids_cap = ids_cap; g_trace_ids_len = 0;
-        traverse_one(&k, grid, tris, &rays[i], &hit, NULL, NULL);
+        if (traverse_one(&k, grid, tris, &rays[i], &hit, NULL, NULL)) note_capped(i);
         num_cells[i] = g_trace_len;
         if (num_ids) num_ids[i] = g_trace_ids_len;
     }
@@ -1212,7 +1276,7 @@ static void* job_main(void* p) {
                 j->hits[i] = hit;
             }
         } else {
-            for (int64_t i = begin; i < end; i++) traverse_one(&k, j->grid, j->tris, &j->rays[i], &j->hits[i], NULL, &local);
+            for (int64_t i = begin; i < end; i++) if (traverse_one(&k, j->grid, j->tris, &j->rays[i], &j->hits[i], NULL, &local)) note_capped(i);
         }
     }
     g_mode = 0;

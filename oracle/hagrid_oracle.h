@@ -115,6 +115,17 @@ void orc_traverse_grid_pinned(const OGrid* grid, const OTri* tris, const ORay* r
 #define ORC_ANY_HIT 1u
 #define ORC_UVS 2u
 void orc_traverse_grid_ex(const OGrid* grid, const OTri* tris, const ORay* rays, OHit* hits, int64_t num_rays, int nthreads, unsigned flags);
+/* checker switches of the walk, process-wide (hagrid_oracle.c, "Checker switches"): the device's float-to-int conversions (NaN -> 0, saturating;
+ * read from the ISA description, not measured), and the reference's prologue without the ray classification */
+/* (One setting for the whole process, read at the start of every ray: set it while no traversal runs in another thread -- a traversal that runs
+ * concurrently with a change sees either mode per ray.  Test use only.) */
+#define ORC_WALK_DEVICE_F2I 1u
+#define ORC_WALK_NO_ADMISSION 2u
+void orc_set_walk_mode(unsigned mode);
+unsigned orc_get_walk_mode(void);
+/* step cap of the oracle's walk (dims.x + dims.y + dims.z + 1 cell steps of the virtual resolution): rays ended by it since the last reset,
+ * *first_ray = the smallest of their indices within their batches (-1: none) */
+int64_t orc_walk_capped(int64_t* first_ray, int reset);
 /* dev analysis: lens[i*cap + s] = list length of the s-th cell ray i visits (clamped to 255), num_cells[i] = cells visited */
 void orc_traverse_trace(const OGrid* grid, const OTri* tris, const ORay* rays, int64_t num_rays, int cap, unsigned char* lens, int* num_cells,
                         int ids_cap, int* ids /* may be NULL: tested reference ids in order */, int* num_ids);

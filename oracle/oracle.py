@@ -86,6 +86,9 @@ def lib() -> C.CDLL:
         L.orc_check_grid.restype = i32; L.orc_check_grid.argtypes = [vp, vp, i32, i32, C.c_char_p, i32]
         L.orc_set_cuda_quirks.restype = None; L.orc_set_cuda_quirks.argtypes = [i32]
         L.orc_get_cuda_quirks.restype = i32; L.orc_get_cuda_quirks.argtypes = []
+        L.orc_set_walk_mode.restype = None; L.orc_set_walk_mode.argtypes = [C.c_uint]
+        L.orc_get_walk_mode.restype = C.c_uint; L.orc_get_walk_mode.argtypes = []
+        L.orc_walk_capped.restype = i64; L.orc_walk_capped.argtypes = [vp, i32]
         _lib = L
     return _lib
 
@@ -299,6 +302,34 @@ def algorithmic_bytes(stats: dict, compressed: bool) -> dict:
     walk = 4 * stats["entry_words"] + s_cell * stats["cells"]
     total = 48 * stats["rays"] + walk + 52 * stats["refs"] + 4 * stats["sentinels"]
     return {"B_ray": total, "B_walk": walk}
+
+
+DEVICE_F2I, NO_ADMISSION = 1, 2
+
+
+class walk_mode:
+    """`with walk_mode(bits):` -- checker switches of the oracle's walk (hagrid_oracle.h): DEVICE_F2I = float-to-int conversions as the
+    device performs them (NaN -> 0, saturating; read from the ISA description, not measured), NO_ADMISSION = the reference's prologue,
+    without the ray classification of DESIGN.md section 2 (the step cap is then what ends some walks)."""
+
+    def __init__(self, bits: int):
+        self.bits = int(bits)
+
+    def __enter__(self):
+        self.old = lib().orc_get_walk_mode()
+        lib().orc_set_walk_mode(self.bits)
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_set_walk_mode(self.old)
+        return False
+
+
+def walk_capped(reset: bool = True):
+    """(number of rays whose walk the oracle's step cap ended since the last reset, smallest batch index among them or -1)"""
+    first = C.c_int64(-1)
+    n = lib().orc_walk_capped(C.byref(first), 1 if reset else 0)
+    return int(n), int(first.value)
 
 
 class cuda_quirks:

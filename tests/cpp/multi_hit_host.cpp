@@ -82,10 +82,14 @@ Box cell_box(const HostGrid& g, uint32_t index) {
     return b;
 }
 
-void walk_ray(const HostGrid& g, const Tri* tris, const Ray& ray, int k, Hit* out) {
-    const vec3 org = ray.org, dir = ray.dir;
-    const float tmin = ray.tmin, tmax = ray.tmax;
+void walk_ray(const HostGrid& g, const Tri* tris, const Ray& ray_in, int k, Hit* out) {
+    const vec3 org = ray_in.org;
+    vec3 dir = ray_in.dir;
+    const float tmin = ray_in.tmin, tmax = ray_in.tmax;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);          // an inadmissible ray is a miss: no cell walk
+    const Ray ray(org, tmin, dir, tmax);          // the window every triangle is tested against
     const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));
     const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
 
     const vec3 ta = (g.lo - org) * inv_dir, tb = (g.hi - org) * inv_dir;
@@ -96,7 +100,7 @@ void walk_ray(const HostGrid& g, const Tri* tris, const Ray& ray, int k, Hit* ou
     HitList<HAGRID_MAX_HITS> list;          // the kernel's list: HAGRID_MAX_HITS slots, k of them in use
     list.init(k, tmax);
 
-    if (!(tstart > tend)) {
+    if (admitted && !(tstart > tend)) {
         const vec3 fv = (tstart * dir + org - g.lo) * g.inv;
         int vx = min(max(int(fv.x), 0), g.dims.x - 1);
         int vy = min(max(int(fv.y), 0), g.dims.y - 1);
@@ -106,7 +110,7 @@ void walk_ray(const HostGrid& g, const Tri* tris, const Ray& ray, int k, Hit* ou
 
             // exit plane of the cell along the ray
             const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
-            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * g.cell_size + g.lo - org) * inv_dir;
+            const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * g.cell_size + g.lo - org) * walk_inv;
             const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
 
             // next voxel, never moving backwards
