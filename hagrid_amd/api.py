@@ -28,7 +28,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import Camera, GridPOD, HagridError, TraversalStats
-from .scene import CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, POINT_QUERY_DTYPE, SMALL_CELL_DTYPE
+from .scene import BOX_QUERY_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, POINT_QUERY_DTYPE, SMALL_CELL_DTYPE
 
 _current = None  # the most recently created MemManager (profile / setup_traversal take no manager)
 
@@ -360,6 +360,33 @@ def closest_points(grid: Grid, tris: int, points: int, results: int, n: int, cou
                                              C.c_void_p(counters or 0), 0), "closest_points")
 
 
+MAX_OVERLAP_IDS = 8      # HAGRID_MAX_OVERLAP_IDS
+OVERLAP_ANY = 1          # HAGRID_OVERLAP_ANY
+
+
+def overlap_boxes(grid: Grid, tris: int, boxes: int, n: int, k: int, ids: int, counts: int = 0, counters: int = 0, flags: int = 0):
+    """Extension (hagrid_overlap_boxes): for each of n boxes (32 bytes: BOX_QUERY_DTYPE -- min, first, max, pad) the k smallest ids >= first of the
+    triangles that meet it, ascending, into ids[i * k .. i * k + k - 1] (int32, unused slots -1), and min(how many meet it, k + 1) into counts[i] (int32;
+    counts may be 0).  1 <= k <= MAX_OVERLAP_IDS; flags: 0 | OVERLAP_ANY (k = 1: stop at the first triangle that meets the box).  counters: 0, or a device
+    int64[4] the batch totals are added to (boxes, cells visited, triangle / box tests, sub-blocks pruned).  All arguments are device addresses (a torch
+    tensor passes as t.data_ptr()); asynchronous on the manager's stream.  Every box is clipped to the grid box first, so infinite bounds mean "no bound on
+    this side".  ids: 16-byte aligned for k = 4 and k = 8, 4-byte aligned otherwise.  scene.overlap_boxes states the results in numpy.  Walks the construction
+    format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_overlap_boxes(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(boxes or 0), int(n), int(k), C.c_void_p(ids or 0),
+                                            C.c_void_p(counts or 0), C.c_void_p(counters or 0), int(flags)), "overlap_boxes")
+
+
+def voxelize(grid: Grid, tris: int, origin, size, n, k: int, ids: int, counts: int = 0, counters: int = 0, flags: int = 0):
+    """Extension (hagrid_overlap_lattice): overlap_boxes over the voxels of an n[0] x n[1] x n[2] lattice, x fastest, made on the device: voxel c of an
+    axis is [origin + float(c) * size, origin + float(c + 1) * size] (scene.lattice_boxes gives the same boxes).  origin, size: 3 floats, n: 3 ints (host
+    values); ids: n[0] * n[1] * n[2] * k int32 on the device.  With k = 1 and OVERLAP_ANY, ids >= 0 is the surface voxelization of the mesh."""
+    mem = grid.mem or _current
+    o = (C.c_float * 3)(*[float(v) for v in origin]); s = (C.c_float * 3)(*[float(v) for v in size]); m = (C.c_int * 3)(*[int(v) for v in n])
+    _check(mem, mem._L.hagrid_overlap_lattice(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), o, s, m, int(k), C.c_void_p(ids or 0), C.c_void_p(counts or 0),
+                                              C.c_void_p(counters or 0), int(flags)), "voxelize")
+
+
 def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, steps: int = 0) -> dict:
     mem = grid.mem or _current
     st = TraversalStats()
@@ -557,4 +584,4 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
-           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE"]
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY"]

@@ -1,0 +1,197 @@
+// overlap.hip -- box-overlap queries: for every box of a batch the k smallest ids of the triangles that meet it (include/hagrid_amd.h:
+// hagrid_overlap_boxes, hagrid_overlap_lattice; the test, the list, the walk and the argument why it is sound: include/hagrid/overlap.h).
+// No counterpart in the reference.
+//
+// The kernel is the header's overlap_query with device loads, in the shape of closest.hip: one box per lane, one wavefront per workgroup, the
+// XCD-aware block -> range map, streaming 16-byte loads of the box records and streaming stores of the ids.  It walks the construction format
+// (entries -> cells | small_cells -> ref_ids).  k, the cell format, ANY and "boxes from a buffer or from lattice constants" are kernel arguments,
+// uniform over the launch: ONE kernel (the product library's kernel budget, tests/test_abi.py).  The id list lives in eight registers -- every loop
+// over it runs over compile-time indices, k only appears in comparisons with them -- and the descent's stack of (node word, next child) per level in
+// LDS, laid out [level][lane]: a lane only ever touches its own column, so there is nothing to synchronise, 64 lanes at one level read 64 consecutive
+// words (no bank conflict) and no register array is indexed at run time (no scratch).  8 KB of LDS per wavefront: 20 wavefronts per CU by LDS
+// (DESIGN.md 4.7).  Boxes are processed in buffer order: no binning, no traversal image, no hints -- each answer depends on its box alone.
+#include "trav_common.h"
+#include "wave_prims.h"
+
+#include "hagrid/overlap.h"
+
+#include <string>
+
+using namespace hagrid;
+using namespace hagrid_impl;
+using namespace hagrid_trav;
+namespace hc = hagrid::closest;
+namespace ho = hagrid::overlap;
+
+namespace {
+
+struct DevGrid {
+    hc::GridConsts c;
+    ho::Clip clip;
+    const uint32_t* __restrict__ entries;
+    const void* __restrict__ cells;
+    const int* __restrict__ refs;
+    const float4* __restrict__ tris;
+    int small;
+
+    __device__ __forceinline__ uint32_t word(uint32_t i) const { return entries[i]; }
+    __device__ __forceinline__ hc::CellRec cell(uint32_t i) const {
+        CellBox b;
+        if (small) { b = load_cell_box<true>(cells, i); b.end = 0x7fffffff; }
+        else       { b = load_cell_box<false>(cells, i); }
+        hc::CellRec r;
+        r.lx = b.lx; r.ly = b.ly; r.lz = b.lz; r.hx = b.hx; r.hy = b.hy; r.hz = b.hz; r.begin = b.begin; r.end = b.end;
+        return r;
+    }
+    __device__ __forceinline__ int ref(int i) const { return refs[i]; }
+    __device__ __forceinline__ Tri tri(int id) const { return load_tri(tris, id); }
+};
+
+// the descent's stack in LDS: column `lane` of two [level][64] arrays
+struct LdsStack {
+    uint32_t* w_;
+    uint32_t* i_;
+    __device__ __forceinline__ void set(int level, uint32_t w, uint32_t i) { w_[level * 64] = w; i_[level * 64] = i; }
+    __device__ __forceinline__ void set_i(int level, uint32_t i) { i_[level * 64] = i; }
+    __device__ __forceinline__ uint32_t w(int level) const { return w_[level * 64]; }
+    __device__ __forceinline__ uint32_t i(int level) const { return i_[level * 64]; }
+};
+
+struct OverlapArgs {
+    const float4* __restrict__ boxes;        // null: the lattice form
+    int* __restrict__ ids;
+    int* __restrict__ counts;                // may be null
+    unsigned long long* __restrict__ counters;   // may be null
+    int n, k, any;
+    float ox, oy, oz, sx, sy, sz;            // lattice: origin, voxel size
+    int nx, ny;                              // lattice: voxels along x and y (x fastest)
+};
+
+__global__ void __launch_bounds__(64) overlap_boxes_kernel(const DevGrid g, const OverlapArgs a) {
+    __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
+    const int lane = threadIdx.x;
+    const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
+    const bool live = id < a.n;
+    ho::Counts cnt;
+    cnt.cells = 0; cnt.sats = 0; cnt.pruned = 0;
+    if (live) {
+        vec3 lo, hi;
+        int first = 0;
+        if (a.boxes) {
+            const float4 b0 = nt_load4(a.boxes + 2 * size_t(id)), b1 = nt_load4(a.boxes + 2 * size_t(id) + 1);
+            lo = vec3(b0.x, b0.y, b0.z); hi = vec3(b1.x, b1.y, b1.z);
+            first = __float_as_int(b0.w);
+        } else {
+            const int x = id % a.nx, yz = id / a.nx, y = yz % a.ny, z = yz / a.ny;
+            lo = vec3(ho::lattice_face(a.ox, x, a.sx), ho::lattice_face(a.oy, y, a.sy), ho::lattice_face(a.oz, z, a.sz));
+            hi = vec3(ho::lattice_face(a.ox, x + 1, a.sx), ho::lattice_face(a.oy, y + 1, a.sy), ho::lattice_face(a.oz, z + 1, a.sz));
+        }
+        LdsStack st;
+        st.w_ = &s_w[0][lane]; st.i_ = &s_i[0][lane];
+        ho::IdList<ho::kMaxIds> list;
+        list.init(a.k, first);
+        ho::overlap_query(g, st, lo, hi, a.any != 0, list, cnt);
+        int* out = a.ids + size_t(id) * size_t(a.k);
+        if (a.k == 8) {         // the base is 16-byte aligned (checked on the host): two streaming stores
+            nt_store4(reinterpret_cast<float4*>(out), __int_as_float(list.id[0]), __int_as_float(list.id[1]), __int_as_float(list.id[2]), __int_as_float(list.id[3]));
+            nt_store4(reinterpret_cast<float4*>(out) + 1, __int_as_float(list.id[4]), __int_as_float(list.id[5]), __int_as_float(list.id[6]), __int_as_float(list.id[7]));
+        } else if (a.k == 4) {
+            nt_store4(reinterpret_cast<float4*>(out), __int_as_float(list.id[0]), __int_as_float(list.id[1]), __int_as_float(list.id[2]), __int_as_float(list.id[3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < ho::kMaxIds; j++)
+                if (j < a.k) __builtin_nontemporal_store(list.id[j], out + j);
+        }
+        if (a.counts) __builtin_nontemporal_store(list.count(), a.counts + id);
+    }
+    if (a.counters) {   // batch totals: the wavefront's sums, one vector atomic each
+        const int boxes = wave_sum(live ? 1 : 0);
+        // a lane's count fits 31 bits, 64 of them need not
+        unsigned long long cells = (unsigned long long)(unsigned)cnt.cells, sats = (unsigned long long)(unsigned)cnt.sats, pruned = (unsigned long long)(unsigned)cnt.pruned;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            cells += (unsigned long long)__shfl_xor((long long)cells, d, 64);
+            sats += (unsigned long long)__shfl_xor((long long)sats, d, 64);
+            pruned += (unsigned long long)__shfl_xor((long long)pruned, d, 64);
+        }
+        if (lane == 0) {
+            atomicAdd(a.counters + 0, (unsigned long long)boxes);
+            atomicAdd(a.counters + 1, cells);
+            atomicAdd(a.counters + 2, sats);
+            atomicAdd(a.counters + 3, pruned);
+        }
+    }
+}
+
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// what both entry points check and do; boxes null: the lattice form (a holds its constants and n)
+int launch(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid, const void* tris, OverlapArgs a, void* ids, void* counts, void* counters, uint32_t flags) {
+    if (flags & ~HAGRID_OVERLAP_ANY) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": unknown flag (HAGRID_OVERLAP_ANY is the only one)").c_str());
+    if (a.k < 1 || a.k > HAGRID_MAX_OVERLAP_IDS) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": k must be 1 .. HAGRID_MAX_OVERLAP_IDS").c_str());
+    if ((flags & HAGRID_OVERLAP_ANY) && a.k != 1) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": HAGRID_OVERLAP_ANY needs k = 1").c_str());
+    if (!grid) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": null grid").c_str());
+    if (!grid->entries || (!grid->cells && !grid->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the walk reads the construction format (grid released for traversal, or incomplete)").c_str());
+    if (!grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": incomplete grid").c_str());
+    if (grid->shift < 0 || grid->shift > 15 || grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": bad shift or dims").c_str());
+    if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the counters must be 8-byte aligned").c_str());
+    if (!aligned(counts, 4)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the counts must be 4-byte aligned").c_str());
+    if (a.n == 0) return HAGRID_OK;
+    if (!tris || !ids) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": null triangle or id buffer").c_str());
+    if (!aligned(tris, 16) || !aligned(a.boxes, 16)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": triangles and boxes must be 16-byte aligned").c_str());
+    // k = 4 and k = 8 store their ids 16 bytes at a time, every other k one id at a time
+    if (!aligned(ids, (a.k == 4 || a.k == 8) ? 16 : 4)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the ids must be 16-byte aligned for k = 4 and k = 8, 4-byte aligned otherwise").c_str());
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+    DevGrid g;
+    g.c.set(ivec3(grid->dims[0], grid->dims[1], grid->dims[2]), grid->shift, vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2]),
+            vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]));
+    g.clip.set(vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2]), vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]));
+    g.entries = static_cast<const uint32_t*>(grid->entries);
+    g.cells = grid->small_cells ? grid->small_cells : grid->cells;
+    g.refs = static_cast<const int*>(grid->ref_ids);
+    g.tris = static_cast<const float4*>(tris);
+    g.small = grid->small_cells != nullptr ? 1 : 0;
+    a.ids = static_cast<int*>(ids);
+    a.counts = static_cast<int*>(counts);
+    a.counters = static_cast<unsigned long long*>(counters);
+    a.any = (flags & HAGRID_OVERLAP_ANY) ? 1 : 0;
+    overlap_boxes_kernel<<<grid_blocks(a.n, 64), 64, 0, ctx->stream>>>(g, a);
+    HG_DBG(ctx);
+    HG_HIP(ctx, hipGetLastError());
+    return HAGRID_OK;
+}
+
+} // namespace
+
+extern "C" int hagrid_overlap_boxes(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* boxes, int num_boxes, int k, void* ids, void* counts,
+                                    void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (num_boxes < 0) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_boxes: negative num_boxes");
+    if (num_boxes > 0 && !boxes) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_boxes: null box buffer");
+    OverlapArgs a = {};
+    a.boxes = static_cast<const float4*>(boxes);
+    a.n = num_boxes; a.k = k;
+    a.nx = 1; a.ny = 1;
+    return launch(ctx, "overlap_boxes", grid, tris, a, ids, counts, counters, flags);
+}
+
+extern "C" int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, int k,
+                                      void* ids, void* counts, void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (!origin || !size || !n) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: null origin, size or n");
+    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: the lattice needs at least one voxel along every axis");
+    const long long plane = (long long)n[0] * n[1];                 // each factor is below 2^31: fits 62 bits
+    if (plane > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: more than 2^31 - 1 voxels");
+    const long long total = plane * n[2];                           // below 2^62 now
+    if (total > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: more than 2^31 - 1 voxels");
+    for (int i = 0; i < 3; i++)
+        if (!(size[i] > 0.0f) || !(size[i] <= 3.4028234663852886e38f) || !(origin[i] >= -3.4028234663852886e38f && origin[i] <= 3.4028234663852886e38f))
+            HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: the voxel size must be positive and finite, the origin finite");
+    OverlapArgs a = {};
+    a.boxes = nullptr;
+    a.n = int(total); a.k = k;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
+    a.sx = size[0]; a.sy = size[1]; a.sz = size[2];
+    a.nx = n[0]; a.ny = n[1];
+    return launch(ctx, "overlap_lattice", grid, tris, a, ids, counts, counters, flags);
+}

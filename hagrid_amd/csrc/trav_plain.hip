@@ -12,9 +12,9 @@ using namespace hagrid_trav;
 
 namespace {
 
-// One instantiation per cell format: the counters are kept in registers whether or not the caller asked for them (a.steps / a.stats null, "traverse.variant" = 1).
-template <bool SMALL>
-__global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
+// ONE kernel: the cell format is a kernel argument, uniform over the launch (as in trav_multi.hip and closest.hip; the product library's kernel budget,
+// tests/test_abi.py); the counters are kept in registers whether or not the caller asked for them (a.steps / a.stats null, "traverse.variant" = 1).
+__global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a, const int small) {
     constexpr bool STATS = true;
     const int id = blockIdx.x * 256 + threadIdx.x;
     if (id >= a.num_rays) return;
@@ -58,7 +58,7 @@ __global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
                 w = a.entries[(w >> 2) + ((vx >> s) & m) + ((((vy >> s) & m) + (((vz >> s) & m) << k)) << k)];
                 if (STATS) n_words++;
             }
-            const CellBox c = load_cell_box<SMALL>(a.cells, w >> 2);
+            const CellBox c = small ? load_cell_box<true>(a.cells, w >> 2) : load_cell_box<false>(a.cells, w >> 2);
 
             // exit plane of the cell along the ray
             const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(256) traverse_kernel(const TraverseArgs a) {
 
             // the cell's triangles
             int consumed = 0;
-            if (SMALL) {
+            if (small) {
                 if (c.begin >= 0) {
                     int cur = c.begin;
                     int ref = a.refs[cur++];
@@ -272,6 +272,5 @@ void hagrid_trav::launch_v2(hipStream_t st, int blocks, bool small, bool narrow,
 
 void hagrid_trav::launch_plain(hipStream_t st, int num_rays, bool small, const TraverseArgs& a) {
     const int blocks = grid_blocks(num_rays, 256);
-    if (small) traverse_kernel<true><<<blocks, 256, 0, st>>>(a);
-    else       traverse_kernel<false><<<blocks, 256, 0, st>>>(a);
+    traverse_kernel<<<blocks, 256, 0, st>>>(a, small ? 1 : 0);
 }

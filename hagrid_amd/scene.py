@@ -20,6 +20,9 @@ SMALL_CELL_DTYPE = np.dtype([("min", "<u2", 3), ("max", "<u2", 3), ("begin", "<i
 # nearest-surface queries (hagrid_closest_points): 16 bytes in, 32 bytes out per query
 POINT_QUERY_DTYPE = np.dtype([("p", "<f4", 3), ("r", "<f4")])
 CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("d2", "<f4"), ("id", "<i4"), ("feature", "<i4"), ("side", "<f4"), ("zero", "<i4")])
+# box-overlap queries (hagrid_overlap_boxes): 32 bytes per box, the layout of BBox with `first` in the pad slot after min
+BOX_QUERY_DTYPE = np.dtype([("min", "<f4", 3), ("first", "<i4"), ("max", "<f4", 3), ("pad", "<i4")])
+OVERLAP_ANY = 1
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 
@@ -639,6 +642,120 @@ def closest_points(tris: np.ndarray, points: np.ndarray, chunk_pairs: int = 1 <<
                 res["side"] = np.where(has, side, 0).astype(np.float32)
             res["d2"] = np.where(p[:, 3] < np.float32(0.0), np.float32(-1.0), res["d2"])
             out[o:o + m] = res
+    return out
+
+
+# ---- box-overlap queries: the numpy statement of include/hagrid/overlap.h (same operations, same order, same truth values) ----------------
+
+def _edge_axis_separates(A, half, e, f, a, b):
+    """edge_axis_separates<A> of prims.h"""
+    if A == 0:
+        p0 = e[1] * a[2] - e[2] * a[1]; p1 = e[1] * b[2] - e[2] * b[1]; rad = f[2] * half[1] + f[1] * half[2]
+    elif A == 1:
+        p0 = e[2] * a[0] - e[0] * a[2]; p1 = e[2] * b[0] - e[0] * b[2]; rad = f[2] * half[0] + f[0] * half[2]
+    else:
+        p0 = e[0] * a[1] - e[1] * a[0]; p1 = e[0] * b[1] - e[1] * b[0]; rad = f[1] * half[0] + f[0] * half[1]
+    return (np.fmin(p0, p1) > rad) | (np.fmax(p0, p1) < -rad)
+
+
+def _tri_box(T, lo, hi):
+    """intersect_tri_box<true, true> of prims.h on broadcastable float32 arrays: T = the 12 columns of the Tri records, lo / hi = (x, y, z)"""
+    zero, half_ = np.float32(0.0), np.float32(0.5)
+    v0, e1, e2, n = (T[0], T[1], T[2]), (T[4], T[5], T[6]), (T[8], T[9], T[10]), (T[3], T[7], T[11])
+    near = tuple(np.where(n[i] > zero, lo[i], hi[i]) for i in range(3))
+    far = tuple(np.where(n[i] <= zero, lo[i], hi[i]) for i in range(3))
+    d = _dot3(v0, n)
+    s0 = _dot3(n, near) - d
+    s1 = _dot3(n, far) - d
+    ok = s1 * s0 <= zero
+    v1 = _sub3(v0, e1); v2 = (v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2])
+    for i in range(3):
+        ok = ok & ~((np.fmin(v0[i], np.fmin(v1[i], v2[i])) > hi[i]) | (np.fmax(v0[i], np.fmax(v1[i], v2[i])) < lo[i]))
+    c = tuple((hi[i] + lo[i]) * half_ for i in range(3)); half = tuple((hi[i] - lo[i]) * half_ for i in range(3))
+    w0, w1, w2 = _sub3(v0, c), _sub3(v1, c), _sub3(v2, c)
+    e3 = (e1[0] + e2[0], e1[1] + e2[1], e1[2] + e2[2])
+    for e, pairs in ((e1, ((w0, w2), (w0, w2), (w1, w2))), (e2, ((w0, w1), (w0, w1), (w1, w2))), (e3, ((w0, w2), (w0, w2), (w0, w1)))):
+        f = (np.abs(e[0]), np.abs(e[1]), np.abs(e[2]))
+        for A in range(3):
+            ok = ok & ~_edge_axis_separates(A, half, e, f, pairs[A][0], pairs[A][1])
+    return ok
+
+
+def _box_rows(boxes) -> np.ndarray:
+    return np.ascontiguousarray(boxes).view(np.float32).reshape(-1, 8)
+
+
+def overlap_pairs(tris: np.ndarray, boxes: np.ndarray) -> np.ndarray:
+    """Triangle i against box i (boxes: (n, 8) float32 rows or BOX_QUERY_DTYPE; `first` is not looked at): does the triangle MEET the box -- meets()
+    of include/hagrid/overlap.h, that is intersect_tri_box<true, true> of prims.h.  An inactive box (a NaN bound, min > max) meets nothing.  This is the
+    pair alone: a query clips its box first (clip_boxes)."""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); B = _box_rows(boxes)
+    lo = (B[:, 0], B[:, 1], B[:, 2]); hi = (B[:, 4], B[:, 5], B[:, 6])
+    with np.errstate(all="ignore"):
+        active = (lo[0] <= hi[0]) & (lo[1] <= hi[1]) & (lo[2] <= hi[2])
+        return _tri_box([T[:, i] for i in range(12)], lo, hi) & active
+
+
+def grid_box(tris: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """The box of the grid that the build makes over these triangles: the scene box enlarged by 0.1 % of its extent on every side (float32, the build's
+    expressions)."""
+    lo, hi = tris_bbox(tris)
+    d = ((hi - lo).astype(np.float32) * np.float32(0.001)).astype(np.float32)
+    return (lo - d).astype(np.float32), (hi + d).astype(np.float32)
+
+
+def clip_boxes(boxes: np.ndarray, grid_lo, grid_hi) -> np.ndarray:
+    """Clip of include/hagrid/overlap.h: (n, 8) float32 rows, every box clipped to the grid box grown by eps = 2^-16 of its largest |coordinate|
+    (lo = fmax(lo, grid min - eps), hi = fmin(hi, grid max + eps)); `first` is kept.  Inactive boxes (a NaN bound, min > max) stay as they are; a box
+    beyond the grid comes out with min > max."""
+    glo = np.asarray(grid_lo, np.float32); ghi = np.asarray(grid_hi, np.float32)
+    eps = np.float32(max(np.abs(glo).max(), np.abs(ghi).max())) * np.float32(1.52587890625e-05)
+    B = _box_rows(boxes).copy()
+    with np.errstate(all="ignore"):
+        active = (B[:, 0:3] <= B[:, 4:7]).all(axis=1)
+        B[active, 0:3] = np.fmax(B[active, 0:3], (glo - eps).astype(np.float32))
+        B[active, 4:7] = np.fmin(B[active, 4:7], (ghi + eps).astype(np.float32))
+    return B
+
+
+def overlap_boxes(tris: np.ndarray, boxes: np.ndarray, k: int = 8, chunk_pairs: int = 1 << 21, grid=None) -> dict:
+    """The definition of hagrid_overlap_boxes by brute force: every box, clipped (clip_boxes) to the box of the grid the query runs over -- `grid` =
+    (min, max), None: grid_box(tris), what the build makes over these triangles --, against every triangle, a chunk of boxes at a time.  With
+    S = {j >= first : j meets the clipped box}: "ids" (n, k) int32 = the min(k, |S|) smallest ids ascending, unused slots -1; "counts" = min(|S|, k + 1);
+    "sizes" = |S| (what the device does not report).  Inactive boxes and boxes beyond the grid: count 0, ids -1."""
+    glo, ghi = grid_box(tris) if grid is None else grid
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); B = clip_boxes(boxes, glo, ghi)
+    n, N = B.shape[0], T.shape[0]
+    first = B[:, 3].view(np.int32)
+    ids = np.full((n, k), -1, dtype=np.int32); sizes = np.zeros(n, dtype=np.int64)
+    cols = [T[None, :, i] for i in range(12)]
+    tid = np.arange(N, dtype=np.int64)[None, :]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        for o in range(0, n if N else 0, m):
+            b = B[o:o + m]
+            lo = (b[:, 0:1], b[:, 1:2], b[:, 2:3]); hi = (b[:, 4:5], b[:, 5:6], b[:, 6:7])
+            active = (lo[0] <= hi[0]) & (lo[1] <= hi[1]) & (lo[2] <= hi[2])
+            mask = _tri_box(cols, lo, hi) & active & (tid >= first[o:o + m, None])
+            sz = mask.sum(axis=1)
+            sizes[o:o + m] = sz
+            rows, col = np.nonzero(mask)                       # by row, then by id ascending
+            pos = np.arange(rows.size) - (np.cumsum(sz) - sz)[rows]
+            sel = pos < k
+            ids[o + rows[sel], pos[sel]] = col[sel]
+    return {"ids": ids, "counts": np.minimum(sizes, k + 1).astype(np.int32), "sizes": sizes}
+
+
+def lattice_boxes(origin, size, n) -> np.ndarray:
+    """The boxes of hagrid_overlap_lattice as BOX_QUERY_DTYPE records, x fastest: voxel c of an axis is [origin + float(c) * size,
+    origin + float(c + 1) * size] -- neighbouring voxels share their faces bit for bit; first = 0."""
+    origin = np.asarray(origin, np.float32); size = np.asarray(size, np.float32)
+    nx, ny, nz = (int(v) for v in n)
+    out = np.zeros(nx * ny * nz, dtype=BOX_QUERY_DTYPE)
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    for a, c in enumerate((x.reshape(-1), y.reshape(-1), z.reshape(-1))):
+        out["min"][:, a] = origin[a] + c.astype(np.float32) * size[a]
+        out["max"][:, a] = origin[a] + (c + 1).astype(np.float32) * size[a]
     return out
 
 

@@ -1,0 +1,294 @@
+// hagrid/overlap.h -- box-overlap queries (hagrid_amd.h: hagrid_overlap_boxes, hagrid_overlap_lattice): for an axis-aligned box, the k smallest
+// ids of the triangles that meet it.  No counterpart in the reference, which answers questions about rays only.
+//
+// Everything is float32 without contraction (-ffp-contract=off), every sum in the order written.  The same functions serve the gfx950
+// kernel (hagrid_amd/csrc/overlap.hip) and host programs (tests/cpp/overlap_host.cpp); hagrid_amd/scene.py (overlap_pairs, overlap_boxes,
+// lattice_boxes) states the same operations in numpy and gives the same bits.
+//
+// ---- one triangle, one box ------------------------------------------------------------------------------------------------------
+// Triangle j MEETS the box [lo, hi] exactly when intersect_tri_box<true, true>(v0, e1, e2, n, lo, hi) of prims.h says so: the plane of
+// the triangle against the box, the three box axes, the nine cross axes, in the expression order of that header.  As a truth value this
+// is the reference's intersect_prim_cell AND the bounds check -- the test the build itself inserts triangles with, plus the box axes.
+//
+// ---- the query ------------------------------------------------------------------------------------------------------------------
+// A box record is 32 bytes, the layout of BBox: min.xyz, int32 `first` (the pad slot after min), max.xyz, pad 0.  With
+// S = {j >= first : j meets the box}, m = |S| and 1 <= k <= 8 the answer is the min(k, m) smallest ids of S, ascending, in k slots (unused
+// slots -1), and count = min(m, k + 1): k + 1 says "there are more".  So the list for k is a prefix of the list for k + 1, and a caller
+// pages through S by asking again with first = last id + 1.  A full, variable-length list is NOT offered: a triangle is referenced by
+// several cells, the build inserts by the separating-axis test and not by the bounding box (so no cell is the canonical owner of a
+// triangle inside a box), and expanded cell boxes overlap -- an exact list would need de-duplication across cells.  "The k smallest ids"
+// does not care how often a triangle is offered.
+//   * an INACTIVE box -- a NaN bound, or min > max on an axis -- has count 0, ids -1 and takes no walk;
+//   * a box with min == max is a point and gets whatever the test says;
+//   * THE CLIP: the query runs over a grid, and before anything else the box is clipped to the grid box grown by eps = GridConsts::abs_margin
+//     on every side (Clip: lo = fmax2(lo, grid min - eps), hi = fmin2(hi, grid max + eps)); S is defined by the test against the CLIPPED box, in
+//     the brute force as in the walk.  Every triangle lies inside the grid box ((b) below), so in exact arithmetic this removes no triangle
+//     from S; a box inside the grown grid box keeps its bits.  What it buys: infinite and huge bounds are legal and well defined.  Handed to
+//     the test as they are they would make the box centre and half extent inf or NaN (or swallow the triangle's coordinates), the cross axes
+//     would never separate, and triangles whose bounding box overlaps the box but which have no point in it would count as meeting it -- an
+//     answer no walk over cells can reproduce.  A box that the clip turns inside out lies beyond the grid and meets nothing.
+//   * ANY (HAGRID_OVERLAP_ANY, k = 1): the walk stops at the first triangle that meets the box; the id is SOME member of S or -1, count 0 or 1.
+// The lattice form makes its boxes itself: voxel (x, y, z) of an nx * ny * nz lattice, x fastest, is lo = origin + float(c) * size,
+// hi = origin + float(c + 1) * size per axis (neighbouring voxels share their faces bit for bit), first = 0.
+//
+// ---- the list -------------------------------------------------------------------------------------------------------------------
+// IdList keeps the ids in eight compile-time slots (the HitList of multi_hit.h on ids only: every loop over compile-time indices, so the
+// array lives in registers), sorted, each id once.  `more` is set when a triangle that meets the box is not in a full list (it was
+// refused, or it fell off the end).  Which triangles skip the test: ids below `first` and ids already listed, always; ids above the
+// last slot of a full list once `more` is set -- they can change neither the list nor the flag.
+//
+// ---- the walk -------------------------------------------------------------------------------------------------------------------
+// overlap_query walks the construction format (entries -> cells | small_cells -> ref_ids) and returns exactly what brute_force gives
+// over all triangles, both for the clipped box.  (1) The box's voxel range: both corners moved OUTWARD by eps = GridConsts::abs_margin (2^-16 of the largest
+// |coordinate| of the grid box, the margin of closest.h), to voxel coordinates, clamped in float to [0, dims - 1], cast; a box that lies
+// beyond a face of the grid by more than the margin ends here.  (2) The top-level cells of that range.  (3) Each one's sub-blocks,
+// keeping a sub-block only if its INTEGER voxel range meets the box's: no float pruning, no ring search.  (4) The list of the cell of
+// every leaf reached; the cell tested last is recognised and skipped, and testing a cell twice changes nothing.  Why it is sound:
+//   (a) a cell's reference list holds every triangle that meets the cell's box (closest.h (a): the build puts a triangle into every voxel
+//       it overlaps, merging unites lists, expansion grows a cell only over neighbours whose lists are subsets or whose extra triangles
+//       miss the grown region);
+//   (b) every triangle lies inside the grid box, so the part of a box beyond a face of the grid meets nothing (the bounds check refuses it);
+//   (c) the clipped box is finite and no larger than the grid box plus the margin, so the test runs on coordinates of the scene's magnitude and
+//       is the separating-axis test it is meant to be: a triangle that meets the box has a point inside it (up to rounding far below eps) and
+//       inside the grid; the voxel that holds this point lies in the voxel range
+//       -- the float voxel coordinate of a corner is off by a few ulp of the largest coordinate, and the build's own decision for that
+//       voxel (the same test in float, the truncating casts of compute_range) by a few more: all far inside eps = 128 ulp -- and the
+//       leaf of that voxel is reached, because the integer range of every sub-block above it contains the voxel; by (a) the cell of the
+//       leaf lists the triangle.
+// Three counts per box: cells visited, triangle / box tests evaluated, sub-blocks pruned.
+#ifndef HAGRID_OVERLAP_H
+#define HAGRID_OVERLAP_H
+
+#include "closest.h"
+#include "grid.h"
+#include "multi_hit.h"
+#include "prims.h"
+#include "vec.h"
+
+namespace hagrid {
+namespace overlap {
+
+using closest::GridConsts;
+using closest::CellRec;
+using closest::ArrayStack;
+using closest::kMaxLevels;
+
+constexpr int kMaxIds = 8;
+
+struct Counts { int cells, sats, pruned; };
+
+/// the pair: does the triangle meet the box?
+HOST DEVICE inline bool meets(const Tri& tri, const vec3& lo, const vec3& hi) {
+    return intersect_tri_box<true, true>(tri.v0, tri.e1, tri.e2, tri.normal(), lo, hi);
+}
+
+/// a NaN bound, or min > max on an axis
+HOST DEVICE inline bool inactive(const vec3& lo, const vec3& hi) { return !(lo.x <= hi.x) || !(lo.y <= hi.y) || !(lo.z <= hi.z); }
+
+/// the grid box grown by the absolute margin: what every query box is clipped to before the test (THE CLIP above)
+struct Clip {
+    vec3 lo, hi;
+    HOST DEVICE void set(const vec3& grid_lo, const vec3& grid_hi) {
+        const float eps = GridConsts::abs_margin(grid_lo, grid_hi);
+        lo = vec3(grid_lo.x - eps, grid_lo.y - eps, grid_lo.z - eps);
+        hi = vec3(grid_hi.x + eps, grid_hi.y + eps, grid_hi.z + eps);
+    }
+    /// false: nothing is left of the box (it was inactive, or it lies beyond the grid)
+    HOST DEVICE bool apply(vec3& blo, vec3& bhi) const {
+        if (inactive(blo, bhi)) return false;
+        blo = vec3(detail::fmax2(blo.x, lo.x), detail::fmax2(blo.y, lo.y), detail::fmax2(blo.z, lo.z));
+        bhi = vec3(detail::fmin2(bhi.x, hi.x), detail::fmin2(bhi.y, hi.y), detail::fmin2(bhi.z, hi.z));
+        return !inactive(blo, bhi);
+    }
+};
+
+/// voxel c of a lattice along one axis
+HOST DEVICE inline float lattice_face(float origin, int c, float size) { return origin + float(c) * size; }
+
+template <int KMAX>
+struct IdList {
+    int id[KMAX];
+    int cap;            ///< k: slots in use, 1 .. KMAX
+    int last;           ///< copy of slot cap - 1: the list is full when last >= 0
+    int first;          ///< only ids >= first take part
+    bool more;          ///< a triangle that meets the box is not in the (full) list
+
+    HOST DEVICE void init(int k, int first_) {
+        cap = k; last = -1; first = first_; more = false;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) id[j] = -1;
+    }
+
+    HOST DEVICE bool found() const { return id[0] >= 0; }
+
+    /// does `ref` need the test at all?
+    HOST DEVICE bool wants(int ref) const {
+        if (ref < first) return false;
+        if (more && last >= 0 && ref > last) return false;
+        bool dup = false;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) dup = dup || id[j] == ref;
+        return !dup;
+    }
+
+    /// `ref` meets the box (and wants() said yes): it sinks to its sorted place, pushing the rest one slot down; what is left over at the
+    /// end -- `ref` itself or the id that fell off slot cap - 1 -- is a member of S outside the list
+    HOST DEVICE void take(int ref) {
+        int ci = ref;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) {
+            const bool t = j < cap && (id[j] < 0 || ci < id[j]);
+            const int oi = id[j];
+            id[j] = t ? ci : oi;
+            ci = t ? oi : ci;
+        }
+        if (ci >= 0) more = true;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++)
+            if (j == cap - 1) last = id[j];
+    }
+
+    /// min(m, k + 1)
+    HOST DEVICE int count() const {
+        int c = more ? 1 : 0;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) c += (j < cap && id[j] >= 0) ? 1 : 0;
+        return c;
+    }
+};
+
+/// the definition: every triangle, in order, against the clipped box.  tri_at(j) -> Tri.  Returns the number of tests evaluated.
+template <typename F, typename L>
+HOST DEVICE inline int brute_force(F tri_at, int num_tris, const Clip& clip, const vec3& box_lo, const vec3& box_hi, bool any, L& list) {
+    int sats = 0;
+    vec3 lo = box_lo, hi = box_hi;
+    if (!clip.apply(lo, hi)) return sats;
+    for (int j = 0; j < num_tris; j++) {
+        if (!list.wants(j)) continue;
+        sats++;
+        if (meets(tri_at(j), lo, hi)) {
+            list.take(j);
+            if (any) break;
+        }
+    }
+    return sats;
+}
+
+// ---- the walk ------------------------------------------------------------------------------------------------------------------
+
+struct VoxelRange { int lx, ly, lz, hx, hy, hz; };     ///< inclusive
+
+/// a float voxel coordinate into [0, dmax] (NaN -> 0), then the cast
+HOST DEVICE inline int clamp_cast(float f, float dmax) {
+    float a = f > 0.0f ? f : 0.0f;
+    a = a < dmax ? a : dmax;
+    return int(a);
+}
+
+/// false: the box lies beyond a face of the grid
+HOST DEVICE inline bool voxel_range(const GridConsts& c, const vec3& lo, const vec3& hi, VoxelRange& r) {
+    const float lx = ((lo.x - c.eps) - c.lo.x) * c.inv.x, ly = ((lo.y - c.eps) - c.lo.y) * c.inv.y, lz = ((lo.z - c.eps) - c.lo.z) * c.inv.z;
+    const float hx = ((hi.x + c.eps) - c.lo.x) * c.inv.x, hy = ((hi.y + c.eps) - c.lo.y) * c.inv.y, hz = ((hi.z + c.eps) - c.lo.z) * c.inv.z;
+    const float dx = float(c.dims.x), dy = float(c.dims.y), dz = float(c.dims.z);
+    if (hx < 0.0f || hy < 0.0f || hz < 0.0f || lx >= dx || ly >= dy || lz >= dz) return false;
+    r.lx = clamp_cast(lx, float(c.dims.x - 1)); r.ly = clamp_cast(ly, float(c.dims.y - 1)); r.lz = clamp_cast(lz, float(c.dims.z - 1));
+    r.hx = clamp_cast(hx, float(c.dims.x - 1)); r.hy = clamp_cast(hy, float(c.dims.y - 1)); r.hz = clamp_cast(hz, float(c.dims.z - 1));
+    return true;
+}
+
+/// does the block of 2^s voxels per axis at (x, y, z) miss the range?
+HOST DEVICE inline bool misses(const VoxelRange& r, int x, int y, int z, int s) {
+    const int e = 1 << s;
+    return x > r.hx || x + e <= r.lx || y > r.hy || y + e <= r.ly || z > r.hz || z + e <= r.lz;
+}
+
+/// the list of one cell.  G: c (GridConsts), clip (Clip), word(i), cell(i) -> CellRec, ref(i), tri(id)
+template <typename G, typename L>
+HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bool any, uint32_t index, L& list, Counts& n) {
+    const CellRec c = g.cell(index);
+    n.cells++;
+    if (c.begin < 0) return;
+    for (int i = c.begin; i < c.end; i++) {
+        const int ref = g.ref(i);
+        if (ref < 0) break;
+        if (!list.wants(ref)) continue;
+        n.sats++;
+        if (meets(g.tri(ref), lo, hi)) {
+            list.take(ref);
+            if (any) return;
+        }
+    }
+}
+
+/// one top-level cell of the range: descend its sub-blocks while their voxel ranges meet the box's
+template <typename G, typename S, typename L>
+HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3& hi, bool any, const VoxelRange& r, int tx, int ty, int tz, uint32_t& last_cell,
+                                  L& list, Counts& n) {
+    const GridConsts& c = g.c;
+    int rs = c.shift;                                   // the current node covers 2^rs voxels per axis from (ox, oy, oz)
+    int ox = tx << rs, oy = ty << rs, oz = tz << rs;
+    const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
+    if (!(top_w & 3u)) {
+        const uint32_t ci = top_w >> 2;
+        if (ci != last_cell) { last_cell = ci; test_cell(g, lo, hi, any, ci, list, n); }
+        return;
+    }
+    int level = 0;
+    st.set(0, top_w, 0u);
+    while (level >= 0) {
+        const uint32_t nw = st.w(level), idx = st.i(level);
+        const int l = int(nw & 3u);
+        if (idx >= (1u << (3 * l))) {                   // this node is done: back to its parent
+            level--;
+            if (level >= 0) {
+                rs += int(st.w(level) & 3u);
+                const int keep = ~((1 << rs) - 1);
+                ox &= keep; oy &= keep; oz &= keep;
+            }
+            continue;
+        }
+        st.set_i(level, idx + 1u);
+        const int m = (1 << l) - 1, s = rs - l;
+        if (s < 0) continue;                            // not a valid voxel map
+        const int cx = ox + ((int(idx) & m) << s), cy = oy + (((int(idx) >> l) & m) << s), cz = oz + ((int(idx) >> (2 * l)) << s);
+        if (misses(r, cx, cy, cz, s)) { n.pruned++; continue; }
+        const uint32_t cw = g.word((nw >> 2) + idx);
+        if (!(cw & 3u)) {
+            const uint32_t ci = cw >> 2;
+            if (ci != last_cell) {
+                last_cell = ci;
+                test_cell(g, lo, hi, any, ci, list, n);
+                if (any && list.found()) return;
+            }
+        } else if (level + 1 < kMaxLevels) {
+            level++;
+            st.set(level, cw, 0u);
+            rs = s; ox = cx; oy = cy; oz = cz;
+        }
+    }
+}
+
+/// the answer for the box [lo, hi] over the grid g: equal to brute_force over all triangles (with ANY: some member of S, or none).
+/// `list` arrives initialised (init(k, first)).
+template <typename G, typename S, typename L>
+HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, const vec3& box_hi, bool any, L& list, Counts& n) {
+    const GridConsts& c = g.c;
+    n.cells = 0; n.sats = 0; n.pruned = 0;
+    vec3 lo = box_lo, hi = box_hi;
+    if (!g.clip.apply(lo, hi)) return;
+    VoxelRange r;
+    if (!voxel_range(c, lo, hi, r)) return;
+    uint32_t last_cell = 0xffffffffu;
+    const int x0 = r.lx >> c.shift, x1 = r.hx >> c.shift, y0 = r.ly >> c.shift, y1 = r.hy >> c.shift, z0 = r.lz >> c.shift, z1 = r.hz >> c.shift;
+    for (int z = z0; z <= z1; z++)
+        for (int y = y0; y <= y1; y++)
+            for (int x = x0; x <= x1; x++) {
+                visit_top(g, st, lo, hi, any, r, x, y, z, last_cell, list, n);
+                if (any && list.found()) return;
+            }
+}
+
+} // namespace overlap
+} // namespace hagrid
+
+#endif // HAGRID_OVERLAP_H

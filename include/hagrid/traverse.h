@@ -51,6 +51,22 @@ inline void closest_points(const Grid& grid, const Tri* tris, const void* points
     detail::check(detail::current_ctx(), hagrid_closest_points(detail::current_ctx(), &p, tris, points, results, num_points, counters, 0u));
 }
 
+/// Extension: box-overlap queries (hagrid_amd.h: hagrid_overlap_boxes, hagrid_overlap_lattice; the test, the list and the walk: overlap.h).  boxes:
+/// num_boxes records of 32 bytes (BBox with `first` in the pad slot after min), ids: num_boxes * k int32, counts: nullptr or num_boxes int32, counters:
+/// nullptr or int64[4] -- all DEVICE pointers.  any: stop at the first triangle that meets the box (k must be 1).  Asynchronous on the context's stream.
+inline void overlap_boxes(const Grid& grid, const Tri* tris, const BBox* boxes, int num_boxes, int k, int* ids, int* counts = nullptr, void* counters = nullptr, bool any = false) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_overlap_boxes(detail::current_ctx(), &p, tris, boxes, num_boxes, k, ids, counts, counters, any ? HAGRID_OVERLAP_ANY : 0u));
+}
+/// The voxels of an n.x * n.y * n.z lattice (x fastest; voxel c of an axis is [origin + float(c) * size, origin + float(c + 1) * size]) as the boxes.
+inline void overlap_lattice(const Grid& grid, const Tri* tris, const vec3& origin, const vec3& size, const ivec3& n, int k, int* ids, int* counts = nullptr, void* counters = nullptr,
+                            bool any = false) {
+    hagrid_grid p = detail::to_pod(grid);
+    const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {size.x, size.y, size.z};
+    const int m[3] = {n.x, n.y, n.z};
+    detail::check(detail::current_ctx(), hagrid_overlap_lattice(detail::current_ctx(), &p, tris, o, s, m, k, ids, counts, counters, any ? HAGRID_OVERLAP_ANY : 0u));
+}
+
 /// Extension: independent batches in flight.  Every MemManager is a context with a stream of its own (hagrid_ctx_set_stream on
 /// mem.context()); `share_traversal(dst, src)` lets `dst` traverse with the traversal image setup_traversal built in `src`, and the
 /// overload below traverses on a named manager instead of the current one.  Two 1M-ray batches in flight take 0.118 ms each

@@ -283,6 +283,35 @@ int hagrid_traverse_grid_multi(hagrid_ctx* ctx, const hagrid_grid* grid, const v
 int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, void* results,
                           int num_points, void* counters, uint32_t flags);
 
+/* Extension (no reference counterpart): BOX-OVERLAP queries -- for every axis-aligned box of a batch, which triangles meet it (contact candidates,
+ * culling, sparse-volume allocation, surface voxelization).  Triangle j MEETS the box [lo, hi] exactly when intersect_tri_box<true, true>(v0, e1, e2, n,
+ * lo, hi) of include/hagrid/prims.h says so: the triangle's plane, the three box axes and the nine cross axes, float32 without contraction in the
+ * expression order of that header (as a truth value: the reference's intersect_prim_cell AND the bounds check).  A box record is 32 bytes, the layout
+ * of BBox: float32 min.xyz, int32 first (the pad slot after min; only ids >= first are reported, zero bits = everything), float32 max.xyz, pad 0.
+ * With S_i = {j >= first : j meets box i}, m = |S_i| and 1 <= k <= HAGRID_MAX_OVERLAP_IDS:
+ *   ids[i*k .. i*k + k-1]  (int32) the min(k, m) smallest ids of S_i, ascending; unused slots -1;
+ *   counts[i]              (int32, counts may be NULL) min(m, k + 1): k + 1 says "there are more".
+ * So the list for k is a prefix of the list for k + 1, and a caller pages through S_i with first = last id + 1.  Variable-length lists and exact counts
+ * above k + 1 are not offered (a triangle is referenced by several cells; include/hagrid/overlap.h).  An INACTIVE box -- a NaN bound, or
+ * min > max on an axis -- has count 0 and ids -1; a box with min == max is a point.  Before the test every box is CLIPPED to the grid box grown
+ * by 2^-16 of its largest |coordinate| (no triangle lies outside the grid box, so nothing is lost; a box inside keeps its bits): infinite and huge bounds
+ * are legal and mean "no bound on this side", and a box beyond the grid meets nothing.  flags: 0 or HAGRID_OVERLAP_ANY (k must be 1): the walk stops at the first triangle that meets the box; ids[i] is SOME member of S_i or -1,
+ * counts[i] is 0 or 1.  One launch walks the CONSTRUCTION format over the box's voxel range (hagrid_amd/csrc/overlap.hip); the results are those of the
+ * brute force over all triangles against the clipped box.  The traversal image, ray binning and the hints kept for the nearest-hit path are neither used nor touched.
+ * counters: NULL, or DEVICE int64[4] to which the batch totals are ADDED (boxes, cells visited, triangle / box tests evaluated, sub-blocks pruned):
+ * clear it first.  Asynchronous on the context's stream.
+ * hagrid_overlap_lattice makes the boxes itself: voxel (x, y, z) of the n[0] x n[1] x n[2] lattice, x fastest, is lo = origin + float(c) * size,
+ * hi = origin + float(c + 1) * size per axis (neighbouring voxels share their faces bit for bit), first = 0; origin, size and n are HOST arrays of 3.
+ * HAGRID_EINVAL: a null grid or one released by hagrid_grid_release_for_traversal, k out of range, HAGRID_OVERLAP_ANY with k != 1, an unknown flag, null
+ * or misaligned buffers (triangles and boxes 16 bytes; ids 16 bytes for k = 4 and k = 8, else 4; counts 4; counters 8), num_boxes < 0, a lattice with n <= 0 on an axis or more than 2^31 - 1
+ * voxels, a voxel size that is not positive and finite, an origin that is not finite.  num_boxes = 0 is HAGRID_OK (null buffers are then fine). */
+#define HAGRID_MAX_OVERLAP_IDS 8
+#define HAGRID_OVERLAP_ANY 1u
+int hagrid_overlap_boxes(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* boxes, int num_boxes, int k,
+                         void* ids, void* counts, void* counters, uint32_t flags);
+int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, int k,
+                           void* ids, void* counts, void* counters, uint32_t flags);
+
 /* Extension (no reference counterpart): spatial binning of the ray batch before traversal.  mode 0 (default): rays
  * are traversed in buffer order, as the reference does.  mode 1: each hagrid_traverse_grid call first bins the rays by
  * the position where they enter the grid (512 Morton-ordered bins, counting sort on the device) and traverses them in
