@@ -34,6 +34,19 @@ int hagrid_kat_scan(hagrid_ctx* ctx, const int32_t* values, int n, int words, co
  * row_len rays, in block dispatch order (slots: 64 * ceil(num_rays / 64) ints; values >= num_rays mark idle lanes). */
 int hagrid_kat_detect_ray_rows(hagrid_ctx* ctx, const void* rays_dev, int num_rays, float bbox_diag, int32_t* row_len);
 int hagrid_kat_tile_slots(hagrid_ctx* ctx, int num_rays, int row_len, int super_log2, int xcd_chunk_log2, int32_t* slots);
+/* The two device sorts of ray_order.hip, run through the product's own host code on inputs of the caller's.
+ * Ray binning (hagrid_set_ray_binning) of num_rays rays in device memory against the box bbox_min3 .. bbox_max3, mode 1 (forced) or 2 (automatic): returns 1
+ * and perm_out[slot] = ray (num_rays ints), keys_out[ray] = Morton key of the ray's bin (num_rays 16-bit words, 0 .. 511); mode 2 also leaves the device's
+ * decision word in decision_out (1 = the batch is binned, 0 = left in buffer order: perm_out is then not meaningful, and for an image-ordered batch neither
+ * is keys_out); mode 1 leaves -1 there.  Returns 0 -- nothing launched, nothing written -- for batches of at most one tile (4096 rays), < 0 on errors. */
+int hagrid_kat_bin_rays(hagrid_ctx* ctx, const float* bbox_min3, const float* bbox_max3, const void* rays_dev, int num_rays, int mode,
+                        int32_t* perm_out, uint16_t* keys_out, int32_t* decision_out);
+/* The tile order of the tail kernel ("traverse.tile_order"): n costs (host, 1 .. 262 144 tiles) are sorted longest first with the order stored rotated by
+ * rot positions (clamped to 0 .. n) and "traverse.quad_head" = head_tenths.  order_out: the n tile indices as stored; cost_after_out: the n costs behind the
+ * sort (cleared); suggest_out: the tiles suggested for the four-lanes-per-ray head; sample_out8: the copy of the sample ray the sort leaves behind the
+ * order (ray 3 * (num_rays >> 3) of rays_dev: 8 floats). */
+int hagrid_kat_tile_order(hagrid_ctx* ctx, const int32_t* cost_in, int n, int rot, int head_tenths, const void* rays_dev, int num_rays,
+                          int32_t* order_out, int32_t* cost_after_out, int32_t* suggest_out, float* sample_out8);
 /* One launch of the headline kernel (table-free image with 20-bit slim records, nearest hit) in its timed instantiation: per block b
  * (64 rays) the 100 MHz wall clock at its start in times_dev[2b] and when its last lane left in times_dev[2b + 1] (the caller zeroes
  * the buffer).  row_len = image width of the batch; tail = 0 times the plain slim kernel instead; tile_order_dev (or null): block b

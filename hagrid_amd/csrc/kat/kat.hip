@@ -1,5 +1,6 @@
 // kat.hip -- known-answer hooks: the device versions of the L0 functions for the golden-vector tests, the lane <-> ray assignment of
-// the tile packets, the records of a traversal image read back voxel by voxel, and a timed instantiation of the headline kernel.
+// the tile packets, the two device sorts of ray_order.hip (ray binning, tile order) run on given inputs, the records of a traversal image read back voxel by
+// voxel, and a timed instantiation of the headline kernel.
 // TEST / DEV INFRASTRUCTURE: built into libhagrid_amd_kat.so (hagrid_amd/build.py), which links against the product library and is
 // loaded only by tests/ and tools/dev_*.py; the product library carries none of this.  Declarations: kat/hagrid_amd_kat.h.
 #include "../trav_kernels.h"
@@ -219,6 +220,70 @@ extern "C" int hagrid_kat_detect_ray_rows(hagrid_ctx* ctx, const void* rays_dev,
     HG_TRY(read_back(ctx, d, row_len, sizeof(int)));
     *row_len &= kRowLenMask;                               // (bit 30: found from the origins alone)
     return HAGRID_OK;
+}
+
+// Ray binning as the product runs it (ray_order.hip bin_rays: keys, scan, scatter; mode 2 with the row-length detection and the device's decision in front).
+// Returns 1 with the permutation and the keys, 0 when bin_rays left the batch alone (at most one tile of rays: nothing was launched), < 0 on errors.
+extern "C" int hagrid_kat_bin_rays(hagrid_ctx* ctx, const float* bbox_min3, const float* bbox_max3, const void* rays_dev, int num_rays, int mode,
+                                   int32_t* perm_out, uint16_t* keys_out, int32_t* decision_out) {
+    if (!ctx || !bbox_min3 || !bbox_max3 || !rays_dev || num_rays <= 0 || (mode != 1 && mode != 2) || !perm_out || !keys_out) return HAGRID_EINVAL;
+    TraverseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rays = static_cast<const float4*>(rays_dev); a.num_rays = num_rays;
+    a.min_x = bbox_min3[0]; a.min_y = bbox_min3[1]; a.min_z = bbox_min3[2];
+    a.max_x = bbox_max3[0]; a.max_y = bbox_max3[1]; a.max_z = bbox_max3[2];
+    if (decision_out) *decision_out = -1;
+    if (num_rays > 4096) {
+        // (best effort: buffers of the sizes bin_rays is about to take, filled with ones and given back -- a pool that keeps its buffers hands the sort these, so
+        // what an earlier call over as many rays left there cannot stand in for a slot this one skips)
+        PoolTemps pre(ctx);
+        int* p0 = pre.get<int>(size_t(num_rays)); unsigned short* p1 = pre.get<unsigned short>(size_t(num_rays));
+        if (p0) HG_TRY(hagrid_mem_one(ctx, p0, size_t(num_rays) * sizeof(int)));
+        if (p1) HG_TRY(hagrid_mem_one(ctx, p1, size_t(num_rays) * sizeof(unsigned short)));
+    }
+    PoolTemps tmp(ctx);
+    const int saved = ctx->ray_binning;
+    ctx->ray_binning = mode;
+    const int rc = bin_rays(ctx, a, num_rays, tmp);
+    ctx->ray_binning = saved;
+    HG_TRY(rc);
+    HG_HIP(ctx, hipGetLastError());
+    if (!a.perm) return 0;
+    if (tmp.ptrs.size() < 2 || tmp.ptrs[0] != a.perm || !tmp.ptrs[1]) HG_FAIL(ctx, HAGRID_EINVAL, "kat_bin_rays: bin_rays no longer takes perm and keys first from its pool temporaries");
+    HG_TRY(hagrid_mem_copy_d2h(ctx, perm_out, a.perm, size_t(num_rays) * sizeof(int)));          // (mode 2 with decision 0: never written -- whatever the pool slot held)
+    HG_TRY(hagrid_mem_copy_d2h(ctx, keys_out, tmp.ptrs[1], size_t(num_rays) * sizeof(uint16_t)));
+    if (decision_out && a.perm_flag) HG_TRY(hagrid_mem_copy_d2h(ctx, decision_out, a.perm_flag, sizeof(int)));
+    return 1;
+}
+
+// The tile-order sort as the tail kernel's host code runs it (ray_order.hip tile_order_buffers + launch_tile_order) on the costs given, with buffers of
+// its own: the order as stored (rotated by rot), the cost array behind the sort, the suggested head share and the copy of the sample ray (2 float4).
+extern "C" int hagrid_kat_tile_order(hagrid_ctx* ctx, const int32_t* cost_in, int n, int rot, int head_tenths, const void* rays_dev, int num_rays,
+                                     int32_t* order_out, int32_t* cost_after_out, int32_t* suggest_out, float* sample_out8) {
+    if (!ctx || !cost_in || n <= 0 || n > kMaxOrderTiles || head_tenths < 0 || head_tenths > 1000 || !rays_dev || num_rays <= 0 ||
+        !order_out || !cost_after_out || !suggest_out || !sample_out8) return HAGRID_EINVAL;
+    hagrid_ctx::RayHints h;
+    if (!tile_order_buffers(ctx, h, n)) return HAGRID_ENOMEM;
+    struct Release { hagrid_ctx* ctx; hagrid_ctx::RayHints& h; ~Release() { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.lpt_buf); } } release{ctx, h};
+    if (h.lpt_cap < n) HG_FAIL(ctx, HAGRID_EINVAL, "kat_tile_order: buffers smaller than the launch");
+    const int32_t unset = -1;
+    Staged sg(ctx, &unset, sizeof(int));
+    if (!sg.d) return HAGRID_ENOMEM;
+    HG_TRY(hagrid_mem_copy_h2d(ctx, h.lpt_buf, cost_in, size_t(n) * sizeof(int)));
+    // (order and samples start as ones, not as the zeroes of a fresh buffer: a position the sort skips must not read as tile 0)
+    HG_HIP(ctx, hipMemsetAsync(h.lpt_buf + h.lpt_cap, 0xFF, size_t(h.lpt_cap) * sizeof(int) + 8 * sizeof(float4), ctx->stream));
+    TraverseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rays = static_cast<const float4*>(rays_dev); a.num_rays = num_rays;
+    const int saved = ctx->opt_quad_head;
+    ctx->opt_quad_head = head_tenths;
+    launch_tile_order(ctx, h, n, a, rot, static_cast<int*>(sg.d));
+    ctx->opt_quad_head = saved;
+    HG_HIP(ctx, hipGetLastError());
+    HG_TRY(hagrid_mem_copy_d2h(ctx, order_out, h.lpt_buf + h.lpt_cap, size_t(n) * sizeof(int)));
+    HG_TRY(hagrid_mem_copy_d2h(ctx, cost_after_out, h.lpt_buf, size_t(n) * sizeof(int)));
+    HG_TRY(hagrid_mem_copy_d2h(ctx, sample_out8, tile_order_samples(h), 2 * sizeof(float4)));
+    return sg.fetch(suggest_out);
 }
 
 extern "C" int hagrid_kat_tile_slots(hagrid_ctx* ctx, int num_rays, int row_len, int super_log2, int xcd_chunk_log2, int32_t* slots) {

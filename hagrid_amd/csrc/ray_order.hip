@@ -402,7 +402,7 @@ int bin_rays_bits(hagrid_ctx* ctx, TraverseArgs& a, int num_rays, PoolTemps& tmp
     constexpr int kBins = 1 << (3 * BITS);
     const int tiles = grid_blocks(num_rays, kBinTile);
     const int table_n = kBins * tiles;
-    int* perm = tmp.get<int>(size_t(num_rays));
+    int* perm = tmp.get<int>(size_t(num_rays));                                   // (perm, then the keys: the known-answer hook kat/kat.hip hagrid_kat_bin_rays reads the keys as tmp's second buffer)
     unsigned short* bin_keys = tmp.get<unsigned short>(size_t(num_rays));
     int* bin_table = tmp.get<int>(size_t(table_n));
     int* bin_partials = tmp.get<int>(size_t(scan_num_tiles(table_n)) + 1);

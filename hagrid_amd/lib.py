@@ -173,6 +173,8 @@ KAT_SIGNATURES = {
     "hagrid_kat_detect_ray_rows": (_i32, [_vp, _vp, _i32, C.c_float, _vp]),
     "hagrid_kat_image_records": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "hagrid_kat_tile_slots": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp]),
+    "hagrid_kat_bin_rays": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "hagrid_kat_tile_order": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "hagrid_kat_traverse_timed": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 

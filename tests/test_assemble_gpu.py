@@ -12,6 +12,7 @@ import pytest
 
 import _assemble_scene as S
 import _subproc
+from _poison import alloc_out, fetch
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
@@ -112,11 +113,10 @@ def test_stadium_mesh_assembled_on_the_device_builds_the_oracles_grid(mem):
     tV = torch.from_numpy(V).cuda(); tF = torch.from_numpy(F).cuda()
     torch.cuda.synchronize()
     ms = api.MeshScene(mem, [(tV.data_ptr(), V.shape[0], tF.data_ptr(), n)])
-    d_tris = mem.alloc(48 * n)
-    mem.zero(d_tris, 48 * n)
+    d_tris = alloc_out(mem, 48 * n)
     ms.assemble(0, d_tris)
     assert ms.bad_indices() == 0
-    assert mem.download(d_tris, np.float32, 12 * n).tobytes() == tris.tobytes()
+    assert fetch(mem, d_tris, np.float32, 12 * n).tobytes() == tris.tobytes()
     grid = api.build_all(mem, d_tris, n)
     G = O.Grid.full(tris)
     d = grid.download()
@@ -124,10 +124,10 @@ def test_stadium_mesh_assembled_on_the_device_builds_the_oracles_grid(mem):
     assert (d["entries"] == G.entries).all() and (d["ref_ids"] == G.ref_ids).all() and d["cells"].tobytes() == G.cells.tobytes()
     rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 1024, 512)
     want, _ = G.traverse(tris, rays, nthreads=8)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
     api.setup_traversal(grid)
     api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-    hits = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+    hits = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
     assert (hits["id"] == want["id"]).all() and (bits(hits["t"]) == bits(want["t"])).all()
     assert 0 < (want["id"] >= 0).sum()
     for p in (d_rays, d_hits, d_tris):
@@ -335,8 +335,8 @@ def test_argument_errors_zero_triangles_and_memory(mem):
 
     # the context still assembles
     v = np.float32([[0, 0, 0], [1, 0, 0], [0, 1, 0]])
-    d_v = mem.upload(v); d_t = mem.alloc(48)
+    d_v = mem.upload(v); d_t = alloc_out(mem, 48)
     ms = api.MeshScene(mem, [(d_v, 3, 0, 1)])
     ms.assemble(0, d_t)
-    assert same_tris(mem.download(d_t, np.float32, 12).reshape(1, 12), scene.tris_from_vertices(v[0:1], v[1:2], v[2:3]))
+    assert same_tris(fetch(mem, d_t, np.float32, 12).reshape(1, 12), scene.tris_from_vertices(v[0:1], v[1:2], v[2:3]))
     ms.close(); mem.free(d_v); mem.free(d_t)

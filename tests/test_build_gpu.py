@@ -5,6 +5,8 @@ import pytest
 
 from hagrid_amd import scene
 
+from _poison import alloc_out, assert_all_written, fetch, poison
+
 pytestmark = pytest.mark.gpu
 
 
@@ -149,10 +151,10 @@ def test_build_then_traverse_matches_reference_bruteforce(mem, golden_dir):
     d_tris = mem.upload(tris)
     for compress in (False, True):
         grid = api.build_all(mem, d_tris, tris.shape[0], compress=compress)
-        d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+        d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
         api.setup_traversal(grid)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-        hits = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+        hits = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
         assert (hits["id"] == g["id"]).all()
         assert (hits["t"].view(np.uint32) == g["t"].view(np.uint32)).all()
         mem.free(d_rays); mem.free(d_hits); grid.free()
@@ -215,9 +217,9 @@ def test_build_scene_with_huge_triangles(mem):
     grid, G, d_tris = run_stages(mem, tris)
     rays = scene.make_rays_incoherent(G.bbox_min, G.bbox_max, 100000, 3)
     from hagrid_amd import api
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
     api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-    hits = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+    hits = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
     want, _ = G.traverse(tris, rays, nthreads=8)
     assert (hits["id"] == want["id"]).all() and (hits["t"].view(np.uint32) == want["t"].view(np.uint32)).all()
     assert (hits["id"] >= soup.shape[0]).mean() > 0.3          # the big triangles are what most rays hit
@@ -236,9 +238,9 @@ def test_build_degenerate_inputs(mem):
     assert max(np.diff(np.stack([G.small_cells["begin"], np.roll(G.small_cells["begin"], -1)]), axis=0).max(), 1) > 0
     from hagrid_amd import api
     rays = scene.make_rays_incoherent(G.bbox_min, G.bbox_max, 50000, 8)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
     api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-    hits = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+    hits = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
     want, _ = G.traverse(tris, rays, nthreads=8)
     assert (hits["id"] == want["id"]).all() and (hits["t"].view(np.uint32) == want["t"].view(np.uint32)).all()
     # of 3000 coincident triangles either the first tested wins (ascending lists -> the smallest id) or, for rays where
@@ -267,9 +269,9 @@ def test_precise_expansion_matches_oracle(mem):
         mem.set_option("expand.subset_only", 1)
     assert_same_grid(grid.download(), G, "precise expand")
     rays = scene.make_rays_incoherent(G.bbox_min, G.bbox_max, 100000, 6)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
     api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-    hits = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+    hits = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
     bf = O.brute_force(tris, rays[:20000], nthreads=8)
     assert (hits["id"][:20000] == bf["id"]).all() and (hits["t"][:20000].view(np.uint32) == bf["t"].view(np.uint32)).all()
     mem.free(d_rays); mem.free(d_hits); grid.free(); mem.free(d_tris)
@@ -346,7 +348,7 @@ def test_random_scenes_and_parameters(mem, seed):
         want, _ = G.traverse(tris, rays, nthreads=4)
         brute = O.brute_force(tris, rays[:4000], nthreads=8)
         assert (want["id"][:4000] == brute["id"]).all() and (want["t"][:4000].view(np.uint32) == brute["t"].view(np.uint32)).all()
-        d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+        d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
         for compressed in (False, True):
             if compressed:
                 ok = api.compress_grid(mem, grid)
@@ -355,8 +357,9 @@ def test_random_scenes_and_parameters(mem, seed):
                     break
                 assert_same_grid(grid.download(), G, "compress")
             api.setup_traversal(grid)
+            poison(mem, d_hits, 16 * rays.shape[0])
             api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-            got = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+            got = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
             assert (got["id"] == want["id"]).all() and (got["t"].view(np.uint32) == want["t"].view(np.uint32)).all(), (seed, compressed)
         mem.free(d_rays); mem.free(d_hits); grid.free(); mem.free(d_tris)
     finally:
@@ -370,7 +373,8 @@ def test_debug_sync_build_runs_the_whole_path(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = r'''
 import os, sys, shutil, importlib
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _poison as P
 import hagrid_amd.build as B
 B.OBJ = os.path.join(OUT, "obj"); B.LIB = os.path.join(OUT, "libhagrid_amd_debug.so")
 B.FLAGS.append("-DHAGRID_DEBUG_SYNC")
@@ -384,10 +388,11 @@ mem = api.MemManager(keep=True)
 tris = scene.make_soup(30000); d_tris = mem.upload(tris)
 grid = api.build_all(mem, d_tris, 30000, compress=True)
 rays = scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, 70000, 3)
-d_rays = mem.upload(rays); d_hits = mem.alloc(16 * 70000)
+d_rays = mem.upload(rays); d_hits = P.alloc_out(mem, 16 * 70000)
 api.setup_traversal(grid); mem.set_ray_binning(1)
 api.traverse_grid(grid, d_tris, d_rays, d_hits, 70000)
-h = mem.download(d_hits, api.HIT_DTYPE, 70000)
+h = P.fetch(mem, d_hits, api.HIT_DTYPE, 70000)
+P.assert_all_written(h)
 print("SUMMARY", grid.num_cells, grid.num_refs, int((h["id"] >= 0).sum()), int(h["id"].astype(np.int64).sum()))
 '''.replace("ROOT", repr(root)).replace("OUT", repr(str(tmp_path)))
     import _subproc
@@ -401,9 +406,10 @@ print("SUMMARY", grid.num_cells, grid.num_refs, int((h["id"] >= 0).sum()), int(h
     tris = scene.make_soup(30000); d_tris = mem.upload(tris)
     grid = api.build_all(mem, d_tris, 30000, compress=True)
     rays = scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, 70000, 3)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * 70000)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * 70000)
     api.setup_traversal(grid); mem.set_ray_binning(1)
     api.traverse_grid(grid, d_tris, d_rays, d_hits, 70000)
-    h = mem.download(d_hits, api.HIT_DTYPE, 70000)
+    h = fetch(mem, d_hits, api.HIT_DTYPE, 70000)
+    assert_all_written(h)
     assert got == [str(grid.num_cells), str(grid.num_refs), str(int((h["id"] >= 0).sum())), str(int(h["id"].astype(np.int64).sum()))]
     mem.close()

@@ -8,6 +8,8 @@ import pytest
 
 from hagrid_amd import scene
 
+from _poison import alloc_out, assert_all_written, fetch, poison
+
 pytestmark = pytest.mark.gpu
 
 
@@ -15,15 +17,17 @@ def run_once(mem, tris, rays, rounds, out, key, barrier=None):
     from hagrid_amd import api
     try:
         d_tris = mem.upload(tris)
-        d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+        d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
         res = []
         for r in range(rounds):
             if barrier is not None:
                 barrier.wait()
             grid = api.build_all(mem, d_tris, tris.shape[0], compress=bool(r & 1))
             api.setup_traversal(grid)
+            poison(mem, d_hits, 16 * rays.shape[0])
             api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-            hits = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+            hits = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
+            assert_all_written(hits)
             d = grid.download()
             res.append((grid.summary(), int(d["entries"].astype(np.int64).sum()), int(d["ref_ids"].astype(np.int64).sum()), hits.copy()))
             grid.free()
@@ -81,19 +85,20 @@ def test_set_stream_drains_the_old_stream():
     grid = api.build_all(mem, d_tris, tris.shape[0])
     rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 1024, 1024)
     n = rays.shape[0]
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-    want = mem.download(d_hits, api.HIT_DTYPE, n)
-    mem.zero(d_hits, 16 * n)
+    want = fetch(mem, d_hits, api.HIT_DTYPE, n)
+    assert_all_written(want)
     a, b = torch.cuda.Stream(), torch.cuda.Stream()
     mem.use_stream(a.cuda_stream)
     mem.set_ray_binning(1)                       # allocates and frees pool buffers around the launch
-    for _ in range(5):
+    for launch in range(5):
+        if launch == 4: poison(mem, d_hits, 16 * n)          # (on stream a, in front of the launch whose hits are read)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
     mem.use_stream(b.cuda_stream)                # drains stream a
     scratch = mem.alloc(64 << 20); mem.one(scratch, 64 << 20); mem.free(scratch)
-    got = mem.download(d_hits, api.HIT_DTYPE, n)
+    got = fetch(mem, d_hits, api.HIT_DTYPE, n)
     assert (got["id"] == want["id"]).all() and (got["t"].view(np.uint32) == want["t"].view(np.uint32)).all()
     mem.use_stream(None)
     mem.close()
@@ -118,23 +123,26 @@ def test_shared_traversal_image_two_batches_in_flight():
     api.setup_traversal(grid)
     # quiet results, context a alone
     want = []
-    d_rays_a = a.upload(rays[0]); d_hits_a = a.alloc(16 * n)
+    d_rays_a = a.upload(rays[0]); d_hits_a = alloc_out(a, 16 * n)
     for r in rays:
         a.copy_h2d(d_rays_a, r)
+        poison(a, d_hits_a, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays_a, d_hits_a, n)
-        want.append(a.download(d_hits_a, api.HIT_DTYPE, n).copy())
+        want.append(fetch(a, d_hits_a, api.HIT_DTYPE, n).copy())
+        assert_all_written(want[-1])
     a.copy_h2d(d_rays_a, rays[0])
     image_bytes = a.image_bytes(grid)
     used_b = b.usage()
     gb = api.share_traversal(b, grid)
     assert b.usage() == used_b and b.image_bytes(gb) == image_bytes            # no copy of the image in b's pool
-    d_rays_b = b.upload(rays[1]); d_hits_b = b.alloc(16 * n)
+    d_rays_b = b.upload(rays[1]); d_hits_b = alloc_out(b, 16 * n)
     sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
     a.use_stream(sa.cuda_stream); b.use_stream(sb.cuda_stream)
-    for _ in range(50):
+    for launch in range(50):
+        if launch == 49: poison(a, d_hits_a, 16 * n); poison(b, d_hits_b, 16 * n)      # (each on its own stream, in front of the launches whose hits are read)
         api.traverse_grid(grid, d_tris, d_rays_a, d_hits_a, n)
         api.traverse_grid(gb, d_tris, d_rays_b, d_hits_b, n)
-    got_a = a.download(d_hits_a, api.HIT_DTYPE, n); got_b = b.download(d_hits_b, api.HIT_DTYPE, n)
+    got_a = fetch(a, d_hits_a, api.HIT_DTYPE, n); got_b = fetch(b, d_hits_b, api.HIT_DTYPE, n)
     for got, w in ((got_a, want[0]), (got_b, want[1])):
         assert (got["id"] == w["id"]).all() and (got["t"].view(np.uint32) == w["t"].view(np.uint32)).all()
     with pytest.raises(api.HagridError):
@@ -142,15 +150,15 @@ def test_shared_traversal_image_two_batches_in_flight():
     # the borrower builds an image of its own: the share ends, the owner's image is untouched
     api.setup_traversal(gb)
     assert b.usage() >= used_b + image_bytes
-    b.zero(d_hits_b, 16 * n)
+    poison(b, d_hits_b, 16 * n)
     api.traverse_grid(gb, d_tris, d_rays_b, d_hits_b, n)
-    got_b = b.download(d_hits_b, api.HIT_DTYPE, n)
-    assert (got_b["id"] == want[1]["id"]).all()
+    got_b = fetch(b, d_hits_b, api.HIT_DTYPE, n)
+    assert (got_b["id"] == want[1]["id"]).all() and (got_b["t"].view(np.uint32) == want[1]["t"].view(np.uint32)).all()
     b.use_stream(None); b.close()
-    a.zero(d_hits_a, 16 * n)
+    poison(a, d_hits_a, 16 * n)
     api.traverse_grid(grid, d_tris, d_rays_a, d_hits_a, n)          # the owner still has its image after the borrower is gone
-    got_a = a.download(d_hits_a, api.HIT_DTYPE, n)
-    assert (got_a["id"] == want[0]["id"]).all() and a.image_bytes(grid) == image_bytes
+    got_a = fetch(a, d_hits_a, api.HIT_DTYPE, n)
+    assert (got_a["id"] == want[0]["id"]).all() and (got_a["t"].view(np.uint32) == want[0]["t"].view(np.uint32)).all() and a.image_bytes(grid) == image_bytes
     a.use_stream(None); a.close()
 
 
@@ -172,16 +180,17 @@ def test_borrowed_traversal_image_is_refused_once_its_owner_drops_it():
     grid = api.build_all(a, d_tris, tris.shape[0])
     rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 256, 256)
     n = rays.shape[0]
-    d_rays_a = a.upload(rays); d_hits_a = a.alloc(16 * n)
-    d_rays_b = b.upload(rays); d_hits_b = b.alloc(16 * n)
+    d_rays_a = a.upload(rays); d_hits_a = alloc_out(a, 16 * n)
+    d_rays_b = b.upload(rays); d_hits_b = alloc_out(b, 16 * n)
     api.setup_traversal(grid)
     api.traverse_grid(grid, d_tris, d_rays_a, d_hits_a, n)
-    want = a.download(d_hits_a, api.HIT_DTYPE, n).copy()
+    want = fetch(a, d_hits_a, api.HIT_DTYPE, n).copy()
+    assert_all_written(want)
 
     def borrower_ok(gb):
-        b.zero(d_hits_b, 16 * n)
+        poison(b, d_hits_b, 16 * n)
         api.traverse_grid(gb, d_tris, d_rays_b, d_hits_b, n)
-        got = b.download(d_hits_b, api.HIT_DTYPE, n)
+        got = fetch(b, d_hits_b, api.HIT_DTYPE, n)
         return (got["id"] == want["id"]).all() and (got["t"].view(np.uint32) == want["t"].view(np.uint32)).all()
 
     gb = api.share_traversal(b, grid)
@@ -199,8 +208,10 @@ def test_borrowed_traversal_image_is_refused_once_its_owner_drops_it():
     with pytest.raises(api.HagridError):
         api.share_traversal(b, grid)                               # the owner has no image now
     api.setup_traversal(grid)
+    poison(a, d_hits_a, 16 * n)
     api.traverse_grid(grid, d_tris, d_rays_a, d_hits_a, n)
-    want = a.download(d_hits_a, api.HIT_DTYPE, n).copy()           # (same hits: expansion never changes them)
+    want = fetch(a, d_hits_a, api.HIT_DTYPE, n).copy()             # (same hits: expansion never changes them)
+    assert_all_written(want)
     gb = api.share_traversal(b, grid)
     assert borrower_ok(gb)
     # 3. the borrower's own setup ends the share and is not affected by the owner any more
@@ -236,9 +247,10 @@ def test_large_scans_of_two_contexts_while_traversal_keeps_the_cus_busy():
     tg = api.build_all(tm, d_small, small.shape[0])
     api.setup_traversal(tg)
     rays = scene.make_rays_primary(tg.bbox_min, tg.bbox_max, 2048, 2048)
-    d_rays = tm.upload(rays); d_hits = tm.alloc(16 * rays.shape[0])
+    d_rays = tm.upload(rays); d_hits = alloc_out(tm, 16 * rays.shape[0])
     api.traverse_grid(tg, d_small, d_rays, d_hits, rays.shape[0])
-    want = tm.download(d_hits, api.HIT_DTYPE, rays.shape[0]).copy()
+    want = fetch(tm, d_hits, api.HIT_DTYPE, rays.shape[0]).copy()
+    assert_all_written(want)
     streams = [torch.cuda.Stream() for _ in range(3)]
     tm.use_stream(streams[2].cuda_stream)
     stop = threading.Event()
@@ -247,7 +259,8 @@ def test_large_scans_of_two_contexts_while_traversal_keeps_the_cus_busy():
     def traffic():
         try:
             while not stop.is_set():
-                for _ in range(8):
+                for k in range(8):
+                    if k == 7: poison(tm, d_hits, 16 * rays.shape[0])          # (the last launch before the thread stops is the one whose hits are read)
                     api.traverse_grid(tg, d_small, d_rays, d_hits, rays.shape[0])
                 tm.synchronize()
             out["t"] = True
@@ -282,6 +295,6 @@ def test_large_scans_of_two_contexts_while_traversal_keeps_the_cus_busy():
         assert not isinstance(out[i], Exception), out[i]
         for r in out[i]:
             assert r == quiet[i]
-    got = tm.download(d_hits, api.HIT_DTYPE, rays.shape[0])
-    assert (got["id"] == want["id"]).all()
+    got = fetch(tm, d_hits, api.HIT_DTYPE, rays.shape[0])
+    assert (got["id"] == want["id"]).all() and (got["t"].view(np.uint32) == want["t"].view(np.uint32)).all()
     tm.use_stream(None); tm.close()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _subproc
+from _poison import alloc_out, assert_all_written, fetch, poison
 
 from hagrid_amd import scene
 
@@ -91,9 +92,9 @@ def _worker(rank, port, q):
         n_rays = 100001
         rays = scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, n_rays, 11)
         b, e = scene.shard_range(n_rays, rank, 2)
-        d_rays = mem.upload(rays[b:e]); d_hits = mem.alloc(16 * (e - b))
+        d_rays = mem.upload(rays[b:e]); d_hits = alloc_out(mem, 16 * (e - b))
         api.traverse_grid(grid, d_tris, d_rays, d_hits, e - b)
-        hits = mem.download(d_hits, api.HIT_DTYPE, e - b)
+        hits = fetch(mem, d_hits, api.HIT_DTYPE, e - b)
         d = grid.download()
         q.put((rank, b, e, hits["id"].copy(), hits["t"].copy(), grid.summary(), int(d["entries"].sum(dtype=np.int64)), int(d["ref_ids"].sum(dtype=np.int64))))
         dist.barrier()
@@ -119,9 +120,10 @@ def test_broadcast_grid_and_sharded_traversal():
     tris = scene.make_soup(30000); d_tris = mem.upload(tris)
     grid = api.build_all(mem, d_tris, 30000, compress=True)
     rays = scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, 100001, 11)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * 100001)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * 100001)
     api.traverse_grid(grid, d_tris, d_rays, d_hits, 100001)
-    want = mem.download(d_hits, api.HIT_DTYPE, 100001)
+    want = fetch(mem, d_hits, api.HIT_DTYPE, 100001)
+    assert_all_written(want)
     for rank, b, e, hid, ht, *_ in res:
         assert (hid == want["id"][b:e]).all() and (ht.view(np.uint32) == want["t"][b:e].view(np.uint32)).all()
     mem.close()
@@ -139,14 +141,16 @@ def test_grid_blob_pack_unpack_save_load(compress, tmp_path):
     d_tris = mem.upload(tris)
     grid = api.build_all(mem, d_tris, n_tris, compress=compress)
     rays = scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, 100_000, 3)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
 
     def hits_of(m, g, t, dr, dh):
         api.setup_traversal(g)
+        poison(m, dh, 16 * rays.shape[0])
         api.traverse_grid(g, t, dr, dh, rays.shape[0])
-        return m.download(dh, api.HIT_DTYPE, rays.shape[0])
+        return fetch(m, dh, api.HIT_DTYPE, rays.shape[0])
 
     want = hits_of(mem, grid, d_tris, d_rays, d_hits)
+    assert_all_written(want)
     # pack == the host packer on the downloaded arrays
     p = C.c_void_p(); nb = C.c_size_t()
     api._check(mem, mem._L.hagrid_grid_pack(mem._ctx, C.byref(grid.pod), C.c_void_p(d_tris), n_tris, C.byref(p), C.byref(nb)), "pack")
@@ -183,7 +187,7 @@ def test_grid_blob_pack_unpack_save_load(compress, tmp_path):
     mem2 = api.MemManager(keep=True)
     g3, t3, n3 = hdist.load_grid(mem2, path)
     assert n3 == n_tris and g3.summary() == grid.summary()
-    dr = mem2.upload(rays); dh = mem2.alloc(16 * rays.shape[0])
+    dr = mem2.upload(rays); dh = alloc_out(mem2, 16 * rays.shape[0])
     got = hits_of(mem2, g3, t3, dr, dh)
     assert (got["id"] == want["id"]).all() and (got["t"].view(np.uint32) == want["t"].view(np.uint32)).all()
     open(path, "wb").write(host.tobytes()[:-4096])

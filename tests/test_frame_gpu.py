@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import _subproc
+from _poison import alloc_out, assert_all_written, fetch
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
@@ -60,10 +61,10 @@ def render(c, w, h, mode=0, ao=0, radius=0.0, seed=0, ws=None, **kw):
     own = ws is None
     if own:
         ws = mem.alloc(api.frame_workspace_bytes(w, h, ao))
-    d_px = mem.alloc(4 * n)
-    mem.one(d_px, 4 * n)
+    mem.one(ws, api.frame_workspace_bytes(w, h, ao))          # (rays and hits of the workspace are compared: not the previous frame's)
+    d_px = alloc_out(mem, 4 * n)
     api.render_frame(c.grid, c.d_tris, cam, cam[4], w, h, ws, d_px, mode=mode, ao_samples=ao, ao_radius=radius, seed=seed)
-    px = mem.download(d_px, np.uint8, 4 * n).reshape(n, 4)
+    px = fetch(mem, d_px, np.uint8, 4 * n).reshape(n, 4)
     lay = api.frame_workspace_layout(w, h, ao)
     rays = mem.download(ws + lay["rays"], np.float32, 8 * n).reshape(n, 8)
     hits = mem.download(ws + lay["hits"], api.HIT_DTYPE, n)
@@ -96,9 +97,9 @@ def test_gen_bounce_rays_bit_identical(case, w, h, seed, first, redraw):
     n = rays.shape[0]
     tmax = 0.125 if not redraw else float(scene.FLT_MAX)
     want = scene.make_rays_bounce(c.tris, rays, hits, c.lo, c.hi, seed, first=first, tmax=tmax, redraw_misses=redraw)
-    d_rays = mem.upload(rays); d_hits = mem.upload(hits); d_out = mem.alloc(32 * n)
+    d_rays = mem.upload(rays); d_hits = mem.upload(hits); d_out = alloc_out(mem, 32 * n)
     api.gen_bounce_rays(mem, c.d_tris, d_rays, d_hits, n, seed, c.lo, c.hi, d_out, first=first, tmax=tmax, redraw_misses=redraw)
-    got = mem.download(d_out, np.float32, 8 * n).reshape(n, 8)
+    got = fetch(mem, d_out, np.float32, 8 * n).reshape(n, 8)
     for p in (d_rays, d_hits, d_out):
         mem.free(p)
     diff = (bits(got) != bits(want)).any(axis=1)
@@ -130,7 +131,7 @@ def test_shade_hits_byte_identical(case, mode, n):
 def test_occlusion_accumulate_and_shade(case, n, samples):
     c = case; api, mem = c.api, c.mem
     prim = _synthetic_hits(n)
-    d_prim = mem.upload(prim); d_counts = mem.alloc(4 * n + 4); mem.zero(d_counts, 4 * n + 4); d_px = mem.alloc(4 * n)
+    d_prim = mem.upload(prim); d_counts = mem.alloc(4 * n + 4); mem.zero(d_counts, 4 * n + 4); d_px = alloc_out(mem, 4 * n)
     counts = np.zeros(n, np.int32)
     for s in range(samples):
         occ = np.zeros(n, dtype=scene.HIT_DTYPE)
@@ -142,7 +143,7 @@ def test_occlusion_accumulate_and_shade(case, n, samples):
     got_counts = mem.download(d_counts, np.int32, n + 1)
     assert (got_counts[:n] == counts).all() and got_counts[n] == 0
     api.shade_occlusion(mem, d_prim, d_counts, n, samples, d_px)
-    got = mem.download(d_px, np.uint8, 4 * n).reshape(n, 4)
+    got = fetch(mem, d_px, np.uint8, 4 * n).reshape(n, 4)
     for p in (d_prim, d_counts, d_px):
         mem.free(p)
     assert (got == scene.shade_occlusion(prim, counts, samples)).all()
@@ -192,9 +193,10 @@ def test_heat_map_of_step_counts_is_the_reference_viewers_picture(case):
             render(c, w, h, ao=2, radius=0.1)
     finally:
         mem.set_option("traverse.id_is_steps", 0)
-    d_steps = mem.alloc(4 * n); d_hits = mem.alloc(16 * n)
+    d_steps = alloc_out(mem, 4 * n); d_hits = alloc_out(mem, 16 * n)
     api.traverse_grid_stats(c.grid, c.d_tris, ws, d_hits, n, d_steps)
-    steps = mem.download(d_steps, np.int32, n)
+    steps = fetch(mem, d_steps, np.int32, n)
+    assert_all_written(fetch(mem, d_hits, c.api.HIT_DTYPE, n))
     for p in (d_steps, d_hits, ws):
         mem.free(p)
     assert (hits["id"] == steps).all()

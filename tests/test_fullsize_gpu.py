@@ -7,6 +7,8 @@ import pytest
 
 from hagrid_amd import scene
 
+from _poison import alloc_out, assert_all_written, fetch, poison
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,11 +25,12 @@ def world():
 def traverse(mem, grid, d_tris, rays):
     from hagrid_amd import api
     n = rays.shape[0]
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)          # (ones and a guard: a ray the launch skips reads id -1, t NaN -- _poison.py)
     api.setup_traversal(grid)
     api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-    hits = mem.download(d_hits, api.HIT_DTYPE, n)
+    hits = fetch(mem, d_hits, api.HIT_DTYPE, n)
     mem.free(d_rays); mem.free(d_hits)
+    assert_all_written(hits)
     return hits
 
 
@@ -85,27 +88,28 @@ def test_config2_loop_over_one_buffer_learned_tile_order_matches_oracle(world):
     rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, w, h)
     n = rays.shape[0]
     oh, _ = G.traverse(tris, rays, nthreads=8)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     fmt = mem.image_format(grid)
     assert fmt.get("slim_id_bits"), fmt                              # the tail kernel with its tile order is what runs here
     checked = []
     for launch in range(1, 41):
-        mem.zero(d_hits, 16 * n)
+        compared = launch in (1, 2, 3, 33, 40)
+        if compared: poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        if launch in (1, 2, 3, 33, 40):
+        if compared:
             mem.synchronize()                                        # (the host sees the row length: the order is learned from the next launch on)
-            assert same_hits(mem.download(d_hits, api.HIT_DTYPE, n), oh), f"launch {launch}"
+            assert same_hits(fetch(mem, d_hits, api.HIT_DTYPE, n), oh), f"launch {launch}"
             checked.append(launch)
     assert checked == [1, 2, 3, 33, 40]
     flipped = np.ascontiguousarray(rays.reshape(h, w, 8)[::-1].reshape(n, 8))
     oh2 = np.ascontiguousarray(oh.reshape(h, w)[::-1].reshape(n))
     mem.copy_h2d(d_rays, flipped)
     for launch in range(1, 6):
-        mem.zero(d_hits, 16 * n)
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
         mem.synchronize()
-        assert same_hits(mem.download(d_hits, api.HIT_DTYPE, n), oh2), f"refilled buffer, launch {launch}"
+        assert same_hits(fetch(mem, d_hits, api.HIT_DTYPE, n), oh2), f"refilled buffer, launch {launch}"
     mem.free(d_rays); mem.free(d_hits); grid.free()
 
 
@@ -126,7 +130,7 @@ def test_config3_dense_grid_16M_primary_rays(world):
     w = h = 4096
     rays = scene.generate_parallel(lambda f, c: scene.make_rays_primary(grid.bbox_min, grid.bbox_max, w, h, first=f, count=c), 0, w * h, chunk=1 << 21)
     n = rays.shape[0]
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     got = {}
     # the uniform layout with the table layout next to it (this grid's default since round 6: rays in image order gather from the uniform one), the table layout alone,
     # the general layout forced, the construction format
@@ -135,8 +139,10 @@ def test_config3_dense_grid_16M_primary_rays(world):
         api.setup_traversal(grid)
         f = mem.image_format(grid)
         if image: assert f["general"] == (general == 2) and f["uniform"] == (key == "default") and f["two_layouts"] == (key == "default"), (key, f)
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        got[key] = mem.download(d_hits, api.HIT_DTYPE, n)
+        got[key] = fetch(mem, d_hits, api.HIT_DTYPE, n)
+        assert_all_written(got[key])
     mem.set_option("traverse.image", 2); mem.set_option("traverse.image_general", 1); mem.set_option("traverse.image_uniform", 1)
     got[2] = got["default"]
     assert same_hits(got[2], got[1]) and same_hits(got[2], got[0]) and same_hits(got[2], got["table"])
@@ -164,13 +170,15 @@ def test_config4_share_16M_incoherent_rays_binned_and_unbinned(world):
     first, end = scene.shard_range(1 << 27, 3, 8)
     assert end - first == n
     rays = scene.generate_parallel(lambda f, c: scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, c, scene.RAY_SEED_BASE + 4, first=f), first, n)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     got = {}
     for mode in (0, 1, 2):
         mem.set_ray_binning(mode)
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        got[mode] = mem.download(d_hits, api.HIT_DTYPE, n)
+        got[mode] = fetch(mem, d_hits, api.HIT_DTYPE, n)
+        assert_all_written(got[mode])
     mem.set_ray_binning(0)
     assert same_hits(got[0], got[1]) and same_hits(got[0], got[2])
     # without the traversal image the batch takes the persistent large-batch kernel (unbinned) and v2 (binned)
@@ -178,8 +186,9 @@ def test_config4_share_16M_incoherent_rays_binned_and_unbinned(world):
     api.setup_traversal(grid)
     for mode in (0, 1):
         mem.set_ray_binning(mode)
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        assert same_hits(got[0], mem.download(d_hits, api.HIT_DTYPE, n)), f"construction format, binning {mode}"
+        assert same_hits(got[0], fetch(mem, d_hits, api.HIT_DTYPE, n)), f"construction format, binning {mode}"
     mem.set_ray_binning(0); mem.set_option("traverse.image", 2)
     hits = got[0]
     assert 0.5 < (hits["id"] >= 0).mean() <= 1.0
@@ -287,7 +296,7 @@ def test_config5_8M_triangles_compressed_bounce_rays():
         sl = slice(off, min(off + (1 << 21), n8))
         bounce[sl] = scene.make_rays_bounce(tris, prim[sl], h0[sl], comp.bbox_min, comp.bbox_max, scene.RAY_SEED_BASE + 5, first=first + off)
     del prim
-    d_rays = mem.upload(bounce); d_hits = mem.alloc(16 * n8)
+    d_rays = mem.upload(bounce); d_hits = alloc_out(mem, 16 * n8)
     api.setup_traversal(comp)
     variants = {}
     for name, opts in (("detect", dict(width=0)), ("off", dict(width=-1)), ("given", dict(width=W)), ("binned", dict(width=0, bin=1)),
@@ -295,8 +304,10 @@ def test_config5_8M_triangles_compressed_bounce_rays():
         mem.set_option("traverse.image_width", opts["width"]); mem.set_ray_binning(opts.get("bin", 0))
         if "image" in opts:
             mem.set_option("traverse.image", opts["image"]); api.setup_traversal(comp)
+        poison(mem, d_hits, 16 * n8)
         api.traverse_grid(comp, d_tris, d_rays, d_hits, n8)
-        variants[name] = mem.download(d_hits, api.HIT_DTYPE, n8)
+        variants[name] = fetch(mem, d_hits, api.HIT_DTYPE, n8)
+        assert_all_written(variants[name])
     mem.set_option("traverse.image_width", 0); mem.set_ray_binning(0); mem.set_option("traverse.image", 2)
     for name, v in variants.items():
         assert same_hits(variants["detect"], v), name
@@ -351,15 +362,16 @@ def test_clustered_scene_structure_and_hits_match_oracle():
         # checked launch gives the oracle's hits; with a lower threshold (more tiles at the head) and without the feature as well.
         prim = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 1024, 1024); n = prim.shape[0]
         ohp, _ = G.traverse(tris, prim, nthreads=8)
-        d_rays = mem.upload(prim); d_hits = mem.alloc(16 * n)
+        d_rays = mem.upload(prim); d_hits = alloc_out(mem, 16 * n)
         for head in (20, 12, 0):
             mem.set_option("traverse.quad_head", head)
             for launch in range(1, 121):
-                if launch in (1, 2, 3, 34, 35, 67, 68, 100, 120): mem.zero(d_hits, 16 * n)
+                compared = launch in (1, 2, 3, 34, 35, 67, 68, 100, 120)
+                if compared: poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-                if launch in (1, 2, 3, 34, 35, 67, 68, 100, 120):
+                if compared:
                     mem.synchronize()
-                    assert same_hits(mem.download(d_hits, api.HIT_DTYPE, n), ohp), (head, launch)
+                    assert same_hits(fetch(mem, d_hits, api.HIT_DTYPE, n), ohp), (head, launch)
         mem.set_option("traverse.quad_head", 20)
         # A camera that MOVES (the reference's viewer writes new rays every frame, main.cpp:591-601): eight frames at the viewer's speed into the same buffer, behind the
         # launches above (a learned order that goes stale, the pause from learning, the share trial of launches in the default order -- half of the tiles with four
@@ -373,7 +385,7 @@ def test_clustered_scene_structure_and_hits_match_oracle():
 
 def moving_camera_frames(mem, grid, d_tris, G, tris, d_rays, d_hits, width, height, frames=8, extra_launches=3):
     """`frames` frames of a camera that turns and strafes at the reference viewer's speed, written into ONE ray buffer; every frame is traversed a few times (the
-    policy's trials take their samples over launches) and its hits compared with the oracle's."""
+    policy's trials take their samples over launches) and its hits compared with the oracle's.  d_hits: from alloc_out (_poison.py)."""
     from hagrid_amd import api
     n = width * height
     for f in range(frames):
@@ -381,10 +393,10 @@ def moving_camera_frames(mem, grid, d_tris, G, tris, d_rays, d_hits, width, heig
         want, _ = G.traverse(tris, r, nthreads=8)
         mem.copy_h2d(d_rays, r)
         for k in range(extra_launches):
-            mem.zero(d_hits, 16 * n)
+            poison(mem, d_hits, 16 * n)
             api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
             mem.synchronize()
-            assert same_hits(mem.download(d_hits, api.HIT_DTYPE, n), want), (f, k, mem.order_state(d_rays))
+            assert same_hits(fetch(mem, d_hits, api.HIT_DTYPE, n), want), (f, k, mem.order_state(d_rays))
 
 
 def test_stadium_mesh_through_the_front_door(tmp_path):
@@ -441,13 +453,14 @@ def test_stadium_mesh_through_the_front_door(tmp_path):
         # a loop over one buffer, then a camera that moves
         prim = scene.make_rays_primary(lo, hi, 1024, 1024); n = prim.shape[0]
         wp, _ = G.traverse(tris, prim, nthreads=8)
-        d_rays = mem.upload(prim); d_hits = mem.alloc(16 * n)
+        d_rays = mem.upload(prim); d_hits = alloc_out(mem, 16 * n)
         for launch in range(1, 80):
-            if launch in (1, 2, 3, 34, 35, 79): mem.zero(d_hits, 16 * n)
+            compared = launch in (1, 2, 3, 34, 35, 79)
+            if compared: poison(mem, d_hits, 16 * n)
             api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-            if launch in (1, 2, 3, 34, 35, 79):
+            if compared:
                 mem.synchronize()
-                assert same_hits(mem.download(d_hits, api.HIT_DTYPE, n), wp), launch
+                assert same_hits(fetch(mem, d_hits, api.HIT_DTYPE, n), wp), launch
         moving_camera_frames(mem, grid, d_tris, G, tris, d_rays, d_hits, 1024, 1024)
         mem.free(d_rays); mem.free(d_hits); grid.free()
     finally:

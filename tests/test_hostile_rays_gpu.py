@@ -8,6 +8,7 @@ import pytest
 
 import _hostile_rays as H
 import _multi_hit as M
+from _poison import alloc_out, fetch
 from _traverse_formats import IMAGE_FORMATS, image_scenes
 
 pytestmark = pytest.mark.gpu
@@ -131,10 +132,10 @@ def test_reference_shaped_kernel(mem, name, grid, compress):
         mem.set_option("traverse.variant", 1)
         api.setup_traversal(dev.grid)
         w.check(dev.run(), "variant 1")
-        d_hits = mem.alloc(16 * w.n); d_steps = mem.alloc(4 * w.n)
+        d_hits = alloc_out(mem, 16 * w.n); d_steps = alloc_out(mem, 4 * w.n)
         st = api.traverse_grid_stats(dev.grid, dev.d_tris, dev.d_rays, d_hits, w.n, d_steps)
-        steps = mem.download(d_steps, np.int32, w.n)
-        w.check(mem.download(d_hits, api.HIT_DTYPE, w.n), "statistics entry point")
+        steps = fetch(mem, d_steps, np.int32, w.n)
+        w.check(fetch(mem, d_hits, api.HIT_DTYPE, w.n), "statistics entry point")
         mem.free(d_hits); mem.free(d_steps)
         assert st == w.stats, (st, w.stats)
         assert (steps == w.steps).all() and (steps[w.inadmissible] == 0).all() and steps.max() > 3

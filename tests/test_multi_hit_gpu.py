@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _multi_hit as M
+from _poison import alloc_out, assert_all_written, fetch
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
@@ -207,14 +208,16 @@ def test_no_interference_with_the_nearest_hit_path(case):
 def test_shade_layers_on_device_lists(case, k, opacity):
     c = case; api, mem = c.api, c.mem
     clip = float(c.rays[1, 7])
-    d_hits = mem.alloc(16 * c.n * k)
+    d_hits = alloc_out(mem, 16 * c.n * k)
     d_px = mem.alloc(4 * c.n + 16)
     mem.one(d_px, 4 * c.n + 16)
     api.traverse_grid_multi(c.grids[True], c.d_tris, c.d_rays, d_hits, c.n, k)
     api.shade_layers(mem, d_hits, c.n, k, clip, opacity, d_px)
     mem.synchronize()
     px = mem.download(d_px, np.uint8, 4 * c.n + 16)
-    lists = mem.download(d_hits, api.HIT_DTYPE, c.n * k).reshape(c.n, k)
+    lists = fetch(mem, d_hits, api.HIT_DTYPE, c.n * k).reshape(c.n, k)
+    assert_all_written(lists.reshape(-1))
+    assert_lists(lists, c.ids, c.t, f"{c.name} k={k} in front of the shader")
     assert (px[4 * c.n:] == 255).all(), "written beyond the pixels"
     want = scene.shade_layers(lists, k, clip, opacity)
     assert (px[:4 * c.n].reshape(c.n, 4) == want).all()

@@ -330,6 +330,7 @@ def test_errors_leave_the_context_working(case):
     assert call(grid, c.d_tris, c.d_boxes + 8, c.n - 1, 8, d_ids) == EINVAL
     assert call(grid, c.d_tris, c.d_boxes, c.n, 8, d_ids + 8) == EINVAL and call(grid, c.d_tris, c.d_boxes, c.n, 4, d_ids + 4) == EINVAL
     # 16 bytes only where 16-byte stores are used: any other k writes at any int32 boundary
+    mem.one(d_ids, 4 * 8 * c.n + 64)                      # (the k = 8 launch above left its ids here: the ones compared below are this launch's)
     assert call(grid, c.d_tris, c.d_boxes, c.n, 3, d_ids + 4) == 0 and call(grid, c.d_tris, c.d_boxes, c.n, 3, d_ids + 2) == EINVAL
     mem.synchronize()
     assert (mem.download(d_ids + 4, np.int32, 3 * c.n).reshape(c.n, 3) == V.expected(c.fixture, c.name, 3)[0]).all(), "k = 3 at an odd offset"

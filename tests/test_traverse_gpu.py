@@ -7,6 +7,7 @@ import pytest
 
 from hagrid_amd import scene
 
+from _poison import alloc_out, assert_all_written, fetch, poison
 from _traverse_formats import IMAGE_FORMATS as _IMAGE_FORMATS, image_scenes as _image_scenes
 
 pytestmark = pytest.mark.gpu
@@ -30,18 +31,19 @@ def upload_oracle_grid(mem, G):
 
 
 def gpu_traverse(mem, grid, d_tris, rays, stats=False):
+    """hits (and steps) of one launch into poisoned, guarded buffers (_poison.py): a ray the launch skips reads id -1, t NaN"""
     from hagrid_amd import api
     n = rays.shape[0]
-    d_rays = mem.upload(rays); d_hits = mem.alloc(max(16 * n, 16))
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     st = None
     if stats:
-        d_steps = mem.alloc(max(4 * n, 4))
+        d_steps = alloc_out(mem, 4 * n)
         st = api.traverse_grid_stats(grid, d_tris, d_rays, d_hits, n, d_steps)
-        steps = mem.download(d_steps, np.int32, n); mem.free(d_steps)
+        steps = fetch(mem, d_steps, np.int32, n); mem.free(d_steps)
     else:
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-    hits = mem.download(d_hits, api.HIT_DTYPE, n)
+    hits = fetch(mem, d_hits, api.HIT_DTYPE, n)
     mem.free(d_rays); mem.free(d_hits)
     return (hits, st, steps) if stats else hits
 
@@ -177,7 +179,8 @@ def test_ray_binning_gives_identical_hits(mem):
             binned = gpu_traverse(mem, grid, d_tris, rays)
             assert (plain["id"] == binned["id"]).all() and (bits(plain["t"]) == bits(binned["t"])).all()
         oh, _ = G.traverse(tris, batches[0], nthreads=8)
-        assert (binned["id"] == plain["id"]).all()
+        assert (binned["id"] == plain["id"]).all() and (bits(binned["t"]) == bits(plain["t"])).all()
+        assert_all_written(binned); assert_all_written(plain)
         mem.set_ray_binning(1)
         b0 = gpu_traverse(mem, grid, d_tris, batches[0])
         assert (b0["id"] == oh["id"]).all() and (bits(b0["t"]) == bits(oh["t"])).all()
@@ -641,18 +644,18 @@ def test_head_share_trial_never_changes_hits(mem, family):
     d_tris = mem.upload(tris); grid = upload_oracle_grid(mem, G)
     rays = scene.make_rays_primary(np.asarray(G.bbox_min), np.asarray(G.bbox_max), 1024, 640).astype(np.float32); n = rays.shape[0]
     want, _ = G.traverse(tris, rays, nthreads=8)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     try:
         for head in (20, 11):
             mem.set_option("traverse.quad_head", head)
             for launch in range(1, 141):
                 check = launch in (1, 2, 3, 30, 60, 61, 62, 90, 100, 101, 120, 140)
-                if check: mem.zero(d_hits, 16 * n)
+                if check: poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
                 if check:
                     mem.synchronize()
-                    got = mem.download(d_hits, api.HIT_DTYPE, n)
+                    got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                     assert (got["id"] == want["id"]).all() and (bits(got["t"]) == bits(want["t"])).all(), (family, head, launch)
     finally:
         mem.set_option("traverse.quad_head", 20)
@@ -679,24 +682,25 @@ def test_share_trial_and_the_order_held_against_it_never_change_hits(mem):
         for name, rays, binning in (("primary", prim, 0), ("bounce-like", bounce, 0), ("incoherent binned", inc, 1)):
             n = rays.shape[0]
             want, _ = G.traverse(tris, rays, nthreads=8)
-            d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+            d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
             mem.set_ray_binning(binning)
             for launch in range(1, 91):
-                mem.zero(d_hits, 16 * n)
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
                 mem.synchronize()
                 if launch <= 30 or launch % 6 == 0:
-                    got = mem.download(d_hits, api.HIT_DTYPE, n)
+                    got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                     assert (got["id"] == want["id"]).all() and (bits(got["t"]) == bits(want["t"])).all(), (name, launch, mem.order_state(d_rays))
             st = mem.order_state(d_rays)
             assert st["slot"] >= 0 and st["share_choice"] in (0, 25, 37, 50, 100), (name, st)          # a choice was made (a percentage of the tiles)
             if name == "primary":
                 # another buffer of the same shape starts with the answer
                 d_rays2 = mem.upload(rays)
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays2, d_hits, n); mem.synchronize()
                 st2 = mem.order_state(d_rays2)
                 assert st2["share_choice"] == st["share_choice"], (st, st2)
-                got = mem.download(d_hits, api.HIT_DTYPE, n)
+                got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                 assert (got["id"] == want["id"]).all() and (bits(got["t"]) == bits(want["t"])).all()
                 mem.free(d_rays2)
             mem.set_ray_binning(0)
@@ -746,7 +750,7 @@ def test_policy_state_machine_under_a_random_sequence_of_launches(mem):
     for i in range(6):
         shape = shapes[i % len(shapes)]; kind = ("primary", "incoherent", "bounce")[i % 3]
         n = shape[0] * shape[1]
-        bufs.append(dict(shape=shape, kind=kind, f=0, n=n, d_rays=mem.upload(np.ascontiguousarray(frame(shape, kind, 0))), d_hits=mem.alloc(16 * n)))
+        bufs.append(dict(shape=shape, kind=kind, f=0, n=n, d_rays=mem.upload(np.ascontiguousarray(frame(shape, kind, 0))), d_hits=alloc_out(mem, 16 * n)))
     try:
         for launch in range(300):
             b = bufs[int(rng.integers(len(bufs))) if launch % 5 else int(rng.integers(2))]        # (two buffers get most of the launches: their trials conclude)
@@ -756,10 +760,10 @@ def test_policy_state_machine_under_a_random_sequence_of_launches(mem):
             if launch == 150:                                        # another grid (and traversal image) of the same scene under the same buffers
                 grid.free(); grid = api.build_all(mem, d_tris, tris.shape[0], top_density=0.2, snd_density=3.0); api.setup_traversal(grid)
             mem.set_ray_binning(1 if (b["kind"] == "incoherent" and rng.random() < 0.7) else 0)
-            mem.zero(b["d_hits"], 16 * b["n"])
+            poison(mem, b["d_hits"], 16 * b["n"])
             api.traverse_grid(grid, d_tris, b["d_rays"], b["d_hits"], b["n"])
             if rng.random() < 0.5: mem.synchronize()
-            got = mem.download(b["d_hits"], api.HIT_DTYPE, b["n"])
+            got = fetch(mem, b["d_hits"], api.HIT_DTYPE, b["n"])
             w = want(b["shape"], b["kind"], b["f"])
             assert (got["id"] == w["id"]).all() and (bits(got["t"]) == bits(w["t"])).all(), (launch, b["shape"], b["kind"], b["f"], mem.order_state(b["d_rays"]))
     finally:
@@ -778,11 +782,12 @@ def test_image_lifetime(mem):
     grid = upload_oracle_grid(mem, G)
     rays = scene.make_rays_incoherent(G.bbox_min, G.bbox_max, 20000, 4)
     want, _ = G.traverse(tris, rays, nthreads=4)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * rays.shape[0])
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * rays.shape[0])
     has_image = lambda g: mem._K.hagrid_kat_image_records(mem._ctx, C.byref(g.pod), None, 0, None, None) == 0
     def check():
+        poison(mem, d_hits, 16 * rays.shape[0])
         api.traverse_grid(grid, d_tris, d_rays, d_hits, rays.shape[0])
-        got = mem.download(d_hits, api.HIT_DTYPE, rays.shape[0])
+        got = fetch(mem, d_hits, api.HIT_DTYPE, rays.shape[0])
         assert (got["id"] == want["id"]).all() and (bits(got["t"]) == bits(want["t"])).all()
     try:
         api.setup_traversal(grid); assert has_image(grid)          # built by default
@@ -906,15 +911,16 @@ def test_row_length_cache_never_changes_hits(mem):
     batches = [np.ascontiguousarray(b, np.float32) for b in batches]
     want = [G.traverse(tris, b, nthreads=8)[0] for b in batches]
     api.setup_traversal(grid)
-    d_rays = mem.upload(batches[0]); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(batches[0]); d_hits = alloc_out(mem, 16 * n)
     try:
         for cache in (1, 0):
             mem.set_option("traverse.row_cache", cache)
             for call in range(40):
                 k = (call * 7 + call // 5) % 3
                 mem.copy_h2d(d_rays, batches[k])
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-                got = mem.download(d_hits, api.HIT_DTYPE, n)
+                got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                 assert (got["id"] == want[k]["id"]).all() and (bits(got["t"]) == bits(want[k]["t"])).all(), (cache, call, k)
     finally:
         mem.set_option("traverse.row_cache", 1)
@@ -944,23 +950,25 @@ def test_tile_order_never_changes_hits(mem, params):
     mem.set_option("traverse.image_uniform", 1)
     info = mem.image_format(grid)
     assert info["slim_id_bits"] == 20 and info["uniform"] == (not params), info          # both layouts of the tail kernel
-    d_rays = mem.upload(batches[0]); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(batches[0]); d_hits = alloc_out(mem, 16 * n)
     try:
         for order, quad in ((1, -1), (-1, -1), (1, 30), (1, 100), (1, 0), (0, -1)):
             mem.set_option("traverse.tile_order", order); mem.set_option("traverse.quad_tail", quad)
             for call in range(126):
                 k = (call // 36) % 4 if call < 108 else (call * 7) % 4     # long runs over one filling (the order is learned, refreshed, reused), then a new filling per call
                 mem.copy_h2d(d_rays, batches[k])
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-                got = mem.download(d_hits, api.HIT_DTYPE, n)
+                got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                 assert (got["id"] == want[k]["id"]).all() and (bits(got["t"]) == bits(want[k]["t"])).all(), (order, quad, call, k)
         # a shorter batch in the same buffer (another tile count: the order starts over), then the long one again
         mem.set_option("traverse.tile_order", 1); mem.set_option("traverse.quad_tail", -1)
         mem.copy_h2d(d_rays, batches[0])
         for call in range(40):
             m = n if (call // 10) % 2 == 0 else 128 * 40
+            poison(mem, d_hits, 16 * m)                                   # (the guard lies right behind the m records of this launch)
             api.traverse_grid(grid, d_tris, d_rays, d_hits, m)
-            got = mem.download(d_hits, api.HIT_DTYPE, m)
+            got = fetch(mem, d_hits, api.HIT_DTYPE, m)
             assert (got["id"] == want[0]["id"][:m]).all() and (bits(got["t"]) == bits(want[0]["t"][:m])).all(), (call, m)
         # several buffers in turn (the context keeps the hints of four): five buffers over four slots, two of them traded places half way
         bufs = [mem.upload(batches[k % 4]) for k in range(5)]
@@ -968,15 +976,17 @@ def test_tile_order_never_changes_hits(mem, params):
             j = call % 5 if call < 100 else (call * 3) % 5
             if call == 75: mem.copy_h2d(bufs[1], batches[3]); mem.copy_h2d(bufs[3], batches[1])
             k = (j % 4) if call < 75 or j not in (1, 3) else (3 if j == 1 else 1)
+            poison(mem, d_hits, 16 * n)
             api.traverse_grid(grid, d_tris, bufs[j], d_hits, n)
-            got = mem.download(d_hits, api.HIT_DTYPE, n)
+            got = fetch(mem, d_hits, api.HIT_DTYPE, n)
             assert (got["id"] == want[k]["id"]).all() and (bits(got["t"]) == bits(want[k]["t"])).all(), ("buffers in turn", call, j, k)
         for b in bufs: mem.free(b)
         # the row length given by the caller instead of looked for ("traverse.image_width"): the order applies from the second call on
         mem.set_option("traverse.image_width", 128); mem.copy_h2d(d_rays, batches[0])
         for call in range(40):
+            poison(mem, d_hits, 16 * n)
             api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-            got = mem.download(d_hits, api.HIT_DTYPE, n)
+            got = fetch(mem, d_hits, api.HIT_DTYPE, n)
             assert (got["id"] == want[0]["id"]).all() and (bits(got["t"]) == bits(want[0]["t"])).all(), ("given width", call)
     finally:
         mem.set_option("traverse.image_width", 0)
@@ -1011,10 +1021,11 @@ def test_any_hit_and_uvs_traversal(mem, compressed):
     rays[1000:2000, 7] = 0.3                    # short shadow-ray-like segments
     n = rays.shape[0]
     nearest, _ = G.traverse(tris, rays, nthreads=8)
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     def run(flags):
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n, flags)
-        return mem.download(d_hits, api.HIT_DTYPE, n)
+        return fetch(mem, d_hits, api.HIT_DTYPE, n)
     api.setup_traversal(grid)                   # uncompressed: the image kernel has these variants too; compressed: v2
     for binning, variant in ((0, 0), (1, 0), (0, 2)):
         mem.set_ray_binning(binning); mem.set_option("traverse.variant", variant)
@@ -1062,7 +1073,7 @@ def test_any_hit_and_uvs_on_a_grid_with_two_layouts(mem):
     rays = np.concatenate([scene.make_rays_primary(G.bbox_min, G.bbox_max, 256, 128),
                            scene.make_rays_incoherent(G.bbox_min - 0.1, G.bbox_max + 0.1, 50001, 6)]).astype(np.float32)
     n = rays.shape[0]
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     info = mem.image_format(grid)
     assert info["uniform"] and info["two_layouts"], info
@@ -1070,19 +1081,21 @@ def test_any_hit_and_uvs_on_a_grid_with_two_layouts(mem):
     try:
         grid.mem = mem
         borrowed = api.share_traversal(other, grid)
-        o_tris = other.upload(tris); o_rays = other.upload(rays); o_hits = other.alloc(16 * n)
+        o_tris = other.upload(tris); o_rays = other.upload(rays); o_hits = alloc_out(other, 16 * n)
         for binning in (0, 1):
             mem.set_ray_binning(binning); other.set_ray_binning(binning)
             for flags, oflags in ((0, 0), (api.ANY_HIT, O.ANY_HIT), (api.UVS, O.UVS), (api.ANY_HIT | api.UVS, O.ANY_HIT | O.UVS)):
                 want = G.traverse_ex(tris, rays, oflags, nthreads=8)
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n, flags)
-                got = mem.download(d_hits, api.HIT_DTYPE, n)
+                got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                 assert (got["id"] == want["id"]).all(), (binning, flags)
                 for f in ("t", "u", "v"):
                     assert (bits(got[f]) == bits(want[f])).all(), (binning, flags, f)
                 if flags in (0, api.UVS):                       # the borrower: its own buffers, the owner's image (both layouts)
+                    poison(other, o_hits, 16 * n)
                     api.traverse_grid(borrowed, o_tris, o_rays, o_hits, n, flags); other.synchronize()
-                    got = other.download(o_hits, api.HIT_DTYPE, n)
+                    got = fetch(other, o_hits, api.HIT_DTYPE, n)
                     assert (got["id"] == want["id"]).all() and (bits(got["t"]) == bits(want["t"])).all(), ("borrowed", binning, flags)
     finally:
         mem.set_ray_binning(0)
@@ -1107,14 +1120,15 @@ def test_any_hit_and_uvs_on_a_deep_clustered_grid(mem):
     rays = np.concatenate([scene.make_rays_primary(G.bbox_min, G.bbox_max, 256, 128), aimed,
                            scene.make_rays_incoherent(G.bbox_min - 0.1, G.bbox_max + 0.1, 30001, 6)]).astype(np.float32)
     n = rays.shape[0]
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
     api.setup_traversal(grid)
     try:
         for binning in (0, 1):
             mem.set_ray_binning(binning)
             for flags, oflags in ((0, 0), (api.ANY_HIT, O.ANY_HIT), (api.UVS, O.UVS), (api.ANY_HIT | api.UVS, O.ANY_HIT | O.UVS)):
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n, flags)
-                got = mem.download(d_hits, api.HIT_DTYPE, n)
+                got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                 want = G.traverse_ex(tris, rays, oflags, nthreads=8)
                 assert (got["id"] == want["id"]).all(), (binning, flags)
                 for f in ("t", "u", "v"):
@@ -1166,18 +1180,19 @@ def test_wave_time_diagnostic_does_not_change_hits(mem):
     grid = api.build_all(mem, d_tris, tris.shape[0])
     rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 256, 128)
     n = rays.shape[0]; nw = n // 64
-    d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n); d_times = mem.alloc(16 * nw)
+    d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n); d_times = alloc_out(mem, 16 * nw)
     api.setup_traversal(grid)
     assert mem.image_format(grid) == {"flat": True, "uniform": True, "general": False, "slim_id_bits": 20, "record_bytes": 16, "two_layouts": False}
     api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-    ref = mem.download(d_hits, api.HIT_DTYPE, n)
+    ref = fetch(mem, d_hits, api.HIT_DTYPE, n)
+    assert_all_written(ref)
     d_order = mem.upload(np.arange(nw, dtype=np.int32)[::-1].copy())
     for tail in (1, 0):
         for order in (None, d_order):
-            mem.zero(d_times, 16 * nw); mem.zero(d_hits, 16 * n)
+            poison(mem, d_times, 16 * nw); mem.zero(d_times, 16 * nw); poison(mem, d_hits, 16 * n)      # (the stamps: zeroes, as the hook asks, in front of a guard of ones)
             api._check(mem, mem._K.hagrid_kat_traverse_timed(mem._ctx, C.byref(grid.pod), d_tris, d_rays, d_hits, n, 256, tail, d_times, order), "kat_traverse_timed")
-            got = mem.download(d_hits, api.HIT_DTYPE, n)
-            t = mem.download(d_times, np.uint64, 2 * nw).reshape(nw, 2)
+            got = fetch(mem, d_hits, api.HIT_DTYPE, n)
+            t = fetch(mem, d_times, np.uint64, 2 * nw).reshape(nw, 2)
             assert (got["id"] == ref["id"]).all() and (bits(got["t"]) == bits(ref["t"])).all()
             assert (t[:, 0] > 0).all() and (t[:, 1] >= t[:, 0]).all()
     mem.free(d_order); mem.free(d_times); mem.free(d_rays); mem.free(d_hits); grid.free(); mem.free(d_tris)
@@ -1198,7 +1213,7 @@ def test_release_for_traversal_keeps_hits_and_frees_the_construction_format():
         rays = np.concatenate([scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 256, 256),
                                scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, 150_000, 21)]).astype(np.float32)
         n = rays.shape[0]
-        d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+        d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
         mem.set_option("traverse.image_uniform", 0 if layout == "table" else 1)       # (a soup this small gets the uniform layout at either density: the table layout is asked for)
         api.setup_traversal(grid)
         mem.set_option("traverse.image_uniform", 1)
@@ -1206,8 +1221,10 @@ def test_release_for_traversal_keeps_hits_and_frees_the_construction_format():
         assert (fmt["uniform"], fmt["general"]) == (layout == "uniform", layout == "general"), (layout, fmt)
         want = {}
         for flags in (0, api.ANY_HIT, api.UVS):
+            poison(mem, d_hits, 16 * n)
             api.traverse_grid(grid, d_tris, d_rays, d_hits, n, flags)
-            want[flags] = mem.download(d_hits, api.HIT_DTYPE, n)
+            want[flags] = fetch(mem, d_hits, api.HIT_DTYPE, n)
+            assert_all_written(want[flags])
         before = mem.usage()
         held = 4 * grid.num_entries + (16 if compress else 32) * grid.num_cells
         api.release_for_traversal(grid)
@@ -1216,9 +1233,9 @@ def test_release_for_traversal_keeps_hits_and_frees_the_construction_format():
         for binning in (0, 1):
             mem.set_ray_binning(binning)
             for flags in (0, api.ANY_HIT, api.UVS):
-                mem.zero(d_hits, 16 * n)
+                poison(mem, d_hits, 16 * n)
                 api.traverse_grid(grid, d_tris, d_rays, d_hits, n, flags)
-                got = mem.download(d_hits, api.HIT_DTYPE, n)
+                got = fetch(mem, d_hits, api.HIT_DTYPE, n)
                 assert got.tobytes() == want[flags].tobytes(), (layout, compress, binning, flags)
         mem.set_ray_binning(0)
         api.setup_traversal(grid)                                   # nothing to rebuild, nothing lost
@@ -1233,8 +1250,9 @@ def test_release_for_traversal_keeps_hits_and_frees_the_construction_format():
         with pytest.raises(api.HagridError):
             api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
         mem.set_option("traverse.variant", 0)
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        assert mem.download(d_hits, api.HIT_DTYPE, n).tobytes() == want[0].tobytes()
+        assert fetch(mem, d_hits, api.HIT_DTYPE, n).tobytes() == want[0].tobytes()
         mem.free(d_rays); mem.free(d_hits); grid.free(); mem.free(d_tris)
     # without an image there is nothing that could stand for the construction format
     mem.set_option("traverse.image", 0)
@@ -1260,13 +1278,15 @@ def test_hit_id_can_carry_the_reference_kernels_step_count():
         G = O.Grid.full(tris, compress=compress)
         rays = np.concatenate([scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 128, 128), scene.make_rays_incoherent(grid.bbox_min, grid.bbox_max, 30_000, 9)]).astype(np.float32)
         n = rays.shape[0]
-        d_rays = mem.upload(rays); d_hits = mem.alloc(16 * n)
+        d_rays = mem.upload(rays); d_hits = alloc_out(mem, 16 * n)
         api.setup_traversal(grid)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        plain = mem.download(d_hits, api.HIT_DTYPE, n)
+        plain = fetch(mem, d_hits, api.HIT_DTYPE, n)
         mem.set_option("traverse.id_is_steps", 1)
+        poison(mem, d_hits, 16 * n)
         api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
-        stepped = mem.download(d_hits, api.HIT_DTYPE, n)
+        stepped = fetch(mem, d_hits, api.HIT_DTYPE, n)
+        assert_all_written(plain); assert_all_written(stepped)
         mem.set_option("traverse.id_is_steps", 0)
         oh, _, osteps = G.traverse(tris, rays, want_steps=True)
         assert (stepped["id"] == osteps).all() and (stepped["t"].view(np.uint32) == plain["t"].view(np.uint32)).all()
