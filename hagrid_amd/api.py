@@ -387,6 +387,53 @@ def voxelize(grid: Grid, tris: int, origin, size, n, k: int, ids: int, counts: i
                                               C.c_void_p(counters or 0), int(flags)), "voxelize")
 
 
+INSIDE_WINDING = 1       # HAGRID_INSIDE_WINDING
+
+
+def _dirs(dirs):
+    """(pointer or None, num_dirs) of the host directions of points_inside / inside_lattice: None = the three defaults (scene.CROSSING_DIRS)"""
+    if dirs is None:
+        return None, 0
+    import numpy as np
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    return (C.c_float * d.size)(*[float(v) for v in d.reshape(-1)]), d.shape[0]
+
+
+def count_crossings(grid: Grid, tris: int, rays: int, records: int, num_rays: int, counters: int = 0, flags: int = 0):
+    """Extension (hagrid_count_crossings): for each of num_rays rays ALL the triangles it crosses (the intersections of traverse_grid_multi, without the
+    bound k), condensed into one Hit-shaped record (HIT_DTYPE): id = count, t = the first t (the bits of tmax when there is none), u = length = the sum of
+    t[2p+1] - t[2p] over the pairs in (t, id) order, v = the int32 bits of winding = #leaving - #entering.  counters: 0, or a device int64[4] the batch
+    totals are added to (rays, cells visited, triangle tests, pages flushed).  All arguments are device addresses (a torch tensor passes as
+    t.data_ptr()); asynchronous on the manager's stream.  scene.ray_crossings states the records in numpy, bit for bit.  Walks the construction format: not
+    for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_count_crossings(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(rays or 0), C.c_void_p(records or 0), int(num_rays),
+                                              C.c_void_p(counters or 0), int(flags)), "count_crossings")
+
+
+def points_inside(grid: Grid, tris: int, points: int, n: int, inside: int, dirs=None, records: int = 0, counters: int = 0, flags: int = 0):
+    """Extension (hagrid_points_inside): for each of n points (16 bytes: x, y, z, reach -- POINT_QUERY_DTYPE) whether it lies inside the closed surface the
+    triangles form: a ray per direction (dirs: None = the three of scene.CROSSING_DIRS, or 1 or 3 host directions) from the point to `reach` (+inf: no
+    bound), the vote of a ray is count & 1 (flags INSIDE_WINDING: winding != 0), inside[i] (int32) = 1 when most rays vote inside, else 0; -1 for an
+    inactive point (reach < 0 or NaN, a NaN or infinite coordinate).  records: 0, or n * m Hit-shaped records (direction fastest) for the per-ray records
+    of count_crossings.  scene.points_inside states the results in numpy."""
+    mem = grid.mem or _current
+    d, m = _dirs(dirs)
+    _check(mem, mem._L.hagrid_points_inside(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(points or 0), int(n), d, int(m), C.c_void_p(inside or 0),
+                                            C.c_void_p(records or 0), C.c_void_p(counters or 0), int(flags)), "points_inside")
+
+
+def inside_lattice(grid: Grid, tris: int, origin, size, n, inside: int, dirs=None, records: int = 0, counters: int = 0, flags: int = 0):
+    """Extension (hagrid_inside_lattice): points_inside over the voxel centres of an n[0] x n[1] x n[2] lattice, x fastest, made on the device: the centre of
+    voxel c of an axis is origin + (float(c) + 0.5) * size (scene.lattice_centres gives the same points), reach +inf.  origin, size: 3 floats, n: 3 ints
+    (host values); inside: n[0] * n[1] * n[2] int32 on the device.  Together with voxelize (the voxels the surface meets) this is the solid voxelization."""
+    mem = grid.mem or _current
+    o = (C.c_float * 3)(*[float(v) for v in origin]); s = (C.c_float * 3)(*[float(v) for v in size]); k = (C.c_int * 3)(*[int(v) for v in n])
+    d, m = _dirs(dirs)
+    _check(mem, mem._L.hagrid_inside_lattice(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), o, s, k, d, int(m), C.c_void_p(inside or 0), C.c_void_p(records or 0),
+                                             C.c_void_p(counters or 0), int(flags)), "inside_lattice")
+
+
 def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, steps: int = 0) -> dict:
     mem = grid.mem or _current
     st = TraversalStats()
@@ -584,4 +631,5 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
-           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY"]
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
+           "count_crossings", "points_inside", "inside_lattice", "INSIDE_WINDING"]

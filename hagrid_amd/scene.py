@@ -139,28 +139,34 @@ def _grid_faces(nu: int, nv: int, wrap_u: bool, wrap_v: bool, base: int) -> np.n
     return np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)]).astype(np.int32)
 
 
-def make_stadium_mesh(detail: float = 1.0) -> tuple[np.ndarray, np.ndarray]:
+def make_stadium_mesh(detail: float = 1.0, solids_only: bool = False):
     """"Teapot in a stadium" (the reference README's own motivation, README.md:5-12) as an INDEXED mesh: finely tessellated connected surfaces -- tori and
     spheres with shared vertices, a grain of dust among them -- inside a hall of ten huge triangles, with terraces of long thin ones and pillars of slivers as
     high as the hall.  With detail = 1: ~0.96M triangles whose edges span four orders of magnitude (1.0 ... 1e-4).  Returns (vertices float32 [nv, 3], faces
-    int32 [nf, 3], zero-based); write_obj() / tris_from_mesh() take it from there.  `detail` scales the tessellation (tests use small ones)."""
-    V = []; F = []; nvert = 0
+    int32 [nf, 3], zero-based); write_obj() / tris_from_mesh() take it from there.  `detail` scales the tessellation (tests use small ones).
+    solids_only: only the CLOSED surfaces -- the four tori, the three spheres and the three lamps, without the hall, the terraces, the pillars and the dust
+    (make_closed_solids) -- and a third return value: each solid's analytic description, a dict with kind ("torus" | "sphere"), centre, radii (R, r of a
+    torus; (r,) of a sphere), tilt (turns about the x axis; 0 for a sphere) and faces (first face, number of faces)."""
+    V = []; F = []; nvert = 0; solids = []
 
     def add(verts, faces):
         nonlocal nvert
         V.append(np.asarray(verts, np.float64)); F.append(np.asarray(faces, np.int32)); nvert += len(verts)
 
     # the hall: floor, ceiling, two side walls, back wall of the unit cube (open towards the camera at -z): 8 shared corners, 10 triangles of edge 1
-    corners = [[x, y, z] for z in (0.0, 1.0) for y in (0.0, 1.0) for x in (0.0, 1.0)]
-    quads = [(0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5), (4, 5, 7, 6)]
-    add(corners, [[nvert + q[0], nvert + q[1], nvert + q[2]] for q in quads] + [[nvert + q[0], nvert + q[2], nvert + q[3]] for q in quads])
+    open_parts = not solids_only          # the hall, the terraces, the pillars and the dust
+    if open_parts:
+        corners = [[x, y, z] for z in (0.0, 1.0) for y in (0.0, 1.0) for x in (0.0, 1.0)]
+        quads = [(0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5), (4, 5, 7, 6)]
+        add(corners, [[nvert + q[0], nvert + q[1], nvert + q[2]] for q in quads] + [[nvert + q[0], nvert + q[2], nvert + q[3]] for q in quads])
     # terraces along the back wall: a staircase profile swept across x (treads and risers 0.9 long, 0.03 deep)
-    steps = 12
-    prof = [(0.0 + 0.03 * ((k + 1) // 2), 0.97 - 0.03 * (k // 2)) for k in range(2 * steps + 1)]          # (y, z) of the profile's corners
-    tv = [[x, y, z] for (y, z) in prof for x in (0.05, 0.95)]
-    add(tv, _grid_faces(len(prof), 2, False, False, nvert))
+    if open_parts:
+        steps = 12
+        prof = [(0.0 + 0.03 * ((k + 1) // 2), 0.97 - 0.03 * (k // 2)) for k in range(2 * steps + 1)]          # (y, z) of the profile's corners
+        tv = [[x, y, z] for (y, z) in prof for x in (0.05, 0.95)]
+        add(tv, _grid_faces(len(prof), 2, False, False, nvert))
     # pillars: coarse cylinders from floor to ceiling, 16 segments: slivers 1.0 high and 0.004 wide
-    for k in range(8):
+    for k in range(8 if open_parts else 0):
         cx, cz = (0.12 if k % 2 == 0 else 0.88), 0.15 + 0.2 * (k // 2)
         sn, cs = _sincos_turns(np.arange(16) / 16.0)
         ring = [[cx + 0.01 * c, y, cz + 0.01 * s_] for c, s_ in zip(cs, sn) for y in (0.0, 1.0)]
@@ -169,6 +175,7 @@ def make_stadium_mesh(detail: float = 1.0) -> tuple[np.ndarray, np.ndarray]:
     def torus(centre, R, r, nu, nv, tilt):
         u = np.arange(nu) / nu; v = np.arange(nv) / nv
         su, cu = _sincos_turns(u); sv, cv = _sincos_turns(v); st, ct = _sincos_turns(np.array([tilt]))
+        solids.append({"kind": "torus", "centre": tuple(centre), "radii": (R, r), "tilt": tilt, "faces": (sum(len(f) for f in F), 2 * nu * nv)})
         x = (R + r * cv[None, :]) * cu[:, None]; z = (R + r * cv[None, :]) * su[:, None]; y = np.broadcast_to(r * sv[None, :], x.shape)
         y2 = y * ct[0] - z * st[0]; z2 = y * st[0] + z * ct[0]                                   # tilted about the x axis
         add(np.stack([x + centre[0], y2 + centre[1], z2 + centre[2]], -1).reshape(-1, 3), _grid_faces(nu, nv, True, True, nvert))
@@ -176,6 +183,7 @@ def make_stadium_mesh(detail: float = 1.0) -> tuple[np.ndarray, np.ndarray]:
     def sphere(centre, r, nu, nv):
         # nu meridians x (nv - 1) rings between two pole vertices (fans at the poles: no degenerate triangles)
         u = np.arange(nu) / nu; lat = np.arange(1, nv) / (2.0 * nv)                              # turns from the north pole, (0, 1/2)
+        solids.append({"kind": "sphere", "centre": tuple(centre), "radii": (r,), "tilt": 0.0, "faces": (sum(len(f) for f in F), 2 * nu * (nv - 1))})
         su, cu = _sincos_turns(u); sl, cl = _sincos_turns(lat)
         x = r * sl[None, :] * cu[:, None]; z = r * sl[None, :] * su[:, None]; y = np.broadcast_to(r * cl[None, :], x.shape)
         base = nvert
@@ -192,10 +200,32 @@ def make_stadium_mesh(detail: float = 1.0) -> tuple[np.ndarray, np.ndarray]:
         torus(c, 0.08, 0.03, d(400), d(200), tilt)                                               # 4 x 160k triangles, edge ~1.3e-3
     for c in ((0.40, 0.06, 0.20), (0.75, 0.30, 0.65), (0.22, 0.25, 0.55)):
         sphere(c, 0.05, d(300), d(150))                                                          # 3 x 90k, edge ~1e-3
-    sphere((0.50, 0.02, 0.30), 0.004, d(200), d(100))                                            # a grain of dust: 40k triangles, edge ~1e-4
+    if open_parts:
+        sphere((0.50, 0.02, 0.30), 0.004, d(200), d(100))                                        # a grain of dust: 40k triangles, edge ~1e-4
     for c in ((0.2, 0.8, 0.5), (0.5, 0.85, 0.7), (0.8, 0.8, 0.45)):
         sphere(c, 0.1, 16, 8)                                                                    # lamps: coarse, edge ~0.04
+    if solids_only:
+        return np.concatenate(V).astype(np.float32), np.concatenate(F).astype(np.int32), solids
     return np.concatenate(V).astype(np.float32), np.concatenate(F).astype(np.int32)
+
+
+def make_closed_solids(detail: float = 1.0) -> tuple[np.ndarray, list]:
+    """(triangles, solids): the closed surfaces of make_stadium_mesh -- four tori, three spheres, three lamps -- in face order, and their analytic
+    descriptions: the scene whose inside / outside is known (solid_distance)."""
+    verts, faces, solids = make_stadium_mesh(detail, solids_only=True)
+    return tris_from_mesh(verts, faces), solids
+
+
+def solid_distance(solid: dict, points: np.ndarray) -> np.ndarray:
+    """signed distance (float64, negative inside) of points (n, 3) to the ANALYTIC surface of one solid of make_closed_solids"""
+    p = np.asarray(points, np.float64)[:, 0:3] - np.asarray(solid["centre"], np.float64)
+    if solid["kind"] == "sphere":
+        return np.sqrt((p * p).sum(axis=1)) - solid["radii"][0]
+    st, ct = _sincos_turns(np.array([solid["tilt"]]))
+    y = p[:, 1] * ct[0] + p[:, 2] * st[0]; z = -p[:, 1] * st[0] + p[:, 2] * ct[0]            # back into the torus's own frame (axis y)
+    R, r = solid["radii"]
+    ring = np.sqrt(p[:, 0] * p[:, 0] + z * z) - R
+    return np.sqrt(ring * ring + y * y) - r
 
 
 def tris_from_mesh(verts: np.ndarray, faces: np.ndarray) -> np.ndarray:
@@ -756,6 +786,133 @@ def lattice_boxes(origin, size, n) -> np.ndarray:
     for a, c in enumerate((x.reshape(-1), y.reshape(-1), z.reshape(-1))):
         out["min"][:, a] = origin[a] + c.astype(np.float32) * size[a]
         out["max"][:, a] = origin[a] + (c + 1).astype(np.float32) * size[a]
+    return out
+
+
+# ---- crossing queries: the numpy statement of include/hagrid/crossings.h (same operations, same order, same bits) ---------------------------
+
+INSIDE_WINDING = 1
+# the default directions of hagrid_points_inside: (3, 1, 2) / sqrt 14, (-2, 4, 3) / sqrt 29, (1, -5, 2) / sqrt 30 -- the float32 literals of crossings.h
+CROSSING_DIRS = np.array([[0.80178373, 0.26726124, 0.53452248], [-0.37139068, 0.74278135, 0.55708601], [0.18257419, -0.91287093, 0.36514837]], dtype=np.float32)
+
+
+def _prodsign(x, y):
+    """prodsign of common.h: x with its sign flipped when y is negative"""
+    x, y = np.broadcast_arrays(np.asarray(x, np.float32), np.asarray(y, np.float32))
+    return (np.ascontiguousarray(x).view(np.uint32) ^ (np.ascontiguousarray(y).view(np.uint32) & np.uint32(0x80000000))).view(np.float32)
+
+
+def admit_rays(rays: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """admit_ray of ray.h on (n, 8) float32 rows: (the rays with every zero of dir made +0, whether the ray may enter the cell walk)"""
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8).copy()
+    d = r[:, 4:7]
+    d[d == 0] = np.float32(0.0)
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(r[:, 0:3]).all(axis=1) & np.isfinite(d).all(axis=1)
+        moves = (np.isfinite(np.float32(1.0) / d) & (d != 0)).any(axis=1)
+    return r, fin & moves & ~np.isnan(r[:, 3]) & ~np.isnan(r[:, 7])
+
+
+def _ray_tri(T, org, dirv, tmin, tmax):
+    """intersect_prim_ray of prims.h on broadcastable float32 arrays: T = the 12 columns of the Tri records -> (accept, t, sign bit of det)"""
+    v0, e1, e2, n = (T[0], T[1], T[2]), (T[4], T[5], T[6]), (T[8], T[9], T[10]), (T[3], T[7], T[11])
+    c = _sub3(v0, org)
+    r = _cross3(dirv, c)
+    det = _dot3(n, dirv)
+    abs_det = np.abs(det)
+    u = _prodsign(_dot3(r, e2), det)
+    v = _prodsign(_dot3(r, e1), det)
+    w = abs_det - u - v
+    eps = np.float32(1e-9)
+    t = _prodsign(_dot3(n, c), det)
+    ok = (u >= -eps) & (v >= -eps) & (w >= -eps) & (t >= abs_det * tmin) & (abs_det * tmax > t)
+    tt = (t * (np.float32(1.0) / abs_det)).astype(np.float32)
+    return ok & ~np.isnan(tt), tt, np.signbit(det)          # (crosses() of crossings.h: a NaN t -- both dot products overflowed -- is refused)
+
+
+def ray_tri_pairs(tris: np.ndarray, rays: np.ndarray) -> dict:
+    """Triangle i against ray i (rays: (n, 8) float32): "accept" (the ray CROSSES the triangle: intersect_prim_ray of prims.h with the ray's own window; an
+    inadmissible ray crosses nothing), "t" and "entering" (the sign bit of det = dot(normal, dir)) -- float32, operation for operation of prims.h."""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    R, adm = admit_rays(rays)
+    with np.errstate(all="ignore"):
+        ok, t, neg = _ray_tri([T[:, i] for i in range(12)], (R[:, 0], R[:, 1], R[:, 2]), (R[:, 4], R[:, 5], R[:, 6]), R[:, 3], R[:, 7])
+    return {"accept": ok & adm, "t": t, "entering": neg}
+
+
+def ray_crossings(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 << 21) -> np.ndarray:
+    """The definition of hagrid_count_crossings by brute force: rays (n, 8) float32 -> HIT_DTYPE records.  With the crossings of a ray sorted by (t, id):
+    id = their number m, t = the first t (the bits of tmax when m = 0), u = length = the sequential float32 sum of t[2p+1] - t[2p] over the pairs,
+    v = the int32 bits of winding = #leaving - #entering.  Every ray against every triangle, a chunk of rays at a time."""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    R, adm = admit_rays(rays)
+    n, N = R.shape[0], T.shape[0]
+    out = np.zeros(n, dtype=HIT_DTYPE)
+    out["t"] = R[:, 7]
+    winding = np.zeros(n, dtype=np.int32)
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    ray_idx, tri_idx, ts, neg = [], [], [], []
+    with np.errstate(all="ignore"):
+        for o in range(0, n if N else 0, m):
+            r = R[o:o + m]
+            ok, t, ng = _ray_tri(cols, (r[:, 0:1], r[:, 1:2], r[:, 2:3]), (r[:, 4:5], r[:, 5:6], r[:, 6:7]), r[:, 3:4], r[:, 7:8])
+            ok = ok & adm[o:o + m, None]
+            rows, col = np.nonzero(ok)
+            ray_idx.append(rows + o); tri_idx.append(col); ts.append(t[rows, col]); neg.append(ng[rows, col])
+    if ray_idx:
+        r = np.concatenate(ray_idx); j = np.concatenate(tri_idx); t = np.concatenate(ts); ng = np.concatenate(neg)
+        order = np.lexsort((j, t, r))                  # by ray, then t, then id
+        r, t, ng = r[order], t[order], ng[order]
+        count = np.bincount(r, minlength=n).astype(np.int32)
+        first = np.cumsum(count) - count
+        has = count > 0
+        out["id"] = count
+        out["t"][has] = t[first[has]]
+        np.add.at(winding, r, np.where(ng, -1, 1).astype(np.int32))
+        length = np.zeros(n, dtype=np.float32)
+        with np.errstate(all="ignore"):                 # (inf - inf on rays whose every crossing has t = inf)
+            for p in range(int(count.max()) // 2 if r.size else 0):          # pair p of every ray that has one: the sum stays sequential per ray
+                sel = np.flatnonzero(count >= 2 * p + 2)
+                a = first[sel] + 2 * p
+                length[sel] = length[sel] + (t[a + 1] - t[a])
+        out["u"] = length
+    out["v"] = winding.view(np.float32)
+    return out
+
+
+def points_inside(tris: np.ndarray, points: np.ndarray, dirs=None, winding: bool = False, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of hagrid_points_inside by brute force: points (n, 4) float32 x, y, z, reach (or POINT_QUERY_DTYPE); dirs: None = CROSSING_DIRS, or
+    (1 | 3, 3) float32.  "records" (n, m) HIT_DTYPE: ray_crossings of org = p, tmin = 0, dir = d, tmax = reach, direction fastest; "inside" (n,) int32: 1 when
+    2 * votes > m with the vote count & 1 (winding: winding != 0), else 0; -1 for an inactive point (reach < 0 or NaN, a NaN or infinite coordinate), whose
+    records are empty (count 0, t = the bits of reach)."""
+    P = np.ascontiguousarray(points).view(np.float32).reshape(-1, 4)
+    D = CROSSING_DIRS if dirs is None else np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    n, m = P.shape[0], D.shape[0]
+    with np.errstate(all="ignore"):
+        active = np.isfinite(P[:, 0:3]).all(axis=1) & (P[:, 3] >= np.float32(0.0))
+    rays = np.zeros((n, m, 8), dtype=np.float32)
+    rays[:, :, 0:3] = P[:, None, 0:3]; rays[:, :, 4:7] = D[None, :, :]; rays[:, :, 7] = P[:, None, 3]
+    rec = np.zeros((n, m), dtype=HIT_DTYPE)
+    rec["t"] = P[:, None, 3]
+    idx = np.flatnonzero(active)
+    if idx.size:
+        rec[idx] = ray_crossings(tris, rays[idx].reshape(-1, 8), chunk_pairs).reshape(idx.size, m)
+    votes = ((rec["v"].view(np.int32) != 0) if winding else (rec["id"] & 1) != 0).sum(axis=1)
+    inside = np.where(active, (2 * votes > m).astype(np.int32), np.int32(-1)).astype(np.int32)
+    return {"inside": inside, "records": rec}
+
+
+def lattice_centres(origin, size, n) -> np.ndarray:
+    """The points of hagrid_inside_lattice as POINT_QUERY_DTYPE records, x fastest: the centre of voxel c of an axis is origin + (float(c) + 0.5) * size
+    in float32; reach +inf."""
+    origin = np.asarray(origin, np.float32); size = np.asarray(size, np.float32)
+    nx, ny, nz = (int(v) for v in n)
+    out = np.zeros(nx * ny * nz, dtype=POINT_QUERY_DTYPE)
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    for a, c in enumerate((x.reshape(-1), y.reshape(-1), z.reshape(-1))):
+        out["p"][:, a] = origin[a] + (c.astype(np.float32) + np.float32(0.5)) * size[a]
+    out["r"] = np.float32(np.inf)
     return out
 
 

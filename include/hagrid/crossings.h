@@ -1,0 +1,311 @@
+// hagrid/crossings.h -- crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_points_inside, hagrid_inside_lattice): ALL the surfaces
+// a ray crosses, condensed into one 16-byte record, and from that whether a point lies inside a closed surface.  No counterpart in the
+// reference, which answers with the nearest hit only.
+//
+// Everything is float32 without contraction (-ffp-contract=off), every sum in the order written.  The same code serves the gfx950 kernel
+// (hagrid_amd/csrc/crossings.hip) and host programs (tests/cpp/crossings_host.cpp); hagrid_amd/scene.py (ray_tri_pairs, ray_crossings,
+// points_inside, lattice_centres) states the same operations in numpy and gives the same bits.
+//
+// ---- one ray, one triangle ------------------------------------------------------------------------------------------------------
+// Ray i CROSSES triangle j exactly when intersect_prim_ray(tri[j], Ray(org, tmin, dir, tmax), j, h) of prims.h accepts the pair with the
+// ray's OWN window -- the intersection set of multi_hit.h.  Its value is t = h.t.  Its FACING is the sign bit of det = dot(tri.normal(),
+// ray.dir), the expression of prims.h: LEAVING when the bit is clear (the ray runs with the normal), ENTERING when it is set.
+// An accepted pair never has det == 0 and never a NaN t:
+//   * det == +-0: abs_det = 0, so both window comparisons have a product with 0 on one side: `t >= abs_det * tmin` and `abs_det * tmax > t` read t >= 0
+//     and 0 > t (or a comparison with NaN for an infinite bound, which is false).  No t is both: refused.  A NaN det makes abs_det NaN and the
+//     comparisons of u, v, w false: refused.
+//   * h.t = t * (1 / abs_det) is NaN only if t is (fails `t >= abs_det * tmin`: refused), if abs_det is (above), or as 0 * inf: t = 0 with abs_det = 0
+//     (above), or t infinite with abs_det infinite.  t = +inf fails `abs_det * tmax > t`.  That leaves t = -inf with abs_det = +inf, tmin < 0 < tmax: BOTH
+//     dot(n, dir) and dot(n, v0 - org) overflowed float32, which takes a direction AND an origin some 1e19 times the scene's size.  prims.h accepts that
+//     pair with a NaN t; crosses() below refuses it (t == t), so that no NaN ever enters the order.  No ray of the tests is such a ray.
+// So the facing is never the sign of a zero, and (t, id) is a strict total order on the crossings of a ray.
+//
+// ---- the record -----------------------------------------------------------------------------------------------------------------
+// 16 bytes in the layout of Hit, so the shading kernels read it as it is (GRAY / HEAT of hagrid_shade_hits over records: the crossing-count
+// picture; DEPTH: the first surface).  With the m crossings of the ray sorted by (t ascending, id ascending) as c_0 .. c_{m-1}:
+//   id  int32         count = m
+//   t   float32       t_first = t of c_0; the bits of the ray's tmax when m = 0
+//   u   float32       length: acc = +0.0f; for p = 0, 1, .. while 2p + 1 < m: acc = acc + (t_{2p+1} - t_{2p}) -- sequential, in that order.  The
+//                     length of the ray inside the solid when it starts outside a closed surface; an unpaired last crossing adds nothing.
+//   v   int32 bits    winding = #leaving - #entering
+// A ray that admit_ray (ray.h) refuses takes no cell step, nor does an inactive ray (tmax = -1: the window is empty); both get count 0,
+// t = the bits of tmax, length +0, winding 0.
+//
+// ---- exact counting without a list of unbounded length --------------------------------------------------------------------------
+// A triangle is referenced by several cells, so counting needs exact de-duplication, and no canonical-cell rule gives it (overlap.h: the
+// build inserts by the separating-axis test, expanded cell boxes overlap).  What multi_hit.h relies on does: a sorted list of bounded
+// capacity that keeps each triangle once -- plus a CURSOR.
+//   * A PAGE holds the P smallest crossings that sort STRICTLY AFTER the cursor (t, id).  It is HitList's structure on (t, key) only
+//     (key = id * 2 + entering; no u, v): the same duplicate check, the same "the last entry only decreases" argument, every loop over
+//     compile-time indices.  P <= PMAX is the same for every ray of a launch.
+//   * When the page is full and its last entry is not beyond the exit of the current cell (last_t <= texit, the stop rule of trav_multi.hip) -- or
+//     the ray has left the grid --, the page is FLUSHED: its entries are folded, in order, into the ACCUMULATOR (count, winding, first t, the
+//     running length and the pending unpaired t, so a pair may straddle two pages), the cursor becomes the page's last entry, the page is
+//     emptied, and the list of the CURRENT cell is tested again before the walk steps on.  A page that is not full when the ray leaves the
+//     grid is folded and the ray is done.
+//   * The cursor strictly increases at every flush, and every flush of a full page folds P distinct crossings: at most floor(m / P) such flushes
+//     plus the final one, so the number of flushes is at most ceil(m / P) + 1.
+// Why nothing is lost and nothing counted twice.  Counted twice: an entry is folded once, and afterwards it does not sort after the cursor,
+// so the page refuses it for good.  Lost: the argument is multi-hit's, per page.  It rests on
+//   (a) a cell's reference list holds every triangle that meets the cell's box (closest.h (a));
+//   (b) every triangle lies inside the grid box, so a crossing lies on the part of the ray inside the grid;
+//   (c) the cells the walk visits cover that part of the ray in order of t, each up to its texit;
+// so when the walk is in cell C, every crossing with t <= texit(C) has been offered by C or a cell before it.  A flush happens with
+// last_t <= texit(C) (or at the end of the ray, where everything has been offered).  Every crossing between the old cursor and the page's
+// last entry has t <= last_t <= texit(C), was therefore offered while the page's last entry was no smaller than now, and so is in the page:
+// the page IS the P smallest crossings after the old cursor, of the whole ray.  What the full page refused or dropped sorts after its last
+// entry, the new cursor.  Such a crossing D is offered again if its triangle is listed by C or a later cell.  If it is listed only by
+// cells before C, it lies in one of them, E, with t_D <= texit(E); it was refused or dropped by a full page whose last entry sorts
+// before D, so that page had last_t <= t_D <= texit(E) while the walk was still in E or before: the flush rule fired THERE, and kept firing
+// with E's list tested again, until D was folded.  So no crossing is left behind a cell the walk has stepped past.
+// The record does not depend on P: crossings_brute_force over ALL triangles defines it, the walk reproduces it.
+//
+// ---- points ---------------------------------------------------------------------------------------------------------------------
+// A point record is 16 bytes: x, y, z, reach.  For each of m in {1, 3} directions d the ray is org = p, tmin = 0, dir = d, tmax = reach (+inf is
+// allowed and the normal case).  The VOTE of d is count & 1, with HAGRID_INSIDE_WINDING it is winding != 0; inside = 1 when 2 * votes > m,
+// else 0; -1 for an INACTIVE point (reach < 0, a NaN reach, a NaN or infinite coordinate), which takes no walk.  The default directions
+// (kDefaultDirs) are (3, 1, 2) / sqrt 14, (-2, 4, 3) / sqrt 29, (1, -5, 2) / sqrt 30: none lies along a lattice axis or a face diagonal, so a ray
+// through a vertex or an edge of an axis-aligned tessellation is not the common case, and the majority of three makes a single grazing
+// ray harmless.  The answer MEANS something for closed surfaces only; a point ON the surface gets whatever the formula gives (tmin = 0
+// accepts t = 0).  The lattice form uses the centre of voxel (x, y, z), x fastest: origin + (float(c) + 0.5f) * size per axis, reach +inf.
+#ifndef HAGRID_CROSSINGS_H
+#define HAGRID_CROSSINGS_H
+
+#include "grid.h"
+#include "multi_hit.h"
+#include "prims.h"
+#include "ray.h"
+#include "vec.h"
+
+namespace hagrid {
+namespace crossings {
+
+constexpr int kMaxPage = 8;
+
+/// the three default directions, unit length to float32 rounding
+constexpr float kDefaultDirs[9] = {0.80178373f, 0.26726124f, 0.53452248f, -0.37139068f, 0.74278135f, 0.55708601f, 0.18257419f, -0.91287093f, 0.36514837f};
+
+/// the pair: does the ray cross the triangle; t and the facing (true: entering, the sign bit of det)
+HOST DEVICE inline bool crosses(const Tri& tri, const Ray& ray, float& t, bool& entering) {
+    Hit h;
+    if (!intersect_prim_ray(tri, ray, 0, h) || !(h.t == h.t)) return false;
+    t = h.t;
+    entering = (as<uint32_t>(dot(tri.normal(), ray.dir)) & 0x80000000u) != 0;          // det of prims.h: the same expression, the same bits
+    return true;
+}
+
+/// what a ray has crossed so far, in the order of (t, id)
+struct Accum {
+    int count, winding;
+    float t_first, length, pending;
+    HOST DEVICE void init(float tmax) { count = 0; winding = 0; t_first = tmax; length = 0.0f; pending = 0.0f; }
+    HOST DEVICE void fold(float t, bool entering) {
+        if (count == 0) t_first = t;
+        if (count & 1) length = length + (t - pending);
+        else pending = t;
+        count++;
+        winding += entering ? -1 : 1;
+    }
+    HOST DEVICE Hit record() const { return Hit(count, t_first, length, as<float>(winding)); }
+};
+
+/// the P smallest crossings after the cursor, sorted, each triangle once.  key = id * 2 + entering (ids fit 31 bits); an empty slot has kEmpty.
+template <int PMAX>
+struct Page {
+    static constexpr uint32_t kEmpty = 0xffffffffu;
+    uint32_t key[PMAX];
+    float t[PMAX];
+    int cap;                                ///< P: slots in use, 1 .. PMAX
+    uint32_t last_key; float last_t;        ///< copy of slot cap - 1: the page is full when last_key != kEmpty
+    bool has_cursor; uint32_t cur_key; float cur_t;
+
+    HOST DEVICE void init(int p) {
+        cap = p; has_cursor = false; cur_key = 0; cur_t = 0.0f;
+        clear();
+    }
+    HOST DEVICE void clear() {
+        last_key = kEmpty; last_t = 0.0f;
+        HAGRID_UNROLL
+        for (int j = 0; j < PMAX; j++) { key[j] = kEmpty; t[j] = 0.0f; }
+    }
+    HOST DEVICE bool full() const { return last_key != kEmpty; }
+    HOST DEVICE bool empty() const { return key[0] == kEmpty; }
+
+    /// (ta, ka) sorts before (tb, kb); keys of different triangles compare like their ids
+    HOST DEVICE static bool before(float ta, uint32_t ka, float tb, uint32_t kb) { return ta < tb || (ta == tb && ka < kb); }
+
+    /// an accepted crossing; returns whether the page changed
+    HOST DEVICE bool insert(float ht, uint32_t k) {
+        if (has_cursor && !before(cur_t, cur_key, ht, k)) return false;             // folded already
+        if (last_key != kEmpty && !before(ht, k, last_t, last_key)) return false;   // cannot change a full page
+        bool dup = false;
+        HAGRID_UNROLL
+        for (int j = 0; j < PMAX; j++) dup = dup || key[j] == k;
+        if (dup) return false;
+        uint32_t ck = k; float ct = ht;
+        HAGRID_UNROLL
+        for (int j = 0; j < PMAX; j++) {
+            const bool take = j < cap && (key[j] == kEmpty || before(ct, ck, t[j], key[j]));
+            const uint32_t ok = key[j]; const float ot = t[j];
+            key[j] = take ? ck : ok; t[j] = take ? ct : ot;
+            ck = take ? ok : ck; ct = take ? ot : ct;
+        }
+        HAGRID_UNROLL
+        for (int j = 0; j < PMAX; j++)
+            if (j == cap - 1) { last_key = key[j]; last_t = t[j]; }
+        return true;
+    }
+
+    /// fold the entries, in order, into the accumulator; the cursor moves to the last of them; the page is empty afterwards
+    HOST DEVICE void flush(Accum& acc) {
+        HAGRID_UNROLL
+        for (int j = 0; j < PMAX; j++)
+            if (j < cap && key[j] != kEmpty) {
+                acc.fold(t[j], (key[j] & 1u) != 0);
+                has_cursor = true; cur_key = key[j]; cur_t = t[j];
+            }
+        clear();
+    }
+};
+
+/// The definition: every triangle against the ray, a page of PMAX over ALL triangles, again and again until a page comes back not full.  tri_at(j) -> Tri.
+/// No grid, no cell, no stop rule: a pass offers everything, so each page is the PMAX smallest crossings after the cursor; the record does not depend on
+/// PMAX (a host program takes a large one: a ray with m crossings costs m / PMAX + 1 passes).
+template <int PMAX = kMaxPage, typename F>
+HOST DEVICE inline Hit crossings_brute_force(F tri_at, int num_tris, const Ray& ray_in) {
+    vec3 dir = ray_in.dir;
+    const bool admitted = admit_ray(ray_in.org, dir, ray_in.tmin, ray_in.tmax);
+    const Ray ray(ray_in.org, ray_in.tmin, dir, ray_in.tmax);
+    Accum acc;
+    acc.init(ray.tmax);
+    if (!admitted) return acc.record();
+    Page<PMAX> page;
+    page.init(PMAX);
+    for (;;) {
+        for (int j = 0; j < num_tris; j++) {
+            float t; bool entering;
+            if (crosses(tri_at(j), ray, t, entering)) page.insert(t, (uint32_t(j) << 1) | (entering ? 1u : 0u));
+        }
+        const bool more = page.full();
+        page.flush(acc);
+        if (!more) break;
+    }
+    return acc.record();
+}
+
+/// float -> int as the gfx950 conversion does it (v_cvt_i32_f32: truncation, saturating, NaN -> 0).  On the host a plain cast of a value that does not fit
+/// is undefined (x86 gives INT_MIN), and the walk does convert such values: the voxel coordinate of an exit point far outside the grid.  Written out, so that
+/// the host walk and the kernel take the same steps on every ray.
+HOST DEVICE inline int f2i(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return int(f);
+#else
+    if (!(f == f)) return 0;
+    if (f >= 2147483648.0f) return 2147483647;
+    if (f <= -2147483648.0f) return -2147483647 - 1;
+    return int(f);
+#endif
+}
+
+/// per-ray counts of the walk
+struct Counts { int cells, tests, flushes; };
+
+/// setup_traversal's constants
+struct WalkConsts {
+    ivec3 top, dims;
+    int shift;
+    vec3 lo, hi, cell_size, inv;
+    HOST DEVICE void set(const ivec3& dims_, int shift_, const vec3& lo_, const vec3& hi_) {
+        dims = dims_; shift = shift_; lo = lo_; hi = hi_;
+        top = ivec3(dims.x >> shift, dims.y >> shift, dims.z >> shift);
+        const vec3 ext = hi - lo;
+        inv = vec3(dims) / ext;
+        cell_size = ext / vec3(dims);
+    }
+};
+
+struct CellRec { int lx, ly, lz, hx, hy, hz, begin, end; };
+
+/// The walk of trav_multi.hip with pages: the record of one ray over the grid g, equal to crossings_brute_force over all triangles.
+/// G: c (WalkConsts), small (SmallCell lists end with their sentinel), cell_at(vx, vy, vz) -> CellRec, ref(i), tri(id).  P: the page capacity.
+/// The device kernel is this function with the next cell's loads issued early; tests/cpp/crossings_host.cpp runs it as it stands.
+template <int PMAX, typename G>
+HOST DEVICE inline Hit crossings_walk(const G& g, const Ray& ray_in, int P, Counts& n) {
+    const WalkConsts& k = g.c;
+    const vec3 org = ray_in.org;
+    vec3 dir = ray_in.dir;
+    const float tmin = ray_in.tmin, tmax = ray_in.tmax;
+    const bool admitted = admit_ray(org, dir, tmin, tmax);
+    const Ray ray(org, tmin, dir, tmax);
+    const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
+    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));
+    const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
+    const vec3 ta = (k.lo - org) * inv_dir, tb = (k.hi - org) * inv_dir;
+    const vec3 t0 = min(ta, tb), t1 = max(ta, tb);
+    const float tstart = detail::fmax2(detail::fmax2(t0.x, detail::fmax2(t0.y, t0.z)), tmin);
+    const float tend = detail::fmin2(detail::fmin2(t1.x, detail::fmin2(t1.y, t1.z)), tmax);
+
+    Accum acc;
+    acc.init(tmax);
+    n.cells = 0; n.tests = 0; n.flushes = 0;
+    if (!(admitted && !(tstart > tend))) return acc.record();
+
+    Page<PMAX> page;
+    page.init(P);
+    const vec3 fv = (tstart * dir + org - k.lo) * k.inv;
+    int vx = min(max(f2i(fv.x), 0), k.dims.x - 1);
+    int vy = min(max(f2i(fv.y), 0), k.dims.y - 1);
+    int vz = min(max(f2i(fv.z), 0), k.dims.z - 1);
+    for (;;) {
+        const CellRec c = g.cell_at(vx, vy, vz);
+        n.cells++;
+        const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
+        const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * k.cell_size + k.lo - org) * walk_inv;
+        const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
+        const vec3 ev = (texit * dir + org - k.lo) * k.inv;
+        const int nx = texit == tcell.x ? cx + (px ? 0 : -1) : f2i(ev.x);
+        const int ny = texit == tcell.y ? cy + (py ? 0 : -1) : f2i(ev.y);
+        const int nz = texit == tcell.z ? cz + (pz ? 0 : -1) : f2i(ev.z);
+        vx = px ? max(nx, vx) : min(nx, vx);
+        vy = py ? max(ny, vy) : min(ny, vy);
+        vz = pz ? max(nz, vz) : min(nz, vz);
+        const bool outside = vx < 0 || vx >= k.dims.x || vy < 0 || vy >= k.dims.y || vz < 0 || vz >= k.dims.z;
+        for (;;) {
+            if (g.small ? c.begin >= 0 : c.begin < c.end) {
+                for (int cur = c.begin; g.small || cur < c.end; cur++) {
+                    const int ref = g.ref(cur);
+                    if (ref < 0) break;
+                    float t; bool entering;
+                    n.tests++;
+                    if (crosses(g.tri(ref), ray, t, entering)) page.insert(t, (uint32_t(ref) << 1) | (entering ? 1u : 0u));
+                }
+            }
+            if (!(page.full() && (page.last_t <= texit || outside))) break;
+            page.flush(acc);          // and this cell's list once more
+            n.flushes++;
+        }
+        if (outside) break;
+    }
+    if (!page.empty()) { page.flush(acc); n.flushes++; }
+    return acc.record();
+}
+
+/// an inactive point takes no walk and gets inside = -1: reach < 0 or NaN, a NaN or infinite coordinate
+HOST DEVICE inline bool point_active(const vec3& p, float reach) {
+    const uint32_t e = 0x7f800000u;
+    const bool finite = ((as<uint32_t>(p.x) & e) != e) & ((as<uint32_t>(p.y) & e) != e) & ((as<uint32_t>(p.z) & e) != e);
+    return finite && reach >= 0.0f;
+}
+
+/// the vote of one ray's record
+HOST DEVICE inline int vote(const Hit& rec, bool winding) { return winding ? (as<int32_t>(rec.v) != 0 ? 1 : 0) : (rec.id & 1); }
+
+/// the centre of voxel c of a lattice along one axis
+HOST DEVICE inline float lattice_centre(float origin, int c, float size) { return origin + (float(c) + 0.5f) * size; }
+
+} // namespace crossings
+} // namespace hagrid
+
+// The C++ shim over the entry points (count_crossings, points_inside, inside_lattice) is with its neighbours in traverse.h.
+
+#endif // HAGRID_CROSSINGS_H

@@ -67,6 +67,30 @@ inline void overlap_lattice(const Grid& grid, const Tri* tris, const vec3& origi
     detail::check(detail::current_ctx(), hagrid_overlap_lattice(detail::current_ctx(), &p, tris, o, s, m, k, ids, counts, counters, any ? HAGRID_OVERLAP_ANY : 0u));
 }
 
+/// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_points_inside, hagrid_inside_lattice; the record, the paging and the walk:
+/// crossings.h).  records: num_rays Hit-shaped records (count, t_first, length, winding bits); counters: nullptr or int64[4] -- DEVICE pointers.  Asynchronous.
+inline void count_crossings(const Grid& grid, const Tri* tris, const Ray* rays, Hit* records, int num_rays, void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_count_crossings(detail::current_ctx(), &p, tris, rays, records, num_rays, counters, 0u));
+}
+/// points: num_points records x, y, z, reach; dirs: nullptr (the three defaults) or num_dirs * 3 HOST floats; inside: num_points int32; records: nullptr or
+/// num_points * m Hit-shaped records, direction fastest.
+inline void points_inside(const Grid& grid, const Tri* tris, const void* points, int num_points, int* inside, const float* dirs = nullptr, int num_dirs = 0,
+                          Hit* records = nullptr, void* counters = nullptr, bool winding = false) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_points_inside(detail::current_ctx(), &p, tris, points, num_points, dirs, num_dirs, inside, records, counters,
+                                                              winding ? HAGRID_INSIDE_WINDING : 0u));
+}
+/// the centres of the voxels of an n.x * n.y * n.z lattice (x fastest) as the points, reach +inf
+inline void inside_lattice(const Grid& grid, const Tri* tris, const vec3& origin, const vec3& size, const ivec3& n, int* inside, const float* dirs = nullptr,
+                           int num_dirs = 0, Hit* records = nullptr, void* counters = nullptr, bool winding = false) {
+    hagrid_grid p = detail::to_pod(grid);
+    const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {size.x, size.y, size.z};
+    const int m[3] = {n.x, n.y, n.z};
+    detail::check(detail::current_ctx(), hagrid_inside_lattice(detail::current_ctx(), &p, tris, o, s, m, dirs, num_dirs, inside, records, counters,
+                                                               winding ? HAGRID_INSIDE_WINDING : 0u));
+}
+
 /// Extension: independent batches in flight.  Every MemManager is a context with a stream of its own (hagrid_ctx_set_stream on
 /// mem.context()); `share_traversal(dst, src)` lets `dst` traverse with the traversal image setup_traversal built in `src`, and the
 /// overload below traverses on a named manager instead of the current one.  Two 1M-ray batches in flight take 0.118 ms each

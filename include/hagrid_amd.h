@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -311,6 +311,41 @@ int hagrid_overlap_boxes(hagrid_ctx* ctx, const hagrid_grid* grid, const void* t
                          void* ids, void* counts, void* counters, uint32_t flags);
 int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, int k,
                            void* ids, void* counts, void* counters, uint32_t flags);
+
+/* Extension (no reference counterpart): CROSSING queries -- ALL the surfaces a ray crosses, and from that whether a point lies inside a closed surface
+ * (thickness and path length through a solid, signed distance = hagrid_closest_points + inside, solid voxelization = hagrid_overlap_lattice + inside;
+ * Embree's rtcIntersect with a collecting filter, Open3D's compute_occupancy).  Ray i CROSSES triangle j exactly when intersect_prim_ray of
+ * include/hagrid/prims.h accepts the pair with the ray's OWN [tmin, tmax) -- the intersection set of hagrid_traverse_grid_multi; its value is t, its
+ * FACING the sign bit of det = dot(normal, dir): leaving when clear, entering when set (an accepted pair never has det == 0).  With the m crossings of the
+ * ray sorted by (t ascending, id ascending) as c_0 .. c_{m-1}, records[i] is 16 bytes in the layout of Hit (so hagrid_shade_hits reads it: GRAY / HEAT = the
+ * crossing-count picture, DEPTH = the first surface):
+ *   int32 count = m;  float32 t_first = t of c_0 (the bits of tmax when m = 0);
+ *   float32 length = the float32 sum, in order, of t_{2p+1} - t_{2p} over the pairs p = 0, 1, .. with 2p + 1 < m, starting from +0 (the length of the ray inside
+ *   the solid when it starts outside a closed surface; an unpaired last crossing adds nothing);  int32 winding = #leaving - #entering.
+ * A ray that is not admissible or inactive (tmax = -1) takes no cell step: count 0, t = the bits of tmax, length +0, winding 0.  m is NOT bounded:
+ * the walk keeps a page of the eight smallest crossings after a cursor, folds it into the record and goes on (include/hagrid/crossings.h); the
+ * records are those of the brute force over all triangles, bit for bit.  One launch walks the CONSTRUCTION format in buffer order (hagrid_amd/csrc/crossings.hip);
+ * the traversal image, hagrid_set_ray_binning, tile packets, the learned tile order and the hints kept for the nearest-hit path are neither used nor touched.
+ * counters: NULL, or DEVICE int64[4] to which the batch totals are ADDED (items, cells visited, triangle tests, pages flushed): clear it first.
+ * hagrid_points_inside: points holds 16 bytes per point, float32 x, y, z, reach.  For each of m = num_dirs in {1, 3} directions d (dirs: HOST floats, m * 3;
+ * NULL with num_dirs = 0 means the three defaults (3, 1, 2) / sqrt 14, (-2, 4, 3) / sqrt 29, (1, -5, 2) / sqrt 30) the ray is org = p, tmin = 0, dir = d, tmax = reach
+ * (+inf is allowed and the normal case).  The vote of d is count & 1, with HAGRID_INSIDE_WINDING it is winding != 0.  inside[i] (int32) is 1 when 2 * votes > m, else
+ * 0; -1 for an INACTIVE point (reach < 0, a NaN reach, a NaN or infinite coordinate), which takes no walk.  records: NULL, or DEVICE n * m records (direction
+ * fastest) that receive the per-ray records.  The answer means something for CLOSED surfaces only; a point ON the surface gets whatever the formula gives
+ * (tmin = 0 accepts t = 0).  hagrid_inside_lattice uses the centre of voxel (x, y, z) of the n[0] x n[1] x n[2] lattice, x fastest, as the point: origin +
+ * (float(c) + 0.5f) * size per axis, reach +inf; origin, size and n are HOST arrays of 3.  All three are asynchronous on the context's stream.
+ * HAGRID_EINVAL: a null grid or one released by hagrid_grid_release_for_traversal; a context with "traverse.id_is_steps" = 1; null or misaligned buffers
+ * (triangles, rays, points and records 16 bytes; inside 4; counters 8); an unknown flag (hagrid_count_crossings has none); a negative count; num_dirs not 1 or 3
+ * (0 is allowed with dirs == NULL); a direction that is not finite or has no component to walk along; a lattice with n <= 0 on an axis or more than 2^31 - 1
+ * voxels, a voxel size that is not positive and finite, an origin that is not finite.  HAGRID_ERANGE: num_points * m beyond 2^31 - 1.  A count of 0 is HAGRID_OK
+ * (null buffers are then fine). */
+int hagrid_count_crossings(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* rays, void* records,
+                           int num_rays, void* counters, uint32_t flags);
+#define HAGRID_INSIDE_WINDING 1u
+int hagrid_points_inside(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points,
+                         const float* dirs, int num_dirs, void* inside, void* records, void* counters, uint32_t flags);
+int hagrid_inside_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n,
+                          const float* dirs, int num_dirs, void* inside, void* records, void* counters, uint32_t flags);
 
 /* Extension (no reference counterpart): spatial binning of the ray batch before traversal.  mode 0 (default): rays
  * are traversed in buffer order, as the reference does.  mode 1: each hagrid_traverse_grid call first bins the rays by
