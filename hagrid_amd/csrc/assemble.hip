@@ -89,7 +89,6 @@ __global__ void __launch_bounds__(kBlock) assemble_tris_kernel(const hagrid_mesh
     if (b && int(threadIdx.x & 63u) == __ffsll(b) - 1) atomicAdd(bad_count, (unsigned long long)__popcll(b));
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 int check_mesh(hagrid_ctx* ctx, const hagrid_mesh& m) {

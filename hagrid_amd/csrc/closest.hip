@@ -21,37 +21,6 @@ namespace hc = hagrid::closest;
 
 namespace {
 
-struct DevGrid {
-    hc::GridConsts c;
-    const uint32_t* __restrict__ entries;
-    const void* __restrict__ cells;
-    const int* __restrict__ refs;
-    const float4* __restrict__ tris;
-    int small;
-
-    __device__ __forceinline__ uint32_t word(uint32_t i) const { return entries[i]; }
-    __device__ __forceinline__ hc::CellRec cell(uint32_t i) const {
-        CellBox b;
-        if (small) { b = load_cell_box<true>(cells, i); b.end = 0x7fffffff; }
-        else       { b = load_cell_box<false>(cells, i); }
-        hc::CellRec r;
-        r.lx = b.lx; r.ly = b.ly; r.lz = b.lz; r.hx = b.hx; r.hy = b.hy; r.hz = b.hz; r.begin = b.begin; r.end = b.end;
-        return r;
-    }
-    __device__ __forceinline__ int ref(int i) const { return refs[i]; }
-    __device__ __forceinline__ Tri tri(int id) const { return load_tri(tris, id); }
-};
-
-// the descent's stack in LDS: column `lane` of two [level][64] arrays
-struct LdsStack {
-    uint32_t* w_;
-    uint32_t* i_;
-    __device__ __forceinline__ void set(int level, uint32_t w, uint32_t i) { w_[level * 64] = w; i_[level * 64] = i; }
-    __device__ __forceinline__ void set_i(int level, uint32_t i) { i_[level * 64] = i; }
-    __device__ __forceinline__ uint32_t w(int level) const { return w_[level * 64]; }
-    __device__ __forceinline__ uint32_t i(int level) const { return i_[level * 64]; }
-};
-
 __global__ void __launch_bounds__(64) closest_points_kernel(const DevGrid g, const float4* __restrict__ points, float4* __restrict__ results, const int n,
                                                             unsigned long long* __restrict__ counters) {
     __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
@@ -69,22 +38,8 @@ __global__ void __launch_bounds__(64) closest_points_kernel(const DevGrid g, con
         nt_store4(results + 2 * size_t(id), b.q.x, b.q.y, b.q.z, b.d2);
         nt_store4(results + 2 * size_t(id) + 1, __int_as_float(b.id), __int_as_float(b.feature), float(b.side), 0.0f);
     }
-    if (counters) {     // batch totals: the wavefront's sums, one vector atomic each
-        const int queries = wave_sum(live ? 1 : 0), cells = wave_sum(cnt.cells), pruned = wave_sum(cnt.pruned);
-        // triangles tested: a lane's count fits 31 bits, 64 of them need not
-        unsigned long long tris = (unsigned long long)(unsigned)cnt.tris;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) tris += (unsigned long long)__shfl_xor((long long)tris, d, 64);
-        if (lane == 0) {
-            atomicAdd(counters + 0, (unsigned long long)queries);
-            atomicAdd(counters + 1, (unsigned long long)(unsigned)cells);
-            atomicAdd(counters + 2, tris);
-            atomicAdd(counters + 3, (unsigned long long)(unsigned)pruned);
-        }
-    }
+    if (counters) add_batch_counters(counters, lane, live ? 1 : 0, cnt.cells, cnt.tris, cnt.pruned);
 }
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 } // namespace
 
@@ -103,13 +58,7 @@ extern "C" int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, c
     if (!aligned(tris, 16) || !aligned(points, 16) || !aligned(results, 16)) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: triangles, points and results must be 16-byte aligned");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     DevGrid g;
-    g.c.set(ivec3(grid->dims[0], grid->dims[1], grid->dims[2]), grid->shift, vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2]),
-            vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]));
-    g.entries = static_cast<const uint32_t*>(grid->entries);
-    g.cells = grid->small_cells ? grid->small_cells : grid->cells;
-    g.refs = static_cast<const int*>(grid->ref_ids);
-    g.tris = static_cast<const float4*>(tris);
-    g.small = grid->small_cells != nullptr ? 1 : 0;
+    g.set(grid, tris);
     closest_points_kernel<<<grid_blocks(num_points, 64), 64, 0, ctx->stream>>>(g, static_cast<const float4*>(points), static_cast<float4*>(results), num_points,
                                                                                 static_cast<unsigned long long*>(counters));
     HG_DBG(ctx);

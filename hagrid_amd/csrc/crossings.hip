@@ -2,14 +2,13 @@
 // from that whether a point lies inside a closed surface (include/hagrid_amd.h: hagrid_count_crossings, hagrid_points_inside, hagrid_inside_lattice; the record,
 // the page, the accumulator and the argument why nothing is lost: include/hagrid/crossings.h).  No counterpart in the reference.
 //
-// The kernel is the header's crossings_walk in the shape of traverse_multi_kernel (trav_multi.hip): one wavefront per workgroup, the XCD-aware block -> item
-// map, the next cell's voxel-map walk and cell load issued before the current cell's triangle tests, streaming 16-byte loads and stores, the construction
-// format (entries -> cells | small_cells -> ref_ids) walked in buffer order.  Like multi-hit it neither uses nor touches the traversal image, ray binning, tile
-// packets, the learned order or the nearest-hit hints.  One lane per ITEM: a ray in the ray form, a point in the point and lattice forms -- the lane then walks
-// its m rays one after another.  The cell format, the source (ray buffer, point buffer or lattice constants), m, the directions, the vote rule and whether
-// records are stored are kernel arguments, uniform over the launch: ONE kernel (the product library's kernel budget, tests/test_abi.py).  The page (kPage
-// entries of t and key, no u, v) and the accumulator live in registers: every loop over the page runs over compile-time indices.  When a page is flushed the
-// SAME cell's list is tested again; `again` keeps that to one copy of the list loop.  kPage was chosen by register count alone, not by timing.
+// The kernel runs the header's crossings_walk (the walk of hagrid/cell_walk.h with the page visitor) over the device accessor of trav_common.h, launched
+// like traverse_multi_kernel (trav_multi.hip): one wavefront per workgroup, the XCD-aware block -> item map, streaming 16-byte loads and stores.  Like
+// multi-hit it neither uses nor touches the traversal image, ray binning, tile packets, the learned order or the nearest-hit hints.  One lane per ITEM: a
+// ray in the ray form, a point in the point and lattice forms -- the lane then walks its m rays one after another.  The cell format, the source (ray
+// buffer, point buffer or lattice constants), m, the directions, the vote rule and whether records are stored are kernel arguments, uniform over the
+// launch: ONE kernel (the product library's kernel budget, tests/test_abi.py).  The page (kPage entries of t and key, no u, v) and the accumulator live in
+// registers: every loop over the page runs over compile-time indices.  kPage was chosen by register count alone, not by timing.
 #include "trav_common.h"
 #include "wave_prims.h"
 
@@ -38,15 +37,7 @@ struct CrossArgs {
     int nx, ny;                                 // lattice: voxels along x and y (x fastest)
 };
 
-__device__ __forceinline__ CellBox load_cell(const void* __restrict__ cells, uint32_t index, bool small) {
-    CellBox c;
-    if (small) { c = load_cell_box<true>(cells, index); c.end = 0x7fffffff; }
-    else       { c = load_cell_box<false>(cells, index); }
-    return c;
-}
-
 __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, const CrossArgs q, const int small_cells) {
-    const bool SMALL = small_cells != 0;
     const int lane = threadIdx.x;
     const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
     const bool live = id < q.n;
@@ -70,121 +61,25 @@ __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, con
             }
             active = hx::point_active(org, tmax);
         }
-        const vec3 gmin(a.min_x, a.min_y, a.min_z), gmax(a.max_x, a.max_y, a.max_z);
-        const vec3 csize(a.cs_x, a.cs_y, a.cs_z), ginv(a.inv_x, a.inv_y, a.inv_z);
+
         int votes = 0;
 #pragma unroll 1
         for (int d = 0; d < q.m; d++) {
-            vec3 dir = q.rays ? ray_dir : (d == 0 ? vec3(q.d0x, q.d0y, q.d0z) : d == 1 ? vec3(q.d1x, q.d1y, q.d1z) : vec3(q.d2x, q.d2y, q.d2z));
-            const bool admitted = active && admit_ray(org, dir, tmin, tmax);          // an inadmissible ray and an inactive point take no cell step
-            const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
-            const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));
-            const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
-            const vec3 ta = (gmin - org) * inv_dir, tb = (gmax - org) * inv_dir;
-            const vec3 t0 = min(ta, tb), t1 = max(ta, tb);
-            const float tstart = detail::fmax2(detail::fmax2(t0.x, detail::fmax2(t0.y, t0.z)), tmin);
-            const float tend = detail::fmin2(detail::fmin2(t1.x, detail::fmin2(t1.y, t1.z)), tmax);
-            const Ray ray(org, tmin, dir, tmax);          // the window every triangle is tested against
-
-            hx::Accum acc;
-            acc.init(tmax);
-            if (admitted && !(tstart > tend)) {
-                hx::Page<kPage> page;
-                page.init(kPage);
-                const vec3 fv = (tstart * dir + org - gmin) * ginv;
-                int vx = min(max(hx::f2i(fv.x), 0), a.dims_x - 1);
-                int vy = min(max(hx::f2i(fv.y), 0), a.dims_y - 1);
-                int vz = min(max(hx::f2i(fv.z), 0), a.dims_z - 1);
-
-                auto walk = [&](uint32_t w, int x, int y, int z) -> uint32_t {   // sub-levels of the voxel map
-                    int depth = 0;
-                    while (w & 3u) {
-                        const int l = int(w & 3u);
-                        depth += l;
-                        const int s = a.shift - depth, m = (1 << l) - 1;
-                        w = a.entries[(w >> 2) + ((x >> s) & m) + ((((y >> s) & m) + (((z >> s) & m) << l)) << l)];
-                    }
-                    return w;
-                };
-                auto top_index = [&](int x, int y, int z) -> int { return (x >> a.shift) + a.top_x * ((y >> a.shift) + a.top_y * (z >> a.shift)); };
-
-                int top_idx = top_index(vx, vy, vz);
-                uint32_t topw = a.entries[top_idx];
-                CellBox c = load_cell(a.cells, walk(topw, vx, vy, vz) >> 2, SMALL);
-                CellBox nc = c;
-                float texit = 0.0f;
-                bool outside = false, again = false;
-
-                for (;;) {
-                    if (!again) {
-                        n_cells++;
-                        const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
-                        const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * csize + gmin - org) * walk_inv;
-                        texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
-                        const vec3 ev = (texit * dir + org - gmin) * ginv;
-                        const int nx = texit == tcell.x ? cx + (px ? 0 : -1) : hx::f2i(ev.x);
-                        const int ny = texit == tcell.y ? cy + (py ? 0 : -1) : hx::f2i(ev.y);
-                        const int nz = texit == tcell.z ? cz + (pz ? 0 : -1) : hx::f2i(ev.z);
-                        vx = px ? max(nx, vx) : min(nx, vx);
-                        vy = py ? max(ny, vy) : min(ny, vy);
-                        vz = pz ? max(nz, vz) : min(nz, vz);
-                        outside = (vx < 0) | (vx >= a.dims_x) | (vy < 0) | (vy >= a.dims_y) | (vz < 0) | (vz >= a.dims_z);
-                    }
-                    // first reference of this cell and the next cell's top entry: two independent loads in flight
-                    const int begin = c.begin;
-                    const bool nonempty = begin >= 0 && begin < c.end;
-                    int cur = nonempty ? begin : 0;
-                    int ref = a.refs[cur];
-                    cur++;
-                    if (!nonempty) ref = -1;
-                    if (!again) {
-                        // (a voxel outside the grid keeps the current top-level entry; the sub-level indices are masked, so its walk stays inside that entry's blocks and is dropped)
-                        const int ntop = outside ? top_idx : top_index(vx, vy, vz);
-                        if (ntop != top_idx) { topw = a.entries[ntop]; top_idx = ntop; }
-                        // next cell: walk + load, overlapping the triangle tests below
-                        nc = load_cell(a.cells, walk(topw, vx, vy, vz) >> 2, SMALL);
-                    }
-                    while (ref >= 0) {
-                        const int next = cur < c.end ? a.refs[cur] : -1;
-                        cur++;
-                        float t; bool entering;
-                        n_tests++;
-                        if (hx::crosses(load_tri(a.tris, ref), ray, t, entering)) page.insert(t, (uint32_t(ref) << 1) | (entering ? 1u : 0u));
-                        ref = next;
-                    }
-                    again = page.full() && (page.last_t <= texit || outside);
-                    if (again) { page.flush(acc); n_flushes++; continue; }          // and this cell's list once more
-                    if (outside) break;
-                    c = nc;
-                }
-                if (!page.empty()) { page.flush(acc); n_flushes++; }
+            const vec3 dir = q.rays ? ray_dir : (d == 0 ? vec3(q.d0x, q.d0y, q.d0z) : d == 1 ? vec3(q.d1x, q.d1y, q.d1z) : vec3(q.d2x, q.d2y, q.d2z));
+            Hit rec(0, tmax, 0.0f, 0.0f);          // an inactive point takes no cell step
+            if (active) {
+                hx::Counts n;
+                const RayGrid g(a, small_cells);
+                rec = hx::crossings_walk<kPage>(g, Ray(org, tmin, dir, tmax), kPage, n);
+                n_cells += n.cells; n_tests += n.tests; n_flushes += n.flushes;
             }
-            const Hit rec = acc.record();
             votes += hx::vote(rec, q.winding != 0);
             if (q.records) nt_store4(q.records + size_t(id) * size_t(q.m) + size_t(d), __int_as_float(rec.id), rec.t, rec.u, rec.v);
         }
         if (q.inside) __builtin_nontemporal_store(active ? (2 * votes > q.m ? 1 : 0) : -1, q.inside + id);
     }
-    if (q.counters) {   // batch totals: the wavefront's sums, one vector atomic each
-        const int items = wave_sum(live ? 1 : 0);
-        // a lane's count fits 31 bits, 64 of them need not
-        unsigned long long cells = (unsigned long long)(unsigned)n_cells, tests = (unsigned long long)(unsigned)n_tests, flushes = (unsigned long long)(unsigned)n_flushes;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            cells += (unsigned long long)__shfl_xor((long long)cells, d, 64);
-            tests += (unsigned long long)__shfl_xor((long long)tests, d, 64);
-            flushes += (unsigned long long)__shfl_xor((long long)flushes, d, 64);
-        }
-        if (lane == 0) {
-            atomicAdd(q.counters + 0, (unsigned long long)items);
-            atomicAdd(q.counters + 1, cells);
-            atomicAdd(q.counters + 2, tests);
-            atomicAdd(q.counters + 3, flushes);
-        }
-    }
+    if (q.counters) add_batch_counters(q.counters, lane, live ? 1 : 0, n_cells, n_tests, n_flushes);
 }
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // what the three entry points check and do; q holds the source and n
 int launch(hagrid_ctx* ctx, const char* who, bool ray_form, const hagrid_grid* grid, const void* tris, CrossArgs q, const float* dirs, int num_dirs, void* inside, void* records,
@@ -255,17 +150,10 @@ extern "C" int hagrid_points_inside(hagrid_ctx* ctx, const hagrid_grid* grid, co
 extern "C" int hagrid_inside_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, const float* dirs, int num_dirs,
                                      void* inside, void* records, void* counters, uint32_t flags) {
     if (!ctx) return HAGRID_EINVAL;
-    if (!origin || !size || !n) HG_FAIL(ctx, HAGRID_EINVAL, "inside_lattice: null origin, size or n");
-    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "inside_lattice: the lattice needs at least one voxel along every axis");
-    const long long plane = (long long)n[0] * n[1];                 // each factor is below 2^31: fits 62 bits
-    if (plane > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, "inside_lattice: more than 2^31 - 1 voxels");
-    const long long total = plane * n[2];                           // below 2^62 now
-    if (total > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, "inside_lattice: more than 2^31 - 1 voxels");
-    for (int i = 0; i < 3; i++)
-        if (!(size[i] > 0.0f) || !(size[i] <= 3.4028234663852886e38f) || !(origin[i] >= -3.4028234663852886e38f && origin[i] <= 3.4028234663852886e38f))
-            HG_FAIL(ctx, HAGRID_EINVAL, "inside_lattice: the voxel size must be positive and finite, the origin finite");
+    int total = 0;
+    HG_TRY(check_lattice(ctx, "inside_lattice", origin, size, n, &total));
     CrossArgs q = {};
-    q.n = int(total);
+    q.n = total;
     q.ox = origin[0]; q.oy = origin[1]; q.oz = origin[2];
     q.sx = size[0]; q.sy = size[1]; q.sz = size[2];
     q.nx = n[0]; q.ny = n[1];

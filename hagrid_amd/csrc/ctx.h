@@ -247,6 +247,9 @@ int read_back(hagrid_ctx* ctx, const void* dptr, void* hptr, size_t bytes);
 
 inline int grid_blocks(long long n, int block) { return (int)((n + block - 1) / block); }
 
+// is p a multiple of n (a power of two)?  a null pointer is
+inline bool aligned(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
 // Status words for one look-back scan of `tiles` tiles with `words_per_tile` words each, and a fresh epoch.
 unsigned long long* lookback_state(hagrid_ctx* ctx, int tiles, int words_per_tile, unsigned* epoch);
 

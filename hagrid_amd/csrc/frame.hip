@@ -75,7 +75,6 @@ __global__ void __launch_bounds__(kBlock) frame_occlusion_kernel(const float4* _
     else bgra[i] = hf::shade_occlusion(id, counts[i], samples);
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 // the sections of a frame workspace (include/hagrid_amd.h: hagrid_render_frame), offsets in bytes

@@ -25,37 +25,8 @@ namespace ho = hagrid::overlap;
 
 namespace {
 
-struct DevGrid {
-    hc::GridConsts c;
-    ho::Clip clip;
-    const uint32_t* __restrict__ entries;
-    const void* __restrict__ cells;
-    const int* __restrict__ refs;
-    const float4* __restrict__ tris;
-    int small;
-
-    __device__ __forceinline__ uint32_t word(uint32_t i) const { return entries[i]; }
-    __device__ __forceinline__ hc::CellRec cell(uint32_t i) const {
-        CellBox b;
-        if (small) { b = load_cell_box<true>(cells, i); b.end = 0x7fffffff; }
-        else       { b = load_cell_box<false>(cells, i); }
-        hc::CellRec r;
-        r.lx = b.lx; r.ly = b.ly; r.lz = b.lz; r.hx = b.hx; r.hy = b.hy; r.hz = b.hz; r.begin = b.begin; r.end = b.end;
-        return r;
-    }
-    __device__ __forceinline__ int ref(int i) const { return refs[i]; }
-    __device__ __forceinline__ Tri tri(int id) const { return load_tri(tris, id); }
-};
-
-// the descent's stack in LDS: column `lane` of two [level][64] arrays
-struct LdsStack {
-    uint32_t* w_;
-    uint32_t* i_;
-    __device__ __forceinline__ void set(int level, uint32_t w, uint32_t i) { w_[level * 64] = w; i_[level * 64] = i; }
-    __device__ __forceinline__ void set_i(int level, uint32_t i) { i_[level * 64] = i; }
-    __device__ __forceinline__ uint32_t w(int level) const { return w_[level * 64]; }
-    __device__ __forceinline__ uint32_t i(int level) const { return i_[level * 64]; }
-};
+// the accessor of overlap.h: the grid and the clip box
+struct OverlapGrid : DevGrid { ho::Clip clip; };
 
 struct OverlapArgs {
     const float4* __restrict__ boxes;        // null: the lattice form
@@ -67,7 +38,7 @@ struct OverlapArgs {
     int nx, ny;                              // lattice: voxels along x and y (x fastest)
 };
 
-__global__ void __launch_bounds__(64) overlap_boxes_kernel(const DevGrid g, const OverlapArgs a) {
+__global__ void __launch_bounds__(64) overlap_boxes_kernel(const OverlapGrid g, const OverlapArgs a) {
     __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
     const int lane = threadIdx.x;
     const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
@@ -104,26 +75,8 @@ __global__ void __launch_bounds__(64) overlap_boxes_kernel(const DevGrid g, cons
         }
         if (a.counts) __builtin_nontemporal_store(list.count(), a.counts + id);
     }
-    if (a.counters) {   // batch totals: the wavefront's sums, one vector atomic each
-        const int boxes = wave_sum(live ? 1 : 0);
-        // a lane's count fits 31 bits, 64 of them need not
-        unsigned long long cells = (unsigned long long)(unsigned)cnt.cells, sats = (unsigned long long)(unsigned)cnt.sats, pruned = (unsigned long long)(unsigned)cnt.pruned;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            cells += (unsigned long long)__shfl_xor((long long)cells, d, 64);
-            sats += (unsigned long long)__shfl_xor((long long)sats, d, 64);
-            pruned += (unsigned long long)__shfl_xor((long long)pruned, d, 64);
-        }
-        if (lane == 0) {
-            atomicAdd(a.counters + 0, (unsigned long long)boxes);
-            atomicAdd(a.counters + 1, cells);
-            atomicAdd(a.counters + 2, sats);
-            atomicAdd(a.counters + 3, pruned);
-        }
-    }
+    if (a.counters) add_batch_counters(a.counters, lane, live ? 1 : 0, cnt.cells, cnt.sats, cnt.pruned);
 }
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // what both entry points check and do; boxes null: the lattice form (a holds its constants and n)
 int launch(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid, const void* tris, OverlapArgs a, void* ids, void* counts, void* counters, uint32_t flags) {
@@ -142,15 +95,9 @@ int launch(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid, const void
     // k = 4 and k = 8 store their ids 16 bytes at a time, every other k one id at a time
     if (!aligned(ids, (a.k == 4 || a.k == 8) ? 16 : 4)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the ids must be 16-byte aligned for k = 4 and k = 8, 4-byte aligned otherwise").c_str());
     HG_HIP(ctx, hipSetDevice(ctx->device));
-    DevGrid g;
-    g.c.set(ivec3(grid->dims[0], grid->dims[1], grid->dims[2]), grid->shift, vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2]),
-            vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]));
-    g.clip.set(vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2]), vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]));
-    g.entries = static_cast<const uint32_t*>(grid->entries);
-    g.cells = grid->small_cells ? grid->small_cells : grid->cells;
-    g.refs = static_cast<const int*>(grid->ref_ids);
-    g.tris = static_cast<const float4*>(tris);
-    g.small = grid->small_cells != nullptr ? 1 : 0;
+    OverlapGrid g;
+    g.set(grid, tris);
+    g.clip.set(g.c.lo, g.c.hi);
     a.ids = static_cast<int*>(ids);
     a.counts = static_cast<int*>(counts);
     a.counters = static_cast<unsigned long long*>(counters);
@@ -178,18 +125,11 @@ extern "C" int hagrid_overlap_boxes(hagrid_ctx* ctx, const hagrid_grid* grid, co
 extern "C" int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, int k,
                                       void* ids, void* counts, void* counters, uint32_t flags) {
     if (!ctx) return HAGRID_EINVAL;
-    if (!origin || !size || !n) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: null origin, size or n");
-    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: the lattice needs at least one voxel along every axis");
-    const long long plane = (long long)n[0] * n[1];                 // each factor is below 2^31: fits 62 bits
-    if (plane > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: more than 2^31 - 1 voxels");
-    const long long total = plane * n[2];                           // below 2^62 now
-    if (total > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: more than 2^31 - 1 voxels");
-    for (int i = 0; i < 3; i++)
-        if (!(size[i] > 0.0f) || !(size[i] <= 3.4028234663852886e38f) || !(origin[i] >= -3.4028234663852886e38f && origin[i] <= 3.4028234663852886e38f))
-            HG_FAIL(ctx, HAGRID_EINVAL, "overlap_lattice: the voxel size must be positive and finite, the origin finite");
+    int total = 0;
+    HG_TRY(check_lattice(ctx, "overlap_lattice", origin, size, n, &total));
     OverlapArgs a = {};
     a.boxes = nullptr;
-    a.n = int(total); a.k = k;
+    a.n = total; a.k = k;
     a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
     a.sx = size[0]; a.sy = size[1]; a.sz = size[2];
     a.nx = n[0]; a.ny = n[1];

@@ -2,12 +2,16 @@
 // packets (lane <-> ray assignment), small device helpers, and the host entry points each unit offers the others.
 //   traverse.hip    the C ABI (setup_traversal, traverse_grid[_ex|_stats], options) and the traversal-image kernels (trav_kernels.h)
 //   trav_plain.hip  the kernels that walk the construction format: the reference-shaped one (statistics, Hit.id = steps) and v2
+//   trav_multi.hip, crossings.hip, closest.hip, overlap.hip   the queries over the construction format (DevGrid below)
+//   hagrid/cell_walk.h  the ray walk over the construction format, written once for kernels and host programs
 //   ray_order.hip   row-length detection of image-ordered batches and the counting sort of unordered ones (ray binning)
 //   kat/kat.hip     known-answer hooks and timed diagnostic instantiations: a separate library, libhagrid_amd_kat.so (tests, dev tools)
 #pragma once
 
 #include "ctx.h"
 
+#include "hagrid/cell_walk.h"
+#include "hagrid/closest.h"
 #include "hagrid/grid.h"
 #include "hagrid/prims.h"
 #include "hagrid/ray.h"
@@ -64,11 +68,11 @@ struct TraverseArgs {
     float inv_x, inv_y, inv_z;    // 1 / cell size (as dims / extents)
 };
 
-struct CellBox { int lx, ly, lz, hx, hy, hz, begin, end; };
+using walk::CellRec;
 
 template <bool SMALL>
-__device__ __forceinline__ CellBox load_cell_box(const void* __restrict__ cells, uint32_t index) {
-    CellBox c;
+__device__ __forceinline__ CellRec load_cell_box(const void* __restrict__ cells, uint32_t index) {
+    CellRec c;
     if (SMALL) {
         const uint4 w = reinterpret_cast<const uint4*>(cells)[index];
         c.lx = int(w.x & 0xffffu); c.ly = int(w.x >> 16); c.lz = int(w.y & 0xffffu);
@@ -83,11 +87,88 @@ __device__ __forceinline__ CellBox load_cell_box(const void* __restrict__ cells,
     return c;
 }
 
+// a cell of either format, the format a run-time value; a SmallCell's list ends with its sentinel, so its `end` is no bound
+__device__ __forceinline__ CellRec load_cell(const void* __restrict__ cells, uint32_t index, bool small) {
+    CellRec c;
+    if (small) { c = load_cell_box<true>(cells, index); c.end = 0x7fffffff; }
+    else       { c = load_cell_box<false>(cells, index); }
+    return c;
+}
+
 __device__ __forceinline__ Tri load_tri(const float4* __restrict__ tris, int ref) {
     const float4* p = tris + 3 * size_t(ref);
     const float4 a = p[0], b = p[1], c = p[2];
     return Tri(vec3(a.x, a.y, a.z), a.w, vec3(b.x, b.y, b.z), b.w, vec3(c.x, c.y, c.z), c.w);
 }
+
+// The construction format behind plain device loads: the grid accessor of closest.h and overlap.h, and (RayGrid) of hagrid/cell_walk.h.  The cell format is a
+// run-time value, uniform over a launch (one kernel per query: the product library's kernel budget, tests/test_abi.py).
+struct DevGrid {
+    closest::GridConsts c;
+    const uint32_t* __restrict__ entries;
+    const void* __restrict__ cells;
+    const int* __restrict__ refs;
+    const float4* __restrict__ tris;
+    int small;
+
+    __device__ __forceinline__ uint32_t word(uint32_t i) const { return entries[i]; }
+    __device__ __forceinline__ CellRec cell(uint32_t i) const { return load_cell(cells, i, small != 0); }
+    __device__ __forceinline__ int ref(int i) const { return refs[i]; }
+    __device__ __forceinline__ Tri tri(int id) const { return load_tri(tris, id); }
+
+    // host: the accessor of a grid as the query entry points receive it
+    void set(const hagrid_grid* grid, const void* tris_) {
+        c.set(ivec3(grid->dims[0], grid->dims[1], grid->dims[2]), grid->shift, vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2]),
+              vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]));
+        entries = static_cast<const uint32_t*>(grid->entries);
+        cells = grid->small_cells ? grid->small_cells : grid->cells;
+        refs = static_cast<const int*>(grid->ref_ids);
+        tris = static_cast<const float4*>(tris_);
+        small = grid->small_cells != nullptr ? 1 : 0;
+    }
+};
+
+// setup_traversal's constants as the argument block carries them (make_args computed them)
+__device__ __forceinline__ walk::WalkConsts walk_consts(const TraverseArgs& a) {
+    walk::WalkConsts c;
+    c.top = ivec3(a.top_x, a.top_y, 0); c.dims = ivec3(a.dims_x, a.dims_y, a.dims_z); c.shift = a.shift;
+    c.lo = vec3(a.min_x, a.min_y, a.min_z); c.hi = vec3(a.max_x, a.max_y, a.max_z);
+    c.cell_size = vec3(a.cs_x, a.cs_y, a.cs_z); c.inv = vec3(a.inv_x, a.inv_y, a.inv_z);
+    return c;
+}
+
+// The top-level word a ray's accessor keeps while the ray stays inside one top-level cell: a look-up in the same cell starts at its sub-levels.
+struct TopWord {
+    int index = -1;
+    uint32_t word = 0;
+    template <typename G>
+    __device__ __forceinline__ uint32_t at(const G& g, int i) {
+        if (i != index) { word = g.word(uint32_t(i)); index = i; }
+        return word;
+    }
+};
+
+// the accessor of hagrid/cell_walk.h for one ray of the multi-hit and crossing kernels
+struct RayGrid : DevGrid {
+    mutable TopWord top;
+    __device__ __forceinline__ RayGrid(const TraverseArgs& a, int small_) {
+        static_cast<walk::WalkConsts&>(c) = walk_consts(a); c.eps = 0.0f;
+        entries = a.entries; cells = a.cells; refs = a.refs; tris = a.tris; small = small_;
+    }
+    __device__ __forceinline__ CellRec cell_at(int x, int y, int z) const {
+        return cell(walk::descend(*this, top.at(*this, walk::top_index(c, x, y, z)), x, y, z) >> 2);
+    }
+};
+
+// the stack of closest.h's and overlap.h's descent in LDS: column `lane` of two [level][64] arrays
+struct LdsStack {
+    uint32_t* w_;
+    uint32_t* i_;
+    __device__ __forceinline__ void set(int level, uint32_t w, uint32_t i) { w_[level * 64] = w; i_[level * 64] = i; }
+    __device__ __forceinline__ void set_i(int level, uint32_t i) { i_[level * 64] = i; }
+    __device__ __forceinline__ uint32_t w(int level) const { return w_[level * 64]; }
+    __device__ __forceinline__ uint32_t i(int level) const { return i_[level * 64]; }
+};
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // streaming (read-once / write-once) accesses for rays and hits: keep them out of the way of the grid in L2
@@ -298,6 +379,21 @@ inline void image_args(const hagrid_ctx* ctx, TraverseArgs& a) {
 // ---- host entry points of the translation units ------------------------------------------------------------------------------
 // traverse.hip: the argument block of a grid (setup_traversal's constants, traverse.cu:97-109); tris / rays / hits may be null when num_rays == 0
 int make_args(hagrid_ctx* ctx, const hagrid_grid* g, const void* tris, const void* rays, void* hits, int num_rays, TraverseArgs& a);
+// the lattice arguments of hagrid_overlap_lattice and hagrid_inside_lattice (`who`: the entry point's name in the message); *total: the number of voxels
+inline int check_lattice(hagrid_ctx* ctx, const char* who, const float* origin, const float* size, const int* n, int* total) {
+    const std::string w(who);
+    if (!origin || !size || !n) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null origin, size or n").c_str());
+    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the lattice needs at least one voxel along every axis").c_str());
+    const long long plane = (long long)n[0] * n[1];                 // each factor is below 2^31: fits 62 bits
+    if (plane > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": more than 2^31 - 1 voxels").c_str());
+    const long long voxels = plane * n[2];                          // below 2^62 now
+    if (voxels > 0x7fffffffLL) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": more than 2^31 - 1 voxels").c_str());
+    for (int i = 0; i < 3; i++)
+        if (!(size[i] > 0.0f) || !(size[i] <= 3.4028234663852886e38f) || !(origin[i] >= -3.4028234663852886e38f && origin[i] <= 3.4028234663852886e38f))
+            HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the voxel size must be positive and finite, the origin finite").c_str());
+    *total = int(voxels);
+    return HAGRID_OK;
+}
 // bytes from p to the end of the device allocation that holds it (all bits set if the runtime does not know the pointer)
 size_t buffer_bytes_from(const void* p);
 // trav_plain.hip: 256 threads per block (reference-shaped kernel), one wavefront per block (v2)

@@ -78,6 +78,22 @@ __device__ __forceinline__ int wave_sum(int v) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += (unsigned long long)__shfl_xor((long long)v, d, 64);
+    return v;
+}
+/// Batch totals of a query kernel (closest, overlap, crossings): the wavefront's sums of four per-lane counts, one vector atomic each from lane 0.
+/// A lane's count fits 31 bits, 64 of them need not: the sums are 64-bit.
+__device__ __forceinline__ void add_batch_counters(unsigned long long* counters, int lane, int a, int b, int c, int d) {
+    const unsigned long long sa = wave_sum_u64((unsigned)a), sb = wave_sum_u64((unsigned)b), sc = wave_sum_u64((unsigned)c), sd = wave_sum_u64((unsigned)d);
+    if (lane == 0) {
+        atomicAdd(counters + 0, sa);
+        atomicAdd(counters + 1, sb);
+        atomicAdd(counters + 2, sc);
+        atomicAdd(counters + 3, sd);
+    }
+}
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) { int o = __shfl_xor(v, d, 64); v = o > v ? o : v; }

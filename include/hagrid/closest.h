@@ -53,6 +53,7 @@
 #ifndef HAGRID_CLOSEST_H
 #define HAGRID_CLOSEST_H
 
+#include "cell_walk.h"
 #include "grid.h"
 #include "prims.h"
 #include "vec.h"
@@ -132,27 +133,21 @@ HOST DEVICE inline void brute_force(F tri_at, int num_tris, const vec3& p, float
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------------
 
-struct GridConsts {
-    ivec3 top, dims;        ///< top-level and virtual resolution
-    int shift;
-    vec3 lo, cs, inv;       ///< grid box minimum, cell size, 1 / cell size (as dims / extents)
+/// walk::WalkConsts set from the TOP-LEVEL resolution (the same operations on the same numbers), and the margin, which only the box queries read
+struct GridConsts : walk::WalkConsts {
     float eps;              ///< the absolute margin
-    /// the constants hagrid_amd/csrc/traverse.hip make_args computes, and the margin
-    HOST DEVICE void set(const ivec3& top_, int shift_, const vec3& lo_, const vec3& hi) {
-        top = top_; shift = shift_; dims = top_ << shift_; lo = lo_;
-        const vec3 ext = hi - lo_;
-        inv = vec3(dims) / ext; cs = ext / vec3(dims);
-        eps = abs_margin(lo_, hi);
+    HOST DEVICE void set(const ivec3& top_, int shift_, const vec3& lo_, const vec3& hi_) {
+        walk::WalkConsts::set(top_ << shift_, shift_, lo_, hi_);
+        eps = abs_margin(lo_, hi_);
     }
-    HOST DEVICE static float abs_margin(const vec3& lo_, const vec3& hi) {
+    HOST DEVICE static float abs_margin(const vec3& lo_, const vec3& hi_) {
         float m = detail::fabs1(lo_.x);
         m = max(m, detail::fabs1(lo_.y)); m = max(m, detail::fabs1(lo_.z));
-        m = max(m, detail::fabs1(hi.x)); m = max(m, detail::fabs1(hi.y)); m = max(m, detail::fabs1(hi.z));
+        m = max(m, detail::fabs1(hi_.x)); m = max(m, detail::fabs1(hi_.y)); m = max(m, detail::fabs1(hi_.z));
         return m * 1.52587890625e-05f;      // 2^-16
     }
 };
-
-struct CellRec { int lx, ly, lz, hx, hy, hz, begin, end; };   ///< end: past-the-end reference, INT_MAX for a SmallCell (sentinel-terminated); begin < 0: empty
+using walk::CellRec;         ///< here `end` bounds the list: INT_MAX for a SmallCell (sentinel-terminated); begin < 0: empty
 struct Counts { int cells, tris, pruned; };
 
 /// a distance reduced by the absolute margin, not below 0
@@ -167,7 +162,7 @@ HOST DEVICE inline float axis_gap(float p, int lc, int hc, float cs, float lo, f
     return shrink(a > b ? a : b, eps);
 }
 HOST DEVICE inline float box_lower2(const GridConsts& c, const vec3& p, int lx, int ly, int lz, int hx, int hy, int hz) {
-    const float dx = axis_gap(p.x, lx, hx, c.cs.x, c.lo.x, c.eps), dy = axis_gap(p.y, ly, hy, c.cs.y, c.lo.y, c.eps), dz = axis_gap(p.z, lz, hz, c.cs.z, c.lo.z, c.eps);
+    const float dx = axis_gap(p.x, lx, hx, c.cell_size.x, c.lo.x, c.eps), dy = axis_gap(p.y, ly, hy, c.cell_size.y, c.lo.y, c.eps), dz = axis_gap(p.z, lz, hz, c.cell_size.z, c.lo.z, c.eps);
     return dx * dx + dy * dy + dz * dz;
 }
 
@@ -274,12 +269,12 @@ HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r,
     {
         const float big = 3.4028234663852886e38f;
         float m = big;
-        if (c0.lx > 0)        m = min(m, p.x - face(c0.lx, c.cs.x, c.lo.x));
-        if (c0.hx < c.dims.x) m = min(m, face(c0.hx, c.cs.x, c.lo.x) - p.x);
-        if (c0.ly > 0)        m = min(m, p.y - face(c0.ly, c.cs.y, c.lo.y));
-        if (c0.hy < c.dims.y) m = min(m, face(c0.hy, c.cs.y, c.lo.y) - p.y);
-        if (c0.lz > 0)        m = min(m, p.z - face(c0.lz, c.cs.z, c.lo.z));
-        if (c0.hz < c.dims.z) m = min(m, face(c0.hz, c.cs.z, c.lo.z) - p.z);
+        if (c0.lx > 0)        m = min(m, p.x - face(c0.lx, c.cell_size.x, c.lo.x));
+        if (c0.hx < c.dims.x) m = min(m, face(c0.hx, c.cell_size.x, c.lo.x) - p.x);
+        if (c0.ly > 0)        m = min(m, p.y - face(c0.ly, c.cell_size.y, c.lo.y));
+        if (c0.hy < c.dims.y) m = min(m, face(c0.hy, c.cell_size.y, c.lo.y) - p.y);
+        if (c0.lz > 0)        m = min(m, p.z - face(c0.lz, c.cell_size.z, c.lo.z));
+        if (c0.hz < c.dims.z) m = min(m, face(c0.hz, c.cell_size.z, c.lo.z) - p.z);
         if (m == big) return;                           // the cell is the whole grid
         const float ms = shrink(m, c.eps);
         if (beyond(ms * ms, b.d2)) return;
@@ -292,12 +287,12 @@ HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r,
         // lower bound of ring k: the nearest face of the cube of rings 0 .. k-1 that still has grid behind it
         const float big = 3.4028234663852886e38f;
         float m = big;
-        if (tx - k + 1 > 0)   m = min(m, p.x - face((tx - k + 1) << c.shift, c.cs.x, c.lo.x));
-        if (tx + k < c.top.x) m = min(m, face((tx + k) << c.shift, c.cs.x, c.lo.x) - p.x);
-        if (ty - k + 1 > 0)   m = min(m, p.y - face((ty - k + 1) << c.shift, c.cs.y, c.lo.y));
-        if (ty + k < c.top.y) m = min(m, face((ty + k) << c.shift, c.cs.y, c.lo.y) - p.y);
-        if (tz - k + 1 > 0)   m = min(m, p.z - face((tz - k + 1) << c.shift, c.cs.z, c.lo.z));
-        if (tz + k < c.top.z) m = min(m, face((tz + k) << c.shift, c.cs.z, c.lo.z) - p.z);
+        if (tx - k + 1 > 0)   m = min(m, p.x - face((tx - k + 1) << c.shift, c.cell_size.x, c.lo.x));
+        if (tx + k < c.top.x) m = min(m, face((tx + k) << c.shift, c.cell_size.x, c.lo.x) - p.x);
+        if (ty - k + 1 > 0)   m = min(m, p.y - face((ty - k + 1) << c.shift, c.cell_size.y, c.lo.y));
+        if (ty + k < c.top.y) m = min(m, face((ty + k) << c.shift, c.cell_size.y, c.lo.y) - p.y);
+        if (tz - k + 1 > 0)   m = min(m, p.z - face((tz - k + 1) << c.shift, c.cell_size.z, c.lo.z));
+        if (tz + k < c.top.z) m = min(m, face((tz + k) << c.shift, c.cell_size.z, c.lo.z) - p.z);
         if (m == big) break;                            // the rings have left the grid
         const float ms = shrink(m, c.eps);
         if (beyond(ms * ms, b.d2)) break;

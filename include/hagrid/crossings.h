@@ -71,6 +71,7 @@
 #ifndef HAGRID_CROSSINGS_H
 #define HAGRID_CROSSINGS_H
 
+#include "cell_walk.h"
 #include "grid.h"
 #include "multi_hit.h"
 #include "prims.h"
@@ -193,99 +194,48 @@ HOST DEVICE inline Hit crossings_brute_force(F tri_at, int num_tris, const Ray& 
     return acc.record();
 }
 
-/// float -> int as the gfx950 conversion does it (v_cvt_i32_f32: truncation, saturating, NaN -> 0).  On the host a plain cast of a value that does not fit
-/// is undefined (x86 gives INT_MIN), and the walk does convert such values: the voxel coordinate of an exit point far outside the grid.  Written out, so that
-/// the host walk and the kernel take the same steps on every ray.
-HOST DEVICE inline int f2i(float f) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return int(f);
-#else
-    if (!(f == f)) return 0;
-    if (f >= 2147483648.0f) return 2147483647;
-    if (f <= -2147483648.0f) return -2147483647 - 1;
-    return int(f);
-#endif
-}
-
 /// per-ray counts of the walk
 struct Counts { int cells, tests, flushes; };
 
-/// setup_traversal's constants
-struct WalkConsts {
-    ivec3 top, dims;
-    int shift;
-    vec3 lo, hi, cell_size, inv;
-    HOST DEVICE void set(const ivec3& dims_, int shift_, const vec3& lo_, const vec3& hi_) {
-        dims = dims_; shift = shift_; lo = lo_; hi = hi_;
-        top = ivec3(dims.x >> shift, dims.y >> shift, dims.z >> shift);
-        const vec3 ext = hi - lo;
-        inv = vec3(dims) / ext;
-        cell_size = ext / vec3(dims);
-    }
-};
+using walk::WalkConsts;
+using walk::CellRec;
 
-struct CellRec { int lx, ly, lz, hx, hy, hz, begin, end; };
-
-/// The walk of trav_multi.hip with pages: the record of one ray over the grid g, equal to crossings_brute_force over all triangles.
-/// G: c (WalkConsts), small (SmallCell lists end with their sentinel), cell_at(vx, vy, vz) -> CellRec, ref(i), tri(id).  P: the page capacity.
-/// The device kernel is this function with the next cell's loads issued early; tests/cpp/crossings_host.cpp runs it as it stands.
+/// What the crossing walk does with a cell (the visitor of walk::walk_cells): every reference of the list against the ray's own window into the page; when
+/// the page is full and its last entry is not beyond the cell's exit (or the ray leaves the grid) the page is flushed and the SAME list tested once more.
 template <int PMAX, typename G>
-HOST DEVICE inline Hit crossings_walk(const G& g, const Ray& ray_in, int P, Counts& n) {
-    const WalkConsts& k = g.c;
-    const vec3 org = ray_in.org;
-    vec3 dir = ray_in.dir;
-    const float tmin = ray_in.tmin, tmax = ray_in.tmax;
-    const bool admitted = admit_ray(org, dir, tmin, tmax);
-    const Ray ray(org, tmin, dir, tmax);
-    const vec3 inv_dir(safe_rcp(dir.x), safe_rcp(dir.y), safe_rcp(dir.z));
-    const vec3 walk_inv(walk_rcp(dir.x), walk_rcp(dir.y), walk_rcp(dir.z));
-    const bool px = dir.x >= 0.0f, py = dir.y >= 0.0f, pz = dir.z >= 0.0f;
-    const vec3 ta = (k.lo - org) * inv_dir, tb = (k.hi - org) * inv_dir;
-    const vec3 t0 = min(ta, tb), t1 = max(ta, tb);
-    const float tstart = detail::fmax2(detail::fmax2(t0.x, detail::fmax2(t0.y, t0.z)), tmin);
-    const float tend = detail::fmin2(detail::fmin2(t1.x, detail::fmin2(t1.y, t1.z)), tmax);
-
-    Accum acc;
-    acc.init(tmax);
-    n.cells = 0; n.tests = 0; n.flushes = 0;
-    if (!(admitted && !(tstart > tend))) return acc.record();
-
-    Page<PMAX> page;
-    page.init(P);
-    const vec3 fv = (tstart * dir + org - k.lo) * k.inv;
-    int vx = min(max(f2i(fv.x), 0), k.dims.x - 1);
-    int vy = min(max(f2i(fv.y), 0), k.dims.y - 1);
-    int vz = min(max(f2i(fv.z), 0), k.dims.z - 1);
-    for (;;) {
-        const CellRec c = g.cell_at(vx, vy, vz);
+struct PageVisitor {
+    const G& g; const Ray& ray; Page<PMAX>& page; Accum& acc; Counts& n;
+    HOST DEVICE bool operator()(const walk::RefList<G>& list, float texit, bool outside) {
         n.cells++;
-        const int cx = px ? c.hx : c.lx, cy = py ? c.hy : c.ly, cz = pz ? c.hz : c.lz;
-        const vec3 tcell = (vec3(float(cx), float(cy), float(cz)) * k.cell_size + k.lo - org) * walk_inv;
-        const float texit = detail::fmin2(tcell.x, detail::fmin2(tcell.y, tcell.z));
-        const vec3 ev = (texit * dir + org - k.lo) * k.inv;
-        const int nx = texit == tcell.x ? cx + (px ? 0 : -1) : f2i(ev.x);
-        const int ny = texit == tcell.y ? cy + (py ? 0 : -1) : f2i(ev.y);
-        const int nz = texit == tcell.z ? cz + (pz ? 0 : -1) : f2i(ev.z);
-        vx = px ? max(nx, vx) : min(nx, vx);
-        vy = py ? max(ny, vy) : min(ny, vy);
-        vz = pz ? max(nz, vz) : min(nz, vz);
-        const bool outside = vx < 0 || vx >= k.dims.x || vy < 0 || vy >= k.dims.y || vz < 0 || vz >= k.dims.z;
         for (;;) {
-            if (g.small ? c.begin >= 0 : c.begin < c.end) {
-                for (int cur = c.begin; g.small || cur < c.end; cur++) {
-                    const int ref = g.ref(cur);
-                    if (ref < 0) break;
-                    float t; bool entering;
-                    n.tests++;
-                    if (crosses(g.tri(ref), ray, t, entering)) page.insert(t, (uint32_t(ref) << 1) | (entering ? 1u : 0u));
-                }
+            walk::RefList<G> l = list;
+            while (!l.done()) {
+                const int ref = l.next();
+                float t; bool entering;
+                n.tests++;
+                if (crosses(g.tri(ref), ray, t, entering)) page.insert(t, (uint32_t(ref) << 1) | (entering ? 1u : 0u));
             }
-            if (!(page.full() && (page.last_t <= texit || outside))) break;
+            if (!(page.full() && (page.last_t <= texit || outside))) return false;
             page.flush(acc);          // and this cell's list once more
             n.flushes++;
         }
-        if (outside) break;
     }
+};
+
+/// The walk of cell_walk.h with pages: the record of one ray over the grid g, equal to crossings_brute_force over all triangles.
+/// G: the accessor of cell_walk.h -- c (WalkConsts), small, cell_at(vx, vy, vz) -> CellRec, ref(i) -- and tri(id).  P: the page capacity.  The kernel (crossings.hip) and tests/cpp/crossings_host.cpp both run this function.
+template <int PMAX, typename G>
+HOST DEVICE inline Hit crossings_walk(const G& g, const Ray& ray_in, int P, Counts& n) {
+    const walk::RaySetup s(g.c, ray_in.org, ray_in.dir, ray_in.tmin, ray_in.tmax);
+    Accum acc;
+    acc.init(ray_in.tmax);
+    n.cells = 0; n.tests = 0; n.flushes = 0;
+    if (!s.enters) return acc.record();
+
+    Page<PMAX> page;
+    page.init(P);
+    PageVisitor<PMAX, G> visit{g, s.ray, page, acc, n};
+    walk::walk_cells(g, s, visit);
     if (!page.empty()) { page.flush(acc); n.flushes++; }
     return acc.record();
 }

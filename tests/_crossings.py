@@ -135,7 +135,7 @@ def rec_bits(records) -> np.ndarray:
 
 def build_host(directory, sanitize: bool = False) -> str:
     exe = os.path.join(str(directory), "crossings_host_san" if sanitize else "crossings_host")
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else ["-O2"]
+    flags = M.SANITIZE if sanitize else ["-O2"]
     subprocess.run(["g++", "-std=c++11", *flags, "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
                     os.path.join(ROOT, "tests", "cpp", "crossings_host.cpp"), "-o", exe], check=True)
     return exe

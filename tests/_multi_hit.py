@@ -64,10 +64,13 @@ def hit_histogram(ids: np.ndarray) -> list:
     return np.bincount((ids >= 0).sum(axis=1), minlength=ids.shape[1] + 1).tolist()
 
 
-def build_host(directory) -> str:
-    """tests/cpp/multi_hit_host.cpp with the flags tests/test_frame_cpu.py uses for frame_host.cpp"""
-    exe = os.path.join(str(directory), "multi_hit_host")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
+SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+
+
+def build_host(directory, sanitize: bool = False) -> str:
+    """tests/cpp/multi_hit_host.cpp with the flags tests/test_frame_cpu.py uses for frame_host.cpp; sanitize: a stand-alone binary with the sanitizers of SANITIZE"""
+    exe = os.path.join(str(directory), "multi_hit_host_san" if sanitize else "multi_hit_host")
+    subprocess.run(["g++", "-std=c++11", *(SANITIZE if sanitize else ["-O2"]), "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
                     os.path.join(ROOT, "tests", "cpp", "multi_hit_host.cpp"), "-o", exe], check=True)
     return exe
 

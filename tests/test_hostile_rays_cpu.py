@@ -8,7 +8,9 @@ import pytest
 
 from oracle import oracle as O
 
+import _crossings as X
 import _hostile_rays as H
+import _multi_hit as M
 
 CASES = [(name, grid, compress) for name in H.SCENES for grid in H.GRID_PARAMS for compress in (False, True)]
 IDS = [f"{n}-{g}-{'small' if c else 'cell'}" for n, g, c in CASES]
@@ -238,3 +240,48 @@ def test_skew_rays_need_the_saturating_conversion(name, grid, compress):
     assert O.walk_capped() == (0, -1)
     print("skew rays:", rays.shape[0], "of which", int((bf["id"] >= 0).sum()), "hit; the x86 cast differs from the brute force on", int((~_equal(x86, bf)).sum()))
     assert _equal(dev, bf).all() and (bf["id"] >= 0).sum() > 256
+
+
+@pytest.fixture(scope="module")
+def multi_host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("multi_hit_host")
+    return M.build_host(d), d
+
+
+@functools.lru_cache(maxsize=None)
+def _skew_lists(name, grid):
+    """the 8 nearest intersections of every skew ray by the brute force of tests/_multi_hit.py (the rays depend on the grid's planes, not on the cell format)"""
+    tris, G, _, _ = _case(name, grid, False)
+    rays = H.skew_rays(tris, G)
+    return (rays,) + M.lists_by_brute_force(tris, rays, k=8)
+
+
+@pytest.mark.parametrize("name,grid,compress", CASES, ids=IDS)
+def test_multi_hit_host_walk_on_skew_rays(name, grid, compress, multi_host):
+    """The contract test_skew_rays_need_the_saturating_conversion holds the oracle's device-conversion mode to, for the multi-hit host walk: on H.skew_rays its
+    records are the k nearest of the brute force, id and t bit for bit, k = 1 and 8, both cell formats.  The walk converts the exit voxel through f2i of
+    include/hagrid/cell_walk.h; with the plain cast it had before, the conversion was undefined on these rays and up to 20 of the 768 differed."""
+    tris, G, _, _ = _case(name, grid, compress)
+    rays, ids, t = _skew_lists(name, grid)
+    assert (H.bits(rays) == H.bits(H.skew_rays(tris, G))).all() and rays.shape[0] == 768 and (ids[:, 0] >= 0).sum() > 256
+    exe, d = multi_host
+    for k in (1, 8):
+        got = M.host_walk(exe, d, M.oracle_grid_arrays(G), tris, rays, k)
+        bad = (got["id"] != ids[:, :k]).any(axis=1) | (M.bits(got["t"]) != M.bits(t[:, :k])).any(axis=1)
+        assert not bad.any(), f"k={k}: {bad.sum()} of {bad.size} rays differ, first at {np.flatnonzero(bad)[:5]}"
+
+
+def test_host_walks_under_sanitizers(multi_host, tmp_path):
+    """multi_hit_host and crossings_host as stand-alone binaries with -fsanitize=address,undefined,float-cast-overflow, once each over the skew rays and the
+    catalogue (SmallCells, the default grid): no report, and the records of the plain builds bit for bit"""
+    tris, G, cat, fam = _case("soup", "default", True)
+    arrays = M.oracle_grid_arrays(G)
+    rays = np.concatenate([H.skew_rays(tris, G), cat])
+    plain, d = multi_host
+    want = M.host_walk(plain, d, arrays, tris, rays, 8)
+    got = M.host_walk(M.build_host(tmp_path, sanitize=True), tmp_path, arrays, tris, rays, 8)
+    assert (words(got) == words(want)).all() and (got["id"][:768, 0] >= 0).sum() > 256
+    want = X.host_query(X.build_host(tmp_path), tmp_path, tris, grid=arrays, page=3, rays=rays)
+    got = X.host_query(X.build_host(tmp_path, sanitize=True), tmp_path, tris, grid=arrays, page=3, rays=rays)
+    X.assert_records_equal(got["records"], want["records"], "sanitized crossings walk")
+    assert (got["totals"] == want["totals"]).all() and got["excess"] <= 0

@@ -278,10 +278,17 @@ def test_multi_hit(mem, name, grid, compress, tmp_path):
         dev.close()
 
 
+@pytest.fixture(scope="module")
+def multi_host(tmp_path_factory):
+    d = tmp_path_factory.mktemp("multi_hit_host")
+    return M.build_host(d), d
+
+
 @pytest.mark.parametrize("name,grid,compress", CASES, ids=IDS)
-def test_skew_rays_next_to_voxel_planes(mem, name, grid, compress):
+def test_skew_rays_next_to_voxel_planes(mem, name, grid, compress, multi_host):
     """H.skew_rays, the admissible rays whose walk converts values beyond the range of int ("What remains"): every kernel gives the records of
-    the oracle with the device's conversions (ORC_WALK_DEVICE_F2I) -- which are the brute force's, bit for bit -- embedded among ordinary rays"""
+    the oracle with the device's conversions (ORC_WALK_DEVICE_F2I) -- which are the brute force's, bit for bit -- embedded among ordinary rays; the multi-hit
+    kernel gives the lists of the host walk (the same include/hagrid/cell_walk.h, the conversion written out), every record bit for bit"""
     from hagrid_amd import api
     from oracle import oracle as O
     tris = H.make_tris(name)
@@ -305,9 +312,13 @@ def test_skew_rays_next_to_voxel_planes(mem, name, grid, compress):
                 got = dev.run()
                 bad = (words(got) != words(want)).any(axis=1)
                 assert not bad.any(), (variant, image_width, launch, int(bad.sum()), np.flatnonzero(bad)[:5], got[bad][:2], want[bad][:2])
-        for k in (1, 8):
-            got = dev.run(k=k).reshape(w.n, k)
-            assert (words(got[:, 0])[:, 0:2] == words(want)[:, 0:2]).all(), k
+        exe, d = multi_host
+        arrays = M.oracle_grid_arrays(G)
+        for k in (1, 2, 8):
+            got = dev.run(k=k)
+            lists = M.host_walk(exe, d, arrays, tris, rays, k)
+            assert (words(got) == words(lists)).all(), k
+            assert (words(got.reshape(w.n, k)[:, 0])[:, 0:2] == words(want)[:, 0:2]).all(), k
     finally:
         mem.set_option("traverse.variant", 0); mem.set_option("traverse.image_width", 0)
         dev.close()
