@@ -62,38 +62,60 @@ __device__ __forceinline__ BBox cell_world_box(const BuildK& k, ivec3 lo, ivec3 
 }
 
 // ---- scene bounding box (compute_bboxes + DeviceReduce, build.cu:725-727) ----------------------------
-// one partial box per workgroup, then a single workgroup folds the partials
+// one partial box per workgroup, then a single workgroup folds the partials.  With the box travels the smallest index of an
+// inadmissible triangle (tri_admissible, prims.h; kNoBadTri if there is none): word 6 of every partial and of the result.
+constexpr int kBoxWords = 8;                 // six floats, the index, one unused
+constexpr int kNoBadTri = 0x7fffffff;
+__device__ __forceinline__ int wave_min_i(int v) { return -wave_max(-v); }      // (v >= 0)
 __global__ void __launch_bounds__(kBlock) bbox_partials(const float4* __restrict__ tris, int n, float* __restrict__ partials) {
     __shared__ float lds[kWaves][6];
+    __shared__ int lds_bad[kWaves];
     float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+    int bad = kNoBadTri;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-        const BBox b = load_tri(tris, i).bbox();
+        const Tri t = load_tri(tris, i);
+        const BBox b = t.bbox();
+        if (!tri_admissible(t)) bad = min(bad, i);
         lo[0] = min(lo[0], b.min.x); lo[1] = min(lo[1], b.min.y); lo[2] = min(lo[2], b.min.z);
         hi[0] = max(hi[0], b.max.x); hi[1] = max(hi[1], b.max.y); hi[2] = max(hi[2], b.max.z);
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) { lo[c] = wave_min_f(lo[c]); hi[c] = wave_max_f(hi[c]); }
-    if (lane_id() == 0) for (int c = 0; c < 3; c++) { lds[wave_id()][c] = lo[c]; lds[wave_id()][3 + c] = hi[c]; }
+    bad = wave_min_i(bad);
+    if (lane_id() == 0) { for (int c = 0; c < 3; c++) { lds[wave_id()][c] = lo[c]; lds[wave_id()][3 + c] = hi[c]; } lds_bad[wave_id()] = bad; }
     __syncthreads();
     if (threadIdx.x < 6) {
         float v = lds[0][threadIdx.x];
         for (int w = 1; w < kWaves; w++) v = threadIdx.x < 3 ? min(v, lds[w][threadIdx.x]) : max(v, lds[w][threadIdx.x]);
-        partials[blockIdx.x * 6 + threadIdx.x] = v;
+        partials[blockIdx.x * kBoxWords + threadIdx.x] = v;
+    } else if (threadIdx.x == 6) {
+        int v = lds_bad[0];
+        for (int w = 1; w < kWaves; w++) v = min(v, lds_bad[w]);
+        reinterpret_cast<int*>(partials)[blockIdx.x * kBoxWords + 6] = v;
     }
 }
 __global__ void __launch_bounds__(kBlock) bbox_final(const float* __restrict__ partials, int num, float* __restrict__ out) {
     __shared__ float lds[kWaves][6];
+    __shared__ int lds_bad[kWaves];
     float v[6] = { FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX };
-    for (int i = threadIdx.x; i < num; i += kBlock)
-        for (int c = 0; c < 6; c++) v[c] = c < 3 ? min(v[c], partials[i * 6 + c]) : max(v[c], partials[i * 6 + c]);
+    int bad = kNoBadTri;
+    for (int i = threadIdx.x; i < num; i += kBlock) {
+        for (int c = 0; c < 6; c++) v[c] = c < 3 ? min(v[c], partials[i * kBoxWords + c]) : max(v[c], partials[i * kBoxWords + c]);
+        bad = min(bad, reinterpret_cast<const int*>(partials)[i * kBoxWords + 6]);
+    }
 #pragma unroll
     for (int c = 0; c < 6; c++) v[c] = c < 3 ? wave_min_f(v[c]) : wave_max_f(v[c]);
-    if (lane_id() == 0) for (int c = 0; c < 6; c++) lds[wave_id()][c] = v[c];
+    bad = wave_min_i(bad);
+    if (lane_id() == 0) { for (int c = 0; c < 6; c++) lds[wave_id()][c] = v[c]; lds_bad[wave_id()] = bad; }
     __syncthreads();
     if (threadIdx.x < 6) {
         float r = lds[0][threadIdx.x];
         for (int w = 1; w < kWaves; w++) r = threadIdx.x < 3 ? min(r, lds[w][threadIdx.x]) : max(r, lds[w][threadIdx.x]);
         out[threadIdx.x] = r;
+    } else if (threadIdx.x == 6) {
+        int r = lds_bad[0];
+        for (int w = 1; w < kWaves; w++) r = min(r, lds_bad[w]);
+        reinterpret_cast<int*>(out)[6] = r;
     }
 }
 
@@ -138,6 +160,10 @@ __device__ __forceinline__ BuildK with_device_shift(BuildK k, const int* __restr
 
 // ---- one subdivision level -----------------------------------------------------------------------------
 // scan functors: 8 children per split cell (build.cu:557-559), then update_entries (build.cu:317-329)
+// A total of 2^32 references or more comes back from a 32-bit scan as a small number.  No summand of these scans reaches 2^30 (a primitive's range lies
+// inside the top-level grid, a child cell's references are among its parent's), so the running sum cannot step over [2^30, 2^31): when the true total is
+// 2^30 or more, the total itself or one of the exclusive prefixes lies in that band, unwrapped.  The output functors look at the prefixes they store anyway.
+__device__ __forceinline__ bool prefix_too_large(int s) { return unsigned(s) >= 0x40000000u; }
 struct ChildCountIn {
     const uint32_t* entries;
     __device__ int operator()(int i) const { return (entries[i] & 3u) ? 8 : 0; }
@@ -151,13 +177,14 @@ struct ChildCountIn {
     }
 };
 struct UpdateEntriesOut {
-    uint32_t* entries;
+    uint32_t* entries; int* too_large;
     __device__ static uint32_t word(uint32_t e, int i, int start) { const uint32_t ld = e & 3u; return ld | (uint32_t(ld ? start : i) << 2); }
-    __device__ void operator()(int i, int start) const { entries[i] = word(entries[i], i, start); }
+    __device__ void operator()(int i, int start) const { entries[i] = word(entries[i], i, start); if (prefix_too_large(start)) *too_large = 1; }
     __device__ void store4(int i, int n, const int* v) const {
         if (i + 4 <= n && lb_aligned16(entries + i)) {
             uint4* p = reinterpret_cast<uint4*>(entries + i);
             const uint4 e = *p;
+            if (prefix_too_large(v[3])) *too_large = 1;
             *p = make_uint4(word(e.x, i, v[0]), word(e.y, i + 1, v[1]), word(e.z, i + 2, v[2]), word(e.w, i + 3, v[3]));
         } else {
             for (int c = 0; c < 4; c++) if (i + c < n) (*this)(i + c, v[c]);
@@ -290,7 +317,10 @@ struct ChildSegIn {
 };
 struct ChildSegOut {
     const int* counts; uint32_t* entries; int* seg_begin; int* tile_first;
+    int* kept;                           // the level's count of kept references (classify_refs has finished): its sign bit says "a prefix left the range" (prefix_too_large)
+    __device__ void flag(Int2 v) const { if (prefix_too_large(v.a) || prefix_too_large(v.b)) atomicOr(kept, int(0x80000000u)); }
     __device__ void operator()(int i, Int2 v) const {
+        flag(v);
         seg_begin[i] = v.a;
         entries[i] = UpdateEntriesOut::word(entries[i], i, v.b);
         mark_tiles(tile_first, i, v.a, counts[i]);
@@ -300,6 +330,7 @@ struct ChildSegOut {
             const int4 c = *reinterpret_cast<const int4*>(counts + i);
             uint4* pe = reinterpret_cast<uint4*>(entries + i);
             const uint4 e = *pe;
+            flag(v[3]);                  // (prefixes ascend: the last of the four is the largest)
             *reinterpret_cast<int4*>(seg_begin + i) = make_int4(v[0].a, v[1].a, v[2].a, v[3].a);
             *pe = make_uint4(UpdateEntriesOut::word(e.x, i, v[0].b), UpdateEntriesOut::word(e.y, i + 1, v[1].b), UpdateEntriesOut::word(e.z, i + 2, v[2].b), UpdateEntriesOut::word(e.w, i + 3, v[3].b));
             // (the four cells together: a tile boundary inside their references is rare -- 2048 references per tile, a handful per cell)
@@ -725,7 +756,10 @@ __global__ void __launch_bounds__(kBlock) concat_level(const uint32_t* __restric
 }
 
 struct PlainIn { const int* v; __device__ int operator()(int i) const { return v[i]; } };
-struct PlainOut { int* v; __device__ void operator()(int i, int s) const { v[i] = s; } };
+struct PlainOut {
+    int* v; int* too_large;
+    __device__ void operator()(int i, int s) const { v[i] = s; if (prefix_too_large(s)) *too_large = 1; }
+};
 
 using Temps = PoolTemps;
 
@@ -783,12 +817,13 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
     int* big_list = ar.get<int>(size_t(num_tris));               // primitives of kCoopCells cells and more (top_range_sizes); their number in dsc[2]
     if (!big_list) return HAGRID_ENOMEM;
     top_range_sizes<<<grid_blocks(num_tris, kBlock), kBlock, 0, st>>>(tris, num_tris, k, counts, big_list, dsc + 2); HG_DBG(ctx);
-    if (!ctx_scan<int>(ctx, PlainIn{counts}, PlainOut{start_emit}, num_tris, partials, (const int*)nullptr, dsc + 0)) return HAGRID_ENOMEM;
+    if (!ctx_scan<int>(ctx, PlainIn{counts}, PlainOut{start_emit, dsc + 3}, num_tris, partials, (const int*)nullptr, dsc + 0)) return HAGRID_ENOMEM;
     int R0 = 0, num_big = 0;
     {
-        int h[3];
+        int h[4];
         HG_TRY(read_back(ctx, dsc, h, sizeof(h)));
         R0 = h[0]; num_big = h[2];
+        if (h[3]) R0 = -1;                       // a prefix left the range (PlainOut): the true total is 2^30 or more, whatever its low 32 bits say
     }
     if (R0 < 0 || R0 > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many top-level references");
     ar.drop(counts);
@@ -820,13 +855,14 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
     // tot (four words per level, zeroed by the caller): {cells of the next level, kept references of this level, {references, cells} of the level after the
     // next: the total of the scan over the new cells}
     {
-        if (!ctx_scan<int>(ctx, ChildCountIn{L.entries}, UpdateEntriesOut{L.entries}, num_top, (int*)nullptr, (const int*)nullptr, dsc + 8)) return HAGRID_ENOMEM;
+        if (!ctx_scan<int>(ctx, ChildCountIn{L.entries}, UpdateEntriesOut{L.entries, dsc + 3}, num_top, (int*)nullptr, (const int*)nullptr, dsc + 8)) return HAGRID_ENOMEM;
     }
     int num_new_cells = 0, shift = 0;
     {   // the shift (dsc[1], top_log_dims) and the cells of the next level (dsc[8]) in one round trip
         int h[8];
         HG_TRY(read_back(ctx, dsc + 1, h, sizeof(h)));
         shift = h[0]; num_new_cells = h[7];
+        if (h[2]) num_new_cells = -1;            // a prefix left the range (UpdateEntriesOut; dsc[3] was zero when the reference total passed)
     }
     if (shift >= 24) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many levels");
     k.shift = shift;
@@ -835,7 +871,7 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
     for (int level = 0;; level++) {
         GLevel& P = levels.back();
         int* tot = dsc + 8 + 4 * level;
-        if (num_new_cells < 0) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: level too large");
+        if (num_new_cells < 0 || num_new_cells > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: level too large");
         if ((int)levels.size() >= 24) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many levels");
         const bool last = num_new_cells == 0;
         if (last && level > 0) {
@@ -860,11 +896,12 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
         }
         Int2* next = reinterpret_cast<Int2*>(tot + 2);
         if (!last) {
-            if (!ctx_scan<Int2>(ctx, ChildSegIn{N.cell_counts, N.entries}, ChildSegOut{N.cell_counts, N.entries, N.seg_begin, N.tile_first}, num_new_cells, (Int2*)nullptr,
+            if (!ctx_scan<Int2>(ctx, ChildSegIn{N.cell_counts, N.entries}, ChildSegOut{N.cell_counts, N.entries, N.seg_begin, N.tile_first, tot + 1}, num_new_cells, (Int2*)nullptr,
                                 (const Int2*)nullptr, next)) return HAGRID_ENOMEM;
         }
         int h3[3] = {0, 0, 0};                        // kept, references of the next level, cells of the level after it
         HG_TRY(read_back(ctx, tot + 1, h3, sizeof(h3)));
+        if (h3[0] < 0) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: level too large");       // (ChildSegOut: a prefix of the next level's references or cells left the range)
         if (level < HAGRID_MAX_LEVELS) { bc.level_refs[level] = P.num_refs; bc.level_cells[level] = P.num_cells; bc.level_kept[level] = h3[0]; bc.num_levels = level + 1; }
         if (last) { ar.drop(masks); break; }
         const int num_children = h3[1];
@@ -951,21 +988,38 @@ extern "C" int hagrid_build_grid(hagrid_ctx* ctx, const void* tris_v, int num_tr
 
     // ---- scene box, top-level resolution (build.cu:725-740) ----
     const int bb_blocks = std::min(grid_blocks(num_tris, kBlock), 1024);
-    float* bb_part = tmp.get<float>(size_t(bb_blocks) * 6 + 8);
+    float* bb_part = tmp.get<float>(size_t(bb_blocks) * kBoxWords + 8);
     if (!bb_part) return HAGRID_ENOMEM;
-    float* bb_out = bb_part + size_t(bb_blocks) * 6;
+    float* bb_out = bb_part + size_t(bb_blocks) * kBoxWords;
     bbox_partials<<<bb_blocks, kBlock, 0, st>>>(tris, num_tris, bb_part); HG_DBG(ctx);
     bbox_final<<<1, kBlock, 0, st>>>(bb_part, bb_blocks, bb_out); HG_DBG(ctx);
-    float hb[6];
+    float hb[8];
     HG_TRY(read_back(ctx, bb_out, hb, sizeof(hb)));
+    // ---- admissible scenes: nothing but the box pass has run when a scene is refused ----
+    int bad_tri; memcpy(&bad_tri, &hb[6], sizeof(int));
+    if (bad_tri != kNoBadTri) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "build_grid: triangle %d is not finite", bad_tri);
+        HG_FAIL(ctx, HAGRID_EINVAL, msg);
+    }
     BBox gb(vec3(hb[0], hb[1], hb[2]), vec3(hb[3], hb[4], hb[5]));
+    {
+        const vec3 e = gb.extents();
+        if (!(e.x <= FLT_MAX && e.y <= FLT_MAX && e.z <= FLT_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: the extent of the scene box is not finite");
+    }
+    if (!grid_dims_defined(gb, num_tris, top_density)) gb = widen_scene_box(gb);      // a flat scene: the widened box is the grid's
     ivec3 dims = compute_grid_dims(gb, num_tris, top_density);
+    if (dims.x > 0x3fffffff || dims.y > 0x3fffffff || dims.z > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: top-level grid too large");
     dims.x += dims.x & 1; dims.y += dims.y & 1; dims.z += dims.z & 1;      // even: 8-entry blocks stay 32 B aligned
     const vec3 ext = gb.extents();
     gb.min -= ext * 0.001f;
     gb.max += ext * 0.001f;
     const long long num_top_ll = (long long)dims.x * dims.y * dims.z;
     if (num_top_ll > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: top-level grid too large");
+    {   // the enlarged box of an admissible scene can still leave float's range
+        const vec3 e = gb.extents();
+        if (!(e.x <= FLT_MAX && e.y <= FLT_MAX && e.z <= FLT_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: the extent of the scene box is not finite");
+    }
 
     BuildK k;
     k.dims = dims; k.shift = 0; k.bmin = gb.min; k.bmax = gb.max; k.cell_size = vec3(0.0f);

@@ -61,24 +61,75 @@ HOST DEVICE inline Entry make_entry(uint32_t log_dim, uint32_t begin) {
     Entry e; e.log_dim = log_dim; e.begin = begin; return e;
 }
 
-/// Inclusive range of grid cells touched by obj_bb, clamped to the grid (truncating casts).
+/// A grid coordinate from its float image, total: a value inside int's range gives its truncation, 2^31 and beyond
+/// `beyond`, -2^31 and below `below`, NaN `nan`.  The comparison is made in the float domain, so no result depends on a
+/// conversion of a value outside int's range ("Admissible scenes").
+HOST DEVICE inline int grid_coord(float v, int below, int beyond, int nan) {
+    return v >= 2147483648.0f ? beyond : (v > -2147483648.0f ? int(v) : (v != v ? nan : below));
+}
+
+/// Inclusive range of grid cells touched by obj_bb, clamped to the grid (truncating casts).  A lower coordinate beyond
+/// int's range counts as 2^30 (past every grid), an upper one below it as -2^30; a NaN covers its axis.
 HOST DEVICE inline Range compute_range(const ivec3& dims, const BBox& grid_bb, const BBox& obj_bb) {
     const vec3 inv = vec3(dims) / grid_bb.extents();
-    return Range(max(int((obj_bb.min.x - grid_bb.min.x) * inv.x), 0),
-                 max(int((obj_bb.min.y - grid_bb.min.y) * inv.y), 0),
-                 max(int((obj_bb.min.z - grid_bb.min.z) * inv.z), 0),
-                 min(int((obj_bb.max.x - grid_bb.min.x) * inv.x), dims.x - 1),
-                 min(int((obj_bb.max.y - grid_bb.min.y) * inv.y), dims.y - 1),
-                 min(int((obj_bb.max.z - grid_bb.min.z) * inv.z), dims.z - 1));
+    const int out = 0x40000000;
+    return Range(max(grid_coord((obj_bb.min.x - grid_bb.min.x) * inv.x, 0, out, 0), 0),
+                 max(grid_coord((obj_bb.min.y - grid_bb.min.y) * inv.y, 0, out, 0), 0),
+                 max(grid_coord((obj_bb.min.z - grid_bb.min.z) * inv.z, 0, out, 0), 0),
+                 min(grid_coord((obj_bb.max.x - grid_bb.min.x) * inv.x, -out, out, out), dims.x - 1),
+                 min(grid_coord((obj_bb.max.y - grid_bb.min.y) * inv.y, -out, out, out), dims.y - 1),
+                 min(grid_coord((obj_bb.max.z - grid_bb.min.z) * inv.z, -out, out, out), dims.z - 1));
+}
+
+/// One component of compute_grid_dims: max(1, int(p)) wherever that is defined, INT_MAX from 2^31 on, 1 for NaN.
+HOST DEVICE inline int grid_dim(float p) {
+    return p >= 2147483648.0f ? 0x7fffffff : (p >= 1.0f ? int(p) : 1);
+}
+
+/// Is Cleary's formula defined for this box?  No when density * n / volume is not finite (a flat box, a volume
+/// that underflows) or a product extent * ratio is NaN or beyond int's range.
+HOST DEVICE inline bool grid_dims_defined(const BBox& bb, int num_prims, float density) {
+    const vec3 e = bb.extents();
+    const float q = density * num_prims / (e.x * e.y * e.z);
+    if (!(q - q == 0.0f)) return false;
+    const float ratio = det_cbrtf(q);
+    const float px = e.x * ratio, py = e.y * ratio, pz = e.z * ratio, lim = 2147483648.0f;
+    return px > -lim && px < lim && py > -lim && py < lim && pz > -lim && pz < lim;
 }
 
 /// Resolution for num_prims primitives in bb at the given density (Cleary's formula);
-/// the cube root is the deterministic det_cbrtf so host and device agree.
+/// the cube root is the deterministic det_cbrtf so host and device agree.  Total: see grid_dim.
 HOST DEVICE inline ivec3 compute_grid_dims(const BBox& bb, int num_prims, float density) {
     const vec3 e = bb.extents();
     const float volume = e.x * e.y * e.z;
     const float ratio = det_cbrtf(density * num_prims / volume);
-    return max(ivec3(1), ivec3(int(e.x * ratio), int(e.y * ratio), int(e.z * ratio)));
+    return ivec3(grid_dim(e.x * ratio), grid_dim(e.y * ratio), grid_dim(e.z * ratio));
+}
+
+/// The fraction of a scene's scale below which an axis of its box is widened, the smallest scale, and the share of the added width
+/// that goes below the box (widen_scene_box).
+constexpr float kWidenFraction = 0.0009765625f;          // 2^-10
+constexpr float kWidenMinScale = 9.5367431640625e-07f;   // 2^-20
+constexpr float kWidenBelow = 0.381966f;                 // 2 - the golden ratio: no plane k / (dims << shift) of a grid comes near it
+
+/// The box a scene gets where Cleary's formula is undefined for its own (a quad, a ground plane, coincident points):
+/// every axis thinner than 2^-10 of the scene's scale is widened to that width.  The scale is the largest extent, or the
+/// largest coordinate magnitude if that is larger (so that the new planes are 2^13 ulp apart at least), and 2^-20 at the
+/// least (so that the volume, 2^-90 or more, is a normal number).  The added width is NOT split evenly: the resolutions
+/// are even, so the centre of the box is a cell boundary at every level, and a flat scene placed there would be
+/// referenced from both sides at best and, where the boundary's rounding goes against it, from neither.
+HOST DEVICE inline BBox widen_scene_box(const BBox& bb) {
+    const vec3 e = bb.extents();
+    float s = e.x > e.y ? e.x : e.y; s = e.z > s ? e.z : s;
+    const float c[6] = { bb.min.x, bb.min.y, bb.min.z, bb.max.x, bb.max.y, bb.max.z };
+    for (int i = 0; i < 6; i++) { const float a = c[i] < 0 ? -c[i] : c[i]; s = a > s ? a : s; }
+    s = s > kWidenMinScale ? s : kWidenMinScale;
+    const float w = s * kWidenFraction;
+    BBox r = bb;
+    if (e.x < w) { const float below = (w - e.x) * kWidenBelow; r.min.x = bb.min.x - below; r.max.x = bb.max.x + ((w - e.x) - below); }
+    if (e.y < w) { const float below = (w - e.y) * kWidenBelow; r.min.y = bb.min.y - below; r.max.y = bb.max.y + ((w - e.y) - below); }
+    if (e.z < w) { const float below = (w - e.z) * kWidenBelow; r.min.z = bb.min.z - below; r.max.z = bb.max.z + ((w - e.z) - below); }
+    return r;
 }
 
 /// Walks the voxel map from the top-level entry of `voxel` (virtual grid coordinates) down to a leaf

@@ -70,6 +70,19 @@ HOST DEVICE inline bool edge_axis_separates(const vec3& half, const vec3& e, con
 
 } // namespace detail
 
+/// Is the triangle admissible in a scene ("Admissible scenes")?  All twelve floats are finite, and so
+/// are the two vertices that are derived from them, v0 - e1 and v0 + e2.
+HOST DEVICE inline bool tri_admissible(const Tri& t) {
+    const vec3 v1 = t.v0 - t.e1, v2 = t.v0 + t.e2;
+    const float m = FLT_MAX;
+    using detail::fabs1;
+    return fabs1(t.v0.x) <= m && fabs1(t.v0.y) <= m && fabs1(t.v0.z) <= m && fabs1(t.nx) <= m &&
+           fabs1(t.e1.x) <= m && fabs1(t.e1.y) <= m && fabs1(t.e1.z) <= m && fabs1(t.ny) <= m &&
+           fabs1(t.e2.x) <= m && fabs1(t.e2.y) <= m && fabs1(t.e2.z) <= m && fabs1(t.nz) <= m &&
+           fabs1(v1.x) <= m && fabs1(v1.y) <= m && fabs1(v1.z) <= m &&
+           fabs1(v2.x) <= m && fabs1(v2.y) <= m && fabs1(v2.z) <= m;
+}
+
 HOST DEVICE inline bool plane_overlap_box(const vec3& n, float d, const vec3& min, const vec3& max) {
     return detail::plane_cuts_box(n, d, min, max);
 }

@@ -137,7 +137,13 @@ int hagrid_profile_begin(hagrid_ctx* ctx);
 float hagrid_profile_end(hagrid_ctx* ctx);
 
 /* ---- construction (build.h:17-31) ------------------------------------------------------------------ */
-/* build_grid (build.cu:718-760).  tris: 48-byte Tri records on the device.  grid is overwritten. */
+/* build_grid (build.cu:718-760).  tris: 48-byte Tri records on the device.  grid is overwritten.
+ * Admissible scenes: HAGRID_EINVAL for a triangle with a float that is not finite, or whose v0 - e1 or v0 + e2 is not finite
+ * (hagrid_last_error names the smallest such index); nothing but the bounding-box pass has run by then.  HAGRID_ERANGE for finite triangles whose
+ * scene-box extent is not finite, for a top-level grid, a level's references or cells, or the totals beyond 2^30 - 1 (true totals: a sum of 2^32 or
+ * more is seen), and for 24 levels or more.  A scene whose box has no volume (a quad, a ground plane, coincident points) is built in a box widened
+ * to 2^-10 of the scene's scale on its thin axes; that box is grid->bbox.  After a refusal *grid is as it was, the context stays usable and the pool's
+ * usage is unchanged. */
 int hagrid_build_grid(hagrid_ctx* ctx, const void* tris, int num_tris, hagrid_grid* grid,
                       float top_density, float snd_density);
 /* merge_grid (merge.cu:331-377).  On an error the grid is gone: cells and ref_ids are released and NULL in the descriptor

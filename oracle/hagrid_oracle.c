@@ -125,28 +125,63 @@ void orc_tri_bbox(const OTri* tri, OBBox* out) {
     out->pad0 = 0; out->pad1 = 0;
 }
 
-/* grid.h:84-93 */
+/* grid.h grid_coord: a grid coordinate from its float image, total ("Admissible scenes") */
+static inline int grid_coord(float v, int below, int beyond, int nan) {
+    return v >= 2147483648.0f ? beyond : (v > -2147483648.0f ? (int)v : (v != v ? nan : below));
+}
+/* grid.h compute_range */
 void orc_compute_range(const oivec3* dims, const OBBox* g, const OBBox* o, ORange* r) {
     ovec3 inv = v3_div(v3_from_i(*dims), v3_sub(g->max, g->min));
-    r->lx = imax((int)((o->min.x - g->min.x) * inv.x), 0);
-    r->ly = imax((int)((o->min.y - g->min.y) * inv.y), 0);
-    r->lz = imax((int)((o->min.z - g->min.z) * inv.z), 0);
-    r->hx = imin((int)((o->max.x - g->min.x) * inv.x), dims->x - 1);
-    r->hy = imin((int)((o->max.y - g->min.y) * inv.y), dims->y - 1);
-    r->hz = imin((int)((o->max.z - g->min.z) * inv.z), dims->z - 1);
+    const int out = 0x40000000;
+    r->lx = imax(grid_coord((o->min.x - g->min.x) * inv.x, 0, out, 0), 0);
+    r->ly = imax(grid_coord((o->min.y - g->min.y) * inv.y, 0, out, 0), 0);
+    r->lz = imax(grid_coord((o->min.z - g->min.z) * inv.z, 0, out, 0), 0);
+    r->hx = imin(grid_coord((o->max.x - g->min.x) * inv.x, -out, out, out), dims->x - 1);
+    r->hy = imin(grid_coord((o->max.y - g->min.y) * inv.y, -out, out, out), dims->y - 1);
+    r->hz = imin(grid_coord((o->max.z - g->min.z) * inv.z, -out, out, out), dims->z - 1);
 }
-static inline int range_size(const ORange* r) { /* grid.h:74 */
-    return (r->hx - r->lx + 1) * (r->hy - r->ly + 1) * (r->hz - r->lz + 1);
+static inline int64_t range_size(const ORange* r) { /* grid.h:74, in 64 bits */
+    return (int64_t)(r->hx - r->lx + 1) * (r->hy - r->ly + 1) * (r->hz - r->lz + 1);
 }
 
-/* grid.h:96-101 (cbrtf -> orc_cbrtf, D5) */
+/* grid.h grid_dim, grid_dims_defined, compute_grid_dims (cbrtf -> orc_cbrtf, D5), widen_scene_box */
+static inline int grid_dim(float p) { return p >= 2147483648.0f ? 0x7fffffff : (p >= 1.0f ? (int)p : 1); }
+int orc_grid_dims_defined(const OBBox* bb, int num_prims, float density) {
+    ovec3 e = v3_sub(bb->max, bb->min);
+    float q = density * num_prims / (e.x * e.y * e.z);
+    if (!(q - q == 0.0f)) return 0;
+    float ratio = orc_cbrtf(q);
+    float px = e.x * ratio, py = e.y * ratio, pz = e.z * ratio, lim = 2147483648.0f;
+    return px > -lim && px < lim && py > -lim && py < lim && pz > -lim && pz < lim;
+}
 void orc_compute_grid_dims(const OBBox* bb, int num_prims, float density, oivec3* out) {
     ovec3 e = v3_sub(bb->max, bb->min);
     float volume = e.x * e.y * e.z;
     float ratio = orc_cbrtf(density * num_prims / volume);
-    out->x = imax(1, (int)(e.x * ratio));
-    out->y = imax(1, (int)(e.y * ratio));
-    out->z = imax(1, (int)(e.z * ratio));
+    out->x = grid_dim(e.x * ratio);
+    out->y = grid_dim(e.y * ratio);
+    out->z = grid_dim(e.z * ratio);
+}
+void orc_widen_scene_box(const OBBox* bb, OBBox* out) {
+    ovec3 e = v3_sub(bb->max, bb->min);
+    float s = e.x > e.y ? e.x : e.y; s = e.z > s ? e.z : s;
+    const float c[6] = { bb->min.x, bb->min.y, bb->min.z, bb->max.x, bb->max.y, bb->max.z };
+    for (int i = 0; i < 6; i++) { float a = c[i] < 0 ? -c[i] : c[i]; s = a > s ? a : s; }
+    s = s > 9.5367431640625e-07f ? s : 9.5367431640625e-07f;     /* 2^-20 */
+    float w = s * 0.0009765625f;                                  /* 2^-10 */
+    const float f = 0.381966f;                                    /* the share of the added width that goes below the box */
+    *out = *bb;
+    if (e.x < w) { float below = (w - e.x) * f; out->min.x = bb->min.x - below; out->max.x = bb->max.x + ((w - e.x) - below); }
+    if (e.y < w) { float below = (w - e.y) * f; out->min.y = bb->min.y - below; out->max.y = bb->max.y + ((w - e.y) - below); }
+    if (e.z < w) { float below = (w - e.z) * f; out->min.z = bb->min.z - below; out->max.z = bb->max.z + ((w - e.z) - below); }
+}
+/* prims.h tri_admissible */
+static inline int finite_f(float x) { return fabsf(x) <= FLT_MAX; }
+int orc_tri_admissible(const OTri* t) {
+    const float* f = (const float*)t;
+    for (int i = 0; i < 12; i++) if (!finite_f(f[i])) return 0;
+    ovec3 v1 = v3_sub(t->v0, t->e1), v2 = v3_add(t->v0, t->e2);
+    return finite_f(v1.x) && finite_f(v1.y) && finite_f(v1.z) && finite_f(v2.x) && finite_f(v2.y) && finite_f(v2.z);
 }
 
 /* grid.h:103-116; *words (optional) receives the number of voxel-map words dereferenced */
@@ -335,8 +370,15 @@ static int split_mask(const BuildConsts* k, const OCell* cell, const OTri* prim)
     return mask;
 }
 
+static void free_levels(Level* levels, int num_levels) {
+    for (int l = 0; l < num_levels; l++) { free(levels[l].ref_ids); free(levels[l].cell_ids); free(levels[l].cells); free(levels[l].entries); }
+}
+
 int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_density, float snd_density) {
     BuildConsts k;
+    /* admissible scenes: refused before anything is allocated */
+    if (!tris || num_tris <= 0) return ORC_EINVAL;
+    for (int i = 0; i < num_tris; i++) if (!orc_tri_admissible(&tris[i])) return ORC_EINVAL;
     /* build.cu:723-727: bboxes + reduction from BBox::empty() */
     OBBox* bboxes = (OBBox*)xmalloc(sizeof(OBBox) * (size_t)(num_tris + 1));
     OBBox gb; gb.min = v3(FLT_MAX, FLT_MAX, FLT_MAX); gb.max = v3(-FLT_MAX, -FLT_MAX, -FLT_MAX); gb.pad0 = gb.pad1 = 0;
@@ -345,8 +387,14 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
         gb.min = v3_min(gb.min, bboxes[i].min);
         gb.max = v3_max(gb.max, bboxes[i].max);
     }
+    {
+        ovec3 e = v3_sub(gb.max, gb.min);
+        if (!(finite_f(e.x) && finite_f(e.y) && finite_f(e.z))) { free(bboxes); return ORC_ERANGE_BOX; }
+    }
+    if (!orc_grid_dims_defined(&gb, num_tris, top_density)) { OBBox w; orc_widen_scene_box(&gb, &w); gb = w; }   /* a flat scene */
     /* build.cu:728-737 */
     oivec3 dims; orc_compute_grid_dims(&gb, num_tris, top_density, &dims);
+    if (dims.x > 0x3fffffff || dims.y > 0x3fffffff || dims.z > 0x3fffffff) { free(bboxes); return ORC_ERANGE; }
     dims.x = dims.x % 2 ? dims.x + 1 : dims.x;
     dims.y = dims.y % 2 ? dims.y + 1 : dims.y;
     dims.z = dims.z % 2 ? dims.z + 1 : dims.z;
@@ -354,6 +402,11 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
     gb.min = v3_sub(gb.min, v3_scale(ext, 0.001f));
     gb.max = v3_add(gb.max, v3_scale(ext, 0.001f));
     k.dims = dims; k.bbox = gb;
+    if ((int64_t)dims.x * dims.y * dims.z > 0x3fffffff) { free(bboxes); return ORC_ERANGE; }
+    {
+        ovec3 e = v3_sub(gb.max, gb.min);
+        if (!(finite_f(e.x) && finite_f(e.y) && finite_f(e.z))) { free(bboxes); return ORC_ERANGE_BOX; }
+    }
 
     int num_top = dims.x * dims.y * dims.z;
 
@@ -364,10 +417,10 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
     for (int i = 0; i < num_tris; i++) {
         ORange r; orc_compute_range(&dims, &gb, &bboxes[i], &r);
         start_emit[i] = total;
-        total += imax(0, range_size(&r));
+        { int64_t sz = range_size(&r); total += sz > 0 ? sz : 0; }
     }
     start_emit[num_tris] = total;
-    if (total > 0x3fffffff) { free(bboxes); free(start_emit); return -1; }
+    if (total > 0x3fffffff) { free(bboxes); free(start_emit); return ORC_ERANGE; }
     int R0 = (int)total;
     int* ref_ids  = (int*)xmalloc(sizeof(int) * (size_t)R0);
     int* cell_ids = (int*)xmalloc(sizeof(int) * (size_t)R0);
@@ -406,6 +459,7 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
         }
     }
     free(refs_per_cell);
+    if (shift >= 24) { free(log_dims); free(ref_ids); free(cell_ids); return ORC_ERANGE_LEVELS; }     /* as hagrid_build_grid: a depth that cannot be served */
     k.shift = shift;
     {   /* build.cu:509 */
         oivec3 vd = iv3(dims.x << shift, dims.y << shift, dims.z << shift);
@@ -446,7 +500,7 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
         /* update_log_dims build.cu:273-278 */
         for (int i = 0; i < num_top; i++) log_dims[i] = imax(0, log_dims[i] - 1);
         /* scan build.cu:557-559 + update_entries build.cu:317-329 */
-        int num_new_cells = 0;
+        int64_t num_new_cells = 0;
         for (int i = 0; i < num_cells; i++) {
             uint32_t ld = ENTRY_LOG_DIM(L->entries[i]);
             L->entries[i] = orc_make_entry(ld, ld ? (uint32_t)num_new_cells : (uint32_t)i);
@@ -475,9 +529,9 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
         free(L->ref_ids); free(L->cell_ids);
         L->ref_ids = nref; L->cell_ids = ncel; L->num_kept = num_kept;
         if (getenv("ORC_VERBOSE"))
-            fprintf(stderr, "[oracle] level %d: cells %d refs %d kept %d new_cells %d\n", num_levels - 1, num_cells, num_refs, num_kept, num_new_cells);
+            fprintf(stderr, "[oracle] level %d: cells %d refs %d kept %d new_cells %lld\n", num_levels - 1, num_cells, num_refs, num_kept, (long long)num_new_cells);
         if (num_new_cells == 0) break;      /* build.cu:583-587 */
-        if (num_levels >= ORC_MAX_LEVELS) return -2;
+        if (num_levels >= 24) { free(log_dims); free_levels(levels, num_levels); return ORC_ERANGE_LEVELS; }
 
         int num_split = num_refs - num_kept;
         /* compute_split_masks build.cu:594 + scan build.cu:597 + split_refs build.cu:219-243 */
@@ -490,7 +544,7 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
             masks[i] = (unsigned char)m;
             nn += __builtin_popcount((unsigned)m);
         }
-        if (nn > 0x3fffffff) return -1;
+        if (nn > 0x3fffffff || num_new_cells > 0x3fffffff) { free(masks); free(log_dims); free_levels(levels, num_levels); return ORC_ERANGE; }
         int num_new_refs = (int)nn;
         int* cref = (int*)xmalloc(sizeof(int) * (size_t)num_new_refs);
         int* ccel = (int*)xmalloc(sizeof(int) * (size_t)num_new_refs);
@@ -523,14 +577,14 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
             }
         }
         OEntry* nentries = (OEntry*)xcalloc((size_t)num_new_cells + 1, sizeof(OEntry));
-        levels[num_levels++] = (Level){ cref, ccel, num_new_refs, num_new_refs, ncells, nentries, num_new_cells };
+        levels[num_levels++] = (Level){ cref, ccel, num_new_refs, num_new_refs, ncells, nentries, (int)num_new_cells };
     }
     free(log_dims);
 
     /* ---- concat_levels, build.cu:621-716 ---- */
     int64_t total_refs64 = 0, total_cells64 = 0;
     for (int i = 0; i < num_levels; i++) { total_refs64 += levels[i].num_kept; total_cells64 += levels[i].num_cells; }
-    if (total_refs64 > 0x3fffffff || total_cells64 > 0x3fffffff) return -1;
+    if (total_refs64 > 0x3fffffff || total_cells64 > 0x3fffffff) { free_levels(levels, num_levels); return ORC_ERANGE; }
     int total_refs = (int)total_refs64, total_cells = (int)total_cells64;
     /* start_cell = exclusive scan of leaf flags over the concatenated cells (build.cu:650-659) */
     int* start_cell = (int*)xmalloc(sizeof(int) * ((size_t)total_cells + 1));
@@ -596,7 +650,7 @@ int orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_densit
         }
     }
     grid->dims = dims; grid->bbox = gb;
-    for (int l = 0; l < num_levels; l++) { free(levels[l].ref_ids); free(levels[l].cell_ids); free(levels[l].cells); free(levels[l].entries); }
+    free_levels(levels, num_levels);
     return 0;
 }
 

@@ -93,6 +93,15 @@ int      orc_intersect_prim_ray_uv(const OTri* tri, const ORay* ray, int id, OHi
 /* ---- passes (build.h:17-31, traverse.h:11-14) -------------------------------------------- */
 void orc_grid_init(OGrid* g);
 void orc_grid_free(OGrid* g);
+/* What orc_build_grid refuses (DESIGN.md sections 2 and 6), as hagrid_build_grid does: the first three where it answers HAGRID_ERANGE,
+ * the last where it answers HAGRID_EINVAL.  A refusal leaves *grid untouched and nothing allocated. */
+#define ORC_ERANGE        (-1)   /* a total of references, cells or top-level cells beyond 2^30 - 1 */
+#define ORC_ERANGE_LEVELS (-2)   /* 24 levels or more */
+#define ORC_ERANGE_BOX    (-4)   /* finite triangles whose scene-box extent is not finite */
+#define ORC_EINVAL        (-3)   /* no triangles, or an inadmissible triangle (orc_tri_admissible) */
+int  orc_tri_admissible(const OTri* tri);                                                  /* prims.h tri_admissible */
+int  orc_grid_dims_defined(const OBBox* bb, int num_prims, float density);                 /* grid.h grid_dims_defined */
+void orc_widen_scene_box(const OBBox* bb, OBBox* out);                                     /* grid.h widen_scene_box */
 int  orc_build_grid(const OTri* tris, int num_tris, OGrid* grid, float top_density, float snd_density);
 int  orc_merge_grid(OGrid* grid, float alpha);
 int  orc_flatten_grid(OGrid* grid);

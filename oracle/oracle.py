@@ -67,6 +67,9 @@ def lib() -> C.CDLL:
         L.orc_tri_bbox.argtypes = [vp, vp]
         L.orc_compute_range.argtypes = [vp, vp, vp, vp]
         L.orc_compute_grid_dims.argtypes = [vp, i32, f32, vp]
+        L.orc_grid_dims_defined.restype = i32; L.orc_grid_dims_defined.argtypes = [vp, i32, f32]
+        L.orc_widen_scene_box.restype = None; L.orc_widen_scene_box.argtypes = [vp, vp]
+        L.orc_tri_admissible.restype = i32; L.orc_tri_admissible.argtypes = [vp]
         L.orc_lookup_entry.restype = C.c_uint32; L.orc_lookup_entry.argtypes = [vp, i32, vp, vp, vp]
         L.orc_intersect_prim_cell.restype = i32; L.orc_intersect_prim_cell.argtypes = [vp, vp]
         L.orc_intersect_prim_ray.restype = i32; L.orc_intersect_prim_ray.argtypes = [vp, vp, i32, vp]
