@@ -4,6 +4,7 @@
 //   trav_plain.hip  the kernels that walk the construction format: the reference-shaped one (statistics, Hit.id = steps) and v2
 //   trav_multi.hip, crossings.hip, closest.hip, overlap.hip   the queries over the construction format (DevGrid below)
 //   hagrid/cell_walk.h  the ray walk over the construction format, written once for kernels and host programs
+//   hagrid/block_walk.h the descent through a top-level cell's sub-blocks (closest.hip, overlap.hip), likewise
 //   ray_order.hip   row-length detection of image-ordered batches and the counting sort of unordered ones (ray binning)
 //   kat/kat.hip     known-answer hooks and timed diagnostic instantiations: a separate library, libhagrid_amd_kat.so (tests, dev tools)
 #pragma once
@@ -101,7 +102,8 @@ __device__ __forceinline__ Tri load_tri(const float4* __restrict__ tris, int ref
     return Tri(vec3(a.x, a.y, a.z), a.w, vec3(b.x, b.y, b.z), b.w, vec3(c.x, c.y, c.z), c.w);
 }
 
-// The construction format behind plain device loads: the grid accessor of closest.h and overlap.h, and (RayGrid) of hagrid/cell_walk.h.  The cell format is a
+// The construction format behind plain device loads: the grid accessor of hagrid/block_walk.h (c, word, cell, ref, tri: what closest.h and overlap.h walk)
+// and, as RayGrid below, of hagrid/cell_walk.h.  c is blocks::GridConsts under the name closest.h gives it.  The cell format is a
 // run-time value, uniform over a launch (one kernel per query: the product library's kernel budget, tests/test_abi.py).
 struct DevGrid {
     closest::GridConsts c;
@@ -160,7 +162,7 @@ struct RayGrid : DevGrid {
     }
 };
 
-// the stack of closest.h's and overlap.h's descent in LDS: column `lane` of two [level][64] arrays
+// the stack of blocks::descend_top (hagrid/block_walk.h: set, set_i, w, i) in LDS: column `lane` of two [level][64] arrays, blocks::kMaxLevels levels
 struct LdsStack {
     uint32_t* w_;
     uint32_t* i_;

@@ -40,7 +40,7 @@ HOST DEVICE inline int f2i(float f) {
 struct CellRec { int lx, ly, lz, hx, hy, hz, begin, end; };
 
 /// setup_traversal's constants (hagrid_amd/csrc/traverse.hip make_args computes the same), from the VIRTUAL resolution dims = top-level resolution << shift.
-/// closest::GridConsts (closest.h) is this struct set from the top-level resolution, plus the margin of the box queries, which no ray walk reads.
+/// blocks::GridConsts (block_walk.h) is this struct set from the top-level resolution, plus the margin of the region queries, which no ray walk reads.
 struct WalkConsts {
     ivec3 top, dims;
     int shift;

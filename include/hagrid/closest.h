@@ -53,6 +53,7 @@
 #ifndef HAGRID_CLOSEST_H
 #define HAGRID_CLOSEST_H
 
+#include "block_walk.h"
 #include "cell_walk.h"
 #include "grid.h"
 #include "prims.h"
@@ -133,21 +134,7 @@ HOST DEVICE inline void brute_force(F tri_at, int num_tris, const vec3& p, float
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------------
 
-/// walk::WalkConsts set from the TOP-LEVEL resolution (the same operations on the same numbers), and the margin, which only the box queries read
-struct GridConsts : walk::WalkConsts {
-    float eps;              ///< the absolute margin
-    HOST DEVICE void set(const ivec3& top_, int shift_, const vec3& lo_, const vec3& hi_) {
-        walk::WalkConsts::set(top_ << shift_, shift_, lo_, hi_);
-        eps = abs_margin(lo_, hi_);
-    }
-    HOST DEVICE static float abs_margin(const vec3& lo_, const vec3& hi_) {
-        float m = detail::fabs1(lo_.x);
-        m = max(m, detail::fabs1(lo_.y)); m = max(m, detail::fabs1(lo_.z));
-        m = max(m, detail::fabs1(hi_.x)); m = max(m, detail::fabs1(hi_.y)); m = max(m, detail::fabs1(hi_.z));
-        return m * 1.52587890625e-05f;      // 2^-16
-    }
-};
-using walk::CellRec;         ///< here `end` bounds the list: INT_MAX for a SmallCell (sentinel-terminated); begin < 0: empty
+// GridConsts, CellRec (here `end` bounds the list), ArrayStack, kMaxLevels: block_walk.h, which names them in this namespace as well
 struct Counts { int cells, tris, pruned; };
 
 /// a distance reduced by the absolute margin, not below 0
@@ -166,17 +153,6 @@ HOST DEVICE inline float box_lower2(const GridConsts& c, const vec3& p, int lx, 
     return dx * dx + dy * dy + dz * dz;
 }
 
-/// A host-side stack for the descent (a run-time indexed array: fine on the host; the kernel keeps its stack in LDS)
-template <int LEVELS>
-struct ArrayStack {
-    uint32_t w_[LEVELS], i_[LEVELS];
-    void set(int level, uint32_t w, uint32_t i) { w_[level] = w; i_[level] = i; }
-    void set_i(int level, uint32_t i) { i_[level] = i; }
-    uint32_t w(int level) const { return w_[level]; }
-    uint32_t i(int level) const { return i_[level]; }
-};
-constexpr int kMaxLevels = 16;     ///< every level of the voxel map consumes at least one of the `shift` <= 15 bits
-
 /// the list of one cell.  G: c (GridConsts), word(i), cell(i) -> CellRec, ref(i), tri(id)
 template <typename G>
 HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, Best& b, Counts& n) {
@@ -193,48 +169,23 @@ HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, 
     return c;
 }
 
-/// one top-level cell: descend its sub-blocks while their boxes are not beyond the best so far
+/// one top-level cell: descend its sub-blocks (block_walk.h) while their boxes are not beyond the best so far
 template <typename G, typename S>
 HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& p, int tx, int ty, int tz, uint32_t first_cell, uint32_t& last_cell, Best& b, Counts& n) {
     const GridConsts& c = g.c;
-    int rs = c.shift;                                   // the current node covers 2^rs voxels per axis from (ox, oy, oz)
-    int ox = tx << rs, oy = ty << rs, oz = tz << rs;
-    if (beyond(box_lower2(c, p, ox, oy, oz, ox + (1 << rs), oy + (1 << rs), oz + (1 << rs)), b.d2)) { n.pruned++; return; }
-    const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
-    if (!(top_w & 3u)) {
-        const uint32_t ci = top_w >> 2;
+    auto prune = [&](int x, int y, int z, int s) {
+        const bool far = beyond(box_lower2(c, p, x, y, z, x + (1 << s), y + (1 << s), z + (1 << s)), b.d2);
+        if (far) n.pruned++;
+        return far;
+    };
+    auto leaf = [&](uint32_t ci) {
         if (ci != first_cell && ci != last_cell) { last_cell = ci; test_cell(g, p, ci, b, n); }
-        return;
-    }
-    int level = 0;
-    st.set(0, top_w, 0u);
-    while (level >= 0) {
-        const uint32_t nw = st.w(level), idx = st.i(level);
-        const int l = int(nw & 3u);
-        if (idx >= (1u << (3 * l))) {                   // this node is done: back to its parent
-            level--;
-            if (level >= 0) {
-                rs += int(st.w(level) & 3u);
-                const int keep = ~((1 << rs) - 1);
-                ox &= keep; oy &= keep; oz &= keep;
-            }
-            continue;
-        }
-        st.set_i(level, idx + 1u);
-        const int m = (1 << l) - 1, s = rs - l;
-        if (s < 0) continue;                            // not a valid voxel map
-        const int cx = ox + ((int(idx) & m) << s), cy = oy + (((int(idx) >> l) & m) << s), cz = oz + ((int(idx) >> (2 * l)) << s);
-        if (beyond(box_lower2(c, p, cx, cy, cz, cx + (1 << s), cy + (1 << s), cz + (1 << s)), b.d2)) { n.pruned++; continue; }
-        const uint32_t cw = g.word((nw >> 2) + idx);
-        if (!(cw & 3u)) {
-            const uint32_t ci = cw >> 2;
-            if (ci != first_cell && ci != last_cell) { last_cell = ci; test_cell(g, p, ci, b, n); }
-        } else if (level + 1 < kMaxLevels) {
-            level++;
-            st.set(level, cw, 0u);
-            rs = s; ox = cx; oy = cy; oz = cz;
-        }
-    }
+        return false;
+    };
+    if (prune(tx << c.shift, ty << c.shift, tz << c.shift, c.shift)) return;       // before the word is read
+    const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
+    if (!(top_w & 3u)) leaf(top_w >> 2);
+    else blocks::descend_top(g, st, top_w, tx, ty, tz, prune, leaf);
 }
 
 /// the answer for (p, r) over the grid g: equal, bit for bit, to brute_force over all triangles
@@ -254,15 +205,7 @@ HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r,
     const int tx = vx >> c.shift, ty = vy >> c.shift, tz = vz >> c.shift;
 
     // its cell
-    uint32_t w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
-    int depth = 0;
-    while (w & 3u) {
-        const int k = int(w & 3u);
-        depth += k;
-        const int s = c.shift - depth, m = (1 << k) - 1;
-        w = g.word((w >> 2) + uint32_t(((vx >> s) & m) + ((((vy >> s) & m) + (((vz >> s) & m) << k)) << k)));
-    }
-    const uint32_t first_cell = w >> 2;
+    const uint32_t first_cell = walk::descend(g, g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz))), vx, vy, vz) >> 2;
     const CellRec c0 = test_cell(g, p, first_cell, b, n);
 
     // does the ball (p, sqrt(best)) stay inside the cell's box?  faces on the grid boundary have nothing behind them

@@ -59,7 +59,7 @@
 #ifndef HAGRID_OVERLAP_H
 #define HAGRID_OVERLAP_H
 
-#include "closest.h"
+#include "block_walk.h"
 #include "grid.h"
 #include "multi_hit.h"
 #include "prims.h"
@@ -68,10 +68,7 @@
 namespace hagrid {
 namespace overlap {
 
-using closest::GridConsts;
-using closest::CellRec;
-using closest::ArrayStack;
-using closest::kMaxLevels;
+// GridConsts, CellRec, ArrayStack, kMaxLevels: block_walk.h, which names them in this namespace as well
 
 constexpr int kMaxIds = 8;
 
@@ -220,52 +217,25 @@ HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bo
     }
 }
 
-/// one top-level cell of the range: descend its sub-blocks while their voxel ranges meet the box's
+/// one top-level cell of the range: descend its sub-blocks (block_walk.h) while their voxel ranges meet the box's
 template <typename G, typename S, typename L>
 HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3& hi, bool any, const VoxelRange& r, int tx, int ty, int tz, uint32_t& last_cell,
                                   L& list, Counts& n) {
     const GridConsts& c = g.c;
-    int rs = c.shift;                                   // the current node covers 2^rs voxels per axis from (ox, oy, oz)
-    int ox = tx << rs, oy = ty << rs, oz = tz << rs;
+    auto prune = [&](int x, int y, int z, int s) {
+        const bool out = misses(r, x, y, z, s);
+        if (out) n.pruned++;
+        return out;
+    };
+    auto leaf = [&](uint32_t ci) {                      // true: ANY has its triangle
+        if (ci == last_cell) return false;
+        last_cell = ci;
+        test_cell(g, lo, hi, any, ci, list, n);
+        return any && list.found();
+    };
     const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
-    if (!(top_w & 3u)) {
-        const uint32_t ci = top_w >> 2;
-        if (ci != last_cell) { last_cell = ci; test_cell(g, lo, hi, any, ci, list, n); }
-        return;
-    }
-    int level = 0;
-    st.set(0, top_w, 0u);
-    while (level >= 0) {
-        const uint32_t nw = st.w(level), idx = st.i(level);
-        const int l = int(nw & 3u);
-        if (idx >= (1u << (3 * l))) {                   // this node is done: back to its parent
-            level--;
-            if (level >= 0) {
-                rs += int(st.w(level) & 3u);
-                const int keep = ~((1 << rs) - 1);
-                ox &= keep; oy &= keep; oz &= keep;
-            }
-            continue;
-        }
-        st.set_i(level, idx + 1u);
-        const int m = (1 << l) - 1, s = rs - l;
-        if (s < 0) continue;                            // not a valid voxel map
-        const int cx = ox + ((int(idx) & m) << s), cy = oy + (((int(idx) >> l) & m) << s), cz = oz + ((int(idx) >> (2 * l)) << s);
-        if (misses(r, cx, cy, cz, s)) { n.pruned++; continue; }
-        const uint32_t cw = g.word((nw >> 2) + idx);
-        if (!(cw & 3u)) {
-            const uint32_t ci = cw >> 2;
-            if (ci != last_cell) {
-                last_cell = ci;
-                test_cell(g, lo, hi, any, ci, list, n);
-                if (any && list.found()) return;
-            }
-        } else if (level + 1 < kMaxLevels) {
-            level++;
-            st.set(level, cw, 0u);
-            rs = s; ox = cx; oy = cy; oz = cz;
-        }
-    }
+    if (!(top_w & 3u)) leaf(top_w >> 2);
+    else blocks::descend_top(g, st, top_w, tx, ty, tz, prune, leaf);
 }
 
 /// the answer for the box [lo, hi] over the grid g: equal to brute_force over all triangles (with ANY: some member of S, or none).

@@ -9,8 +9,9 @@ import numpy as np
 
 from hagrid_amd import scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = os.path.join(ROOT, "include")
+import _host
+from _host import ROOT, INC, bits, oracle_grid, oracle_grid_arrays          # names the tests and the fixture generator use
+
 FIXTURE = os.path.join(ROOT, "tests", "golden", "closest.npz")
 SCENES = ("soup", "mesh")
 NUM_QUERIES = 4096
@@ -66,10 +67,6 @@ def fixture_queries(tris: np.ndarray) -> np.ndarray:
     return q
 
 
-def bits(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def assert_results_equal(got: np.ndarray, want: np.ndarray, what: str):
     """CLOSEST_DTYPE records: id, feature, side equal, d2 and q bit-equal (so the whole 32 bytes), no query excepted"""
     g = np.ascontiguousarray(got).view(np.uint32).reshape(-1, 8); w = np.ascontiguousarray(want).view(np.uint32).reshape(-1, 8)
@@ -80,18 +77,11 @@ def assert_results_equal(got: np.ndarray, want: np.ndarray, what: str):
 
 # ---- tests/cpp/closest_host.cpp ------------------------------------------------------------------------------------------------
 
-def build_host(directory) -> str:
-    """tests/cpp/closest_host.cpp with the flags tests/_multi_hit.py uses for multi_hit_host.cpp"""
-    exe = os.path.join(str(directory), "closest_host")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
-                    os.path.join(ROOT, "tests", "cpp", "closest_host.cpp"), "-o", exe], check=True)
-    return exe
+def build_host(directory, sanitize: bool = False) -> str:
+    return _host.build_host("closest_host", directory, sanitize)
 
 
-def _put(directory, name, arr) -> str:
-    path = os.path.join(str(directory), name + ".bin")
-    np.ascontiguousarray(arr).tofile(path)
-    return path
+_put = _host.put
 
 
 def host_pairs(exe: str, directory, tris: np.ndarray, points: np.ndarray) -> dict:
@@ -122,33 +112,14 @@ def host_walk(exe: str, directory, grid: dict, tris: np.ndarray, points: np.ndar
     """closest_query of include/hagrid/closest.h over grid arrays (keys entries, ref_ids, cells | small_cells, bbox_min, bbox_max, dims, shift: what
     api.Grid.download returns): (CLOSEST_DTYPE records, per-query counts (n, 3) int32: cells visited, triangles tested, pruned)"""
     d = str(directory)
-    small = grid.get("small_cells") is not None
     n = points.shape[0]
     par = os.path.join(d, "walk_params.bin")
     with open(par, "wb") as f:
-        f.write(struct.pack("<i3ii3f3fi", 1 if small else 0, *[int(v) for v in grid["dims"]], int(grid["shift"]),
-                            *[float(v) for v in grid["bbox_min"]], *[float(v) for v in grid["bbox_max"]], n))
+        f.write(_host.grid_header(grid) + struct.pack("<i", n))
     out, counts = os.path.join(d, "walk_out.bin"), os.path.join(d, "walk_counts.bin")
-    subprocess.run([exe, "walk", par, _put(d, "entries", grid["entries"]), _put(d, "cells", grid["small_cells"] if small else grid["cells"]),
-                    _put(d, "refs", grid["ref_ids"]), _put(d, "tris", np.ascontiguousarray(tris, dtype=np.float32)),
+    subprocess.run([exe, "walk", par, *_host.grid_files(d, grid), _put(d, "tris", np.ascontiguousarray(tris, dtype=np.float32)),
                     _put(d, "points", np.ascontiguousarray(points, dtype=np.float32)), out, counts], check=True, timeout=1200)
     return np.fromfile(out, dtype=scene.CLOSEST_DTYPE), np.fromfile(counts, dtype=np.int32).reshape(n, 3)
-
-
-def oracle_grid_arrays(G) -> dict:
-    """the arrays of an oracle.Grid in the shape host_walk takes"""
-    return {"entries": np.array(G.entries), "ref_ids": np.array(G.ref_ids), "cells": None if G.cells is None else np.array(G.cells),
-            "small_cells": None if G.small_cells is None else np.array(G.small_cells),
-            "bbox_min": G.bbox_min, "bbox_max": G.bbox_max, "dims": G.dims, "shift": G.shift}
-
-
-def oracle_grid(tris: np.ndarray, compress: bool, subset_only: bool):
-    """the construction sequence of the CPU oracle with either expansion mode"""
-    from oracle import oracle as O
-    G = O.Grid.build(tris).merge().flatten().expand(tris, 3, subset_only=subset_only)
-    if compress:
-        G.compress()
-    return G
 
 
 # ---- float64, written independently: the projection onto the plane, clamped into the triangle region by region ---------------------

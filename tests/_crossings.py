@@ -8,10 +8,10 @@ import numpy as np
 
 from hagrid_amd import scene
 
+import _host
 import _multi_hit as M
+from _host import ROOT, INC, oracle_grid, oracle_grid_arrays                # names the tests use
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = os.path.join(ROOT, "include")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "crossings.npz")
 SCENES = ("soup", "mesh", "solids")
 DETAIL = 0.05
@@ -134,11 +134,7 @@ def rec_bits(records) -> np.ndarray:
 # ---- tests/cpp/crossings_host.cpp ------------------------------------------------------------------------------------------------
 
 def build_host(directory, sanitize: bool = False) -> str:
-    exe = os.path.join(str(directory), "crossings_host_san" if sanitize else "crossings_host")
-    flags = M.SANITIZE if sanitize else ["-O2"]
-    subprocess.run(["g++", "-std=c++11", *flags, "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
-                    os.path.join(ROOT, "tests", "cpp", "crossings_host.cpp"), "-o", exe], check=True)
-    return exe
+    return _host.build_host("crossings_host", directory, sanitize)
 
 
 def _query_params(form: int, n: int, dirs, winding: bool, lattice) -> tuple[bytes, int]:
@@ -162,37 +158,21 @@ def host_query(exe: str, directory, tris: np.ndarray, grid: dict | None = None, 
     items = rays if form == 0 else (points if form == 1 else np.zeros(0, np.float32))
     n = int(np.prod(lattice[2])) if form == 2 else int(np.ascontiguousarray(items).view(np.float32).size // (8 if form == 0 else 4))
     params, m = _query_params(form, n, dirs, winding, lattice)
-    names = {"tris": np.ascontiguousarray(tris, dtype=np.float32), "items": np.ascontiguousarray(items).view(np.float32)}
-    args = [exe, ("paged" if paged else "brute") if grid is None else "walk", os.path.join(d, "cx_params.bin")]
+    par = os.path.join(d, "cx_params.bin")
+    args = [exe, ("paged" if paged else "brute") if grid is None else "walk", par]
     if grid is not None:
-        small = grid.get("small_cells") is not None
-        params += struct.pack("<ii3ii3f3f", 1 if small else 0, int(page), *[int(v) for v in grid["dims"]], int(grid["shift"]),
-                              *[float(v) for v in grid["bbox_min"]], *[float(v) for v in grid["bbox_max"]])
-        names.update({"entries": grid["entries"], "cells": grid["small_cells"] if small else grid["cells"], "refs": grid["ref_ids"]})
-        args += [os.path.join(d, "cx_entries.bin"), os.path.join(d, "cx_cells.bin"), os.path.join(d, "cx_refs.bin")]
-    for key, arr in names.items():
-        np.ascontiguousarray(arr).tofile(os.path.join(d, "cx_" + key + ".bin"))
-    with open(os.path.join(d, "cx_params.bin"), "wb") as f:
+        params += _host.grid_header(grid) + struct.pack("<i", int(page))
+        args += _host.grid_files(d, grid, "cx_")
+    with open(par, "wb") as f:
         f.write(params)
     out = os.path.join(d, "cx_out.bin")
-    subprocess.run(args + [os.path.join(d, "cx_tris.bin"), os.path.join(d, "cx_items.bin"), out], check=True, timeout=900)
+    subprocess.run(args + [_host.put(d, "cx_tris", np.ascontiguousarray(tris, dtype=np.float32)), _host.put(d, "cx_items", np.ascontiguousarray(items).view(np.float32)), out],
+                   check=True, timeout=900)
     raw = np.fromfile(out, dtype=np.uint8)
     nrec = n * m * 16
     tail = raw[nrec + 4 * n:].view(np.int64)
     return {"records": raw[:nrec].view(scene.HIT_DTYPE).reshape(n, m), "inside": raw[nrec:nrec + 4 * n].view(np.int32), "totals": tail[:4].copy(),
             "excess": int(tail[4])}
-
-
-oracle_grid_arrays = M.oracle_grid_arrays
-
-
-def oracle_grid(tris: np.ndarray, compress: bool, subset_only: bool):
-    """the construction sequence of the CPU oracle with either expansion mode"""
-    from oracle import oracle as O
-    G = O.Grid.build(tris).merge().flatten().expand(tris, 3, subset_only=subset_only)
-    if compress:
-        G.compress()
-    return G
 
 
 def empty_records(rays: np.ndarray) -> np.ndarray:

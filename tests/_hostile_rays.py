@@ -15,6 +15,7 @@ import numpy as np
 from hagrid_amd import scene
 
 import _closest as K
+import _host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "hostile_rays.npz")
@@ -46,8 +47,7 @@ PLANE_MARGIN = 1e-3
 AMBIGUOUS_CAP = 0.05                # of family (k); no other family may hold an ambiguous ray
 
 
-def bits(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+bits = _host.bits
 
 
 def oracle_grid(tris, params: dict, compress: bool):

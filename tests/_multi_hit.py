@@ -9,8 +9,9 @@ import numpy as np
 
 from hagrid_amd import scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = os.path.join(ROOT, "include")
+import _host
+from _host import ROOT, INC, SANITIZE, bits, oracle_grid_arrays               # names the tests use
+
 FIXTURE = os.path.join(ROOT, "tests", "golden", "multi_hit.npz")
 KMAX = 8
 SCENES = ("soup", "mesh")
@@ -64,44 +65,19 @@ def hit_histogram(ids: np.ndarray) -> list:
     return np.bincount((ids >= 0).sum(axis=1), minlength=ids.shape[1] + 1).tolist()
 
 
-SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-
-
 def build_host(directory, sanitize: bool = False) -> str:
-    """tests/cpp/multi_hit_host.cpp with the flags tests/test_frame_cpu.py uses for frame_host.cpp; sanitize: a stand-alone binary with the sanitizers of SANITIZE"""
-    exe = os.path.join(str(directory), "multi_hit_host_san" if sanitize else "multi_hit_host")
-    subprocess.run(["g++", "-std=c++11", *(SANITIZE if sanitize else ["-O2"]), "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
-                    os.path.join(ROOT, "tests", "cpp", "multi_hit_host.cpp"), "-o", exe], check=True)
-    return exe
+    return _host.build_host("multi_hit_host", directory, sanitize)
 
 
 def host_walk(exe: str, directory, grid: dict, tris: np.ndarray, rays: np.ndarray, k: int) -> np.ndarray:
     """The host walk over grid arrays (keys entries, ref_ids, cells | small_cells, bbox_min, bbox_max, dims, shift: what api.Grid.download
     returns); the hits as an (n, k) HIT_DTYPE array."""
     d = str(directory)
-    small = grid.get("small_cells") is not None
     n = rays.shape[0]
-    params = struct.pack("<ii3ii3f3fi", 1 if small else 0, k, *[int(v) for v in grid["dims"]], int(grid["shift"]),
-                         *[float(v) for v in grid["bbox_min"]], *[float(v) for v in grid["bbox_max"]], n)
-    names = {}
-    for key, arr in (("entries", grid["entries"]), ("cells", grid["small_cells"] if small else grid["cells"]), ("refs", grid["ref_ids"]),
-                     ("tris", np.ascontiguousarray(tris, dtype=np.float32)), ("rays", np.ascontiguousarray(rays, dtype=np.float32))):
-        names[key] = os.path.join(d, key + ".bin")
-        np.ascontiguousarray(arr).tofile(names[key])
-    with open(os.path.join(d, "params.bin"), "wb") as f:
-        f.write(params)
+    par = os.path.join(d, "params.bin")
+    with open(par, "wb") as f:
+        f.write(_host.grid_header(grid) + struct.pack("<ii", k, n))
     out = os.path.join(d, "out.bin")
-    subprocess.run([exe, "walk", os.path.join(d, "params.bin"), names["entries"], names["cells"], names["refs"], names["tris"], names["rays"], out],
-                   check=True, timeout=600)
+    subprocess.run([exe, "walk", par, *_host.grid_files(d, grid), _host.put(d, "tris", np.ascontiguousarray(tris, dtype=np.float32)),
+                    _host.put(d, "rays", np.ascontiguousarray(rays, dtype=np.float32)), out], check=True, timeout=600)
     return np.fromfile(out, dtype=scene.HIT_DTYPE).reshape(n, k)
-
-
-def oracle_grid_arrays(G) -> dict:
-    """the arrays of an oracle.Grid in the shape host_walk takes"""
-    return {"entries": np.array(G.entries), "ref_ids": np.array(G.ref_ids), "cells": None if G.cells is None else np.array(G.cells),
-            "small_cells": None if G.small_cells is None else np.array(G.small_cells),
-            "bbox_min": G.bbox_min, "bbox_max": G.bbox_max, "dims": G.dims, "shift": G.shift}
-
-
-def bits(a) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)

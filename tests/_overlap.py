@@ -9,8 +9,9 @@ import numpy as np
 
 from hagrid_amd import scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INC = os.path.join(ROOT, "include")
+import _host
+from _host import ROOT, INC, oracle_grid, oracle_grid_arrays                # names the tests use
+
 FIXTURE = os.path.join(ROOT, "tests", "golden", "overlap.npz")
 SCENES = ("soup", "mesh")
 NUM_BOXES = 4096
@@ -172,17 +173,11 @@ def bounds_check(tris: np.ndarray, boxes: np.ndarray) -> np.ndarray:
 
 # ---- tests/cpp/overlap_host.cpp -------------------------------------------------------------------------------------------------
 
-def build_host(directory) -> str:
-    exe = os.path.join(str(directory), "overlap_host")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-Wall", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC,
-                    os.path.join(ROOT, "tests", "cpp", "overlap_host.cpp"), "-o", exe], check=True)
-    return exe
+def build_host(directory, sanitize: bool = False) -> str:
+    return _host.build_host("overlap_host", directory, sanitize)
 
 
-def _put(directory, name, arr) -> str:
-    path = os.path.join(str(directory), name + ".bin")
-    np.ascontiguousarray(arr).tofile(path)
-    return path
+_put = _host.put
 
 
 def _rows(boxes) -> np.ndarray:
@@ -216,33 +211,14 @@ def host_walk(exe: str, directory, grid: dict, tris: np.ndarray, boxes: np.ndarr
     """overlap_query of include/hagrid/overlap.h over grid arrays (keys entries, ref_ids, cells | small_cells, bbox_min, bbox_max, dims, shift: what
     api.Grid.download returns): (ids (n, k), counts, per-box totals (n, 3) int32: cells visited, tests evaluated, sub-blocks pruned)"""
     d = str(directory)
-    small = grid.get("small_cells") is not None
     b = _rows(boxes); n = b.shape[0]
     par = os.path.join(d, "walk_params.bin")
     with open(par, "wb") as f:
-        f.write(struct.pack("<i3ii3f3f3i", 1 if small else 0, *[int(v) for v in grid["dims"]], int(grid["shift"]),
-                            *[float(v) for v in grid["bbox_min"]], *[float(v) for v in grid["bbox_max"]], n, k, 1 if any_ else 0))
+        f.write(_host.grid_header(grid) + struct.pack("<3i", n, k, 1 if any_ else 0))
     ids, counts, totals = os.path.join(d, "walk_ids.bin"), os.path.join(d, "walk_counts.bin"), os.path.join(d, "walk_totals.bin")
-    subprocess.run([exe, "walk", par, _put(d, "entries", grid["entries"]), _put(d, "cells", grid["small_cells"] if small else grid["cells"]),
-                    _put(d, "refs", grid["ref_ids"]), _put(d, "tris", np.ascontiguousarray(tris, dtype=np.float32)), _put(d, "boxes", b), ids, counts, totals],
+    subprocess.run([exe, "walk", par, *_host.grid_files(d, grid), _put(d, "tris", np.ascontiguousarray(tris, dtype=np.float32)), _put(d, "boxes", b), ids, counts, totals],
                    check=True, timeout=1200)
     return np.fromfile(ids, dtype=np.int32).reshape(n, k), np.fromfile(counts, dtype=np.int32), np.fromfile(totals, dtype=np.int32).reshape(n, 3)
-
-
-def oracle_grid_arrays(G) -> dict:
-    """the arrays of an oracle.Grid in the shape host_walk takes"""
-    return {"entries": np.array(G.entries), "ref_ids": np.array(G.ref_ids), "cells": None if G.cells is None else np.array(G.cells),
-            "small_cells": None if G.small_cells is None else np.array(G.small_cells),
-            "bbox_min": G.bbox_min, "bbox_max": G.bbox_max, "dims": G.dims, "shift": G.shift}
-
-
-def oracle_grid(tris: np.ndarray, compress: bool, subset_only: bool):
-    """the construction sequence of the CPU oracle with either expansion mode"""
-    from oracle import oracle as O
-    G = O.Grid.build(tris).merge().flatten().expand(tris, 3, subset_only=subset_only)
-    if compress:
-        G.compress()
-    return G
 
 
 def assert_answers_equal(got_ids, got_counts, want_ids, want_counts, what: str):

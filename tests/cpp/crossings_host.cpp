@@ -6,14 +6,11 @@
 // construction format with a page capacity chosen at run time (1 .. 8).
 //
 //   crossings_host brute|paged PARAMS TRIS ITEMS OUT                      PARAMS: i32 form, i32 n, i32 m, i32 winding, 9 f32 dirs, 3 f32 origin, 3 f32 size, 3 i32 lattice n
-//   crossings_host walk  PARAMS ENTRIES CELLS REFS TRIS ITEMS OUT        PARAMS: the same, then i32 small, i32 page, 3 i32 top-level dims, i32 shift, 3 f32 bbox min, 3 f32 bbox max
+//   crossings_host walk  PARAMS ENTRIES CELLS REFS TRIS ITEMS OUT        PARAMS: the same, then the grid header (host_support.h), i32 page
 // form 0: ITEMS = n rays (32 bytes), m = 1; form 1: ITEMS = n points (16 bytes: x, y, z, reach); form 2: the lattice, ITEMS is not read.
 // OUT: n * m Hit-shaped records, then n int32 `inside` (forms 1 and 2; zeros for form 0), then int64[4] totals (items, cells, tests, flushes) and the int64
 // largest excess of a ray's flushes over ceil(count / page) + 1 (<= 0 when the bound holds; the brute force leaves the last four at 0).
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
@@ -22,71 +19,16 @@
 #include "hagrid/prims.h"
 #include "hagrid/grid.h"
 #include "hagrid/crossings.h"
+#include "host_support.h"
 
 using namespace hagrid;
+using namespace host_support;
 namespace hx = hagrid::crossings;
 
 namespace {
 
-template <typename T>
-std::vector<T> read_file(const char* name) {
-    std::vector<T> v;
-    FILE* f = fopen(name, "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", name); exit(2); }
-    fseek(f, 0, SEEK_END);
-    const long bytes = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    v.resize(size_t(bytes) / sizeof(T));
-    if (!v.empty() && fread(v.data(), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "short read of %s\n", name); exit(2); }
-    fclose(f);
-    return v;
-}
-
-struct Params {
-    std::vector<char> bytes;
-    size_t pos = 0;
-    template <typename T> T get() {
-        T t;
-        if (pos + sizeof(T) > bytes.size()) { fprintf(stderr, "parameter file too short\n"); exit(2); }
-        memcpy(&t, bytes.data() + pos, sizeof(T));
-        pos += sizeof(T);
-        return t;
-    }
-    vec3 get3() { const float x = get<float>(), y = get<float>(), z = get<float>(); return vec3(x, y, z); }
-};
-
-struct HostGrid {
-    hx::WalkConsts c;
-    bool small;
-    const Entry* entries;
-    const Cell* cells;
-    const SmallCell* small_cells;
-    const int* refs;
-    const Tri* tris;
-    size_t num_cells, num_refs, num_tris;
-
-    hx::CellRec cell_at(int vx, int vy, int vz) const {
-        const uint32_t index = lookup_entry(entries, c.shift, c.top, ivec3(vx, vy, vz));
-        if (index >= num_cells) { fprintf(stderr, "walk: cell index beyond the cells\n"); exit(2); }
-        hx::CellRec b;
-        if (small) {
-            const SmallCell& s = small_cells[index];
-            b.lx = s.min.x; b.ly = s.min.y; b.lz = s.min.z; b.hx = s.max.x; b.hy = s.max.y; b.hz = s.max.z; b.begin = s.begin; b.end = 0;
-        } else {
-            const Cell& s = cells[index];
-            b.lx = s.min.x; b.ly = s.min.y; b.lz = s.min.z; b.hx = s.max.x; b.hy = s.max.y; b.hz = s.max.z; b.begin = s.begin; b.end = s.end;
-        }
-        return b;
-    }
-    int ref(int i) const {
-        if (i < 0 || size_t(i) >= num_refs) { fprintf(stderr, "walk: reference index beyond ref_ids\n"); exit(2); }
-        return refs[i];
-    }
-    const Tri& tri(int id) const {
-        if (id < 0 || size_t(id) >= num_tris) { fprintf(stderr, "walk: triangle id beyond the triangles\n"); exit(2); }
-        return tris[id];
-    }
-};
+// the accessor of cell_walk.h over host arrays, every index checked, and tri(id)
+typedef HostGrid<kEndUnread> RayGrid;
 
 struct Query {
     int form, n, m, winding;
@@ -112,31 +54,17 @@ int main(int argc, char** argv) {
     q.lat.x = p.get<int32_t>(); q.lat.y = p.get<int32_t>(); q.lat.z = p.get<int32_t>();
     if (q.form < 0 || q.form > 2 || q.n < 0 || (q.m != 1 && q.m != 3) || (q.form == 0 && q.m != 1)) { fprintf(stderr, "crossings_host: bad form, n or m\n"); return 2; }
 
-    HostGrid g = HostGrid();
+    RayGrid g;
     g.c.set(ivec3(1), 0, vec3(0.0f), vec3(1.0f));          // the brute force reads no grid
     int page = hx::kMaxPage;
-    std::vector<uint32_t> entries;
-    std::vector<char> cells;
-    std::vector<int32_t> refs;
     if (walk) {
-        const int small = p.get<int32_t>();
+        const GridHeader h = p.get_grid_header();
         page = p.get<int32_t>();
-        ivec3 top;
-        top.x = p.get<int32_t>(); top.y = p.get<int32_t>(); top.z = p.get<int32_t>();
-        const int shift = p.get<int32_t>();
-        const vec3 lo = p.get3(), hi = p.get3();
         if (page < 1 || page > hx::kMaxPage) { fprintf(stderr, "walk: the page capacity must be 1 .. 8\n"); return 2; }
-        entries = read_file<uint32_t>(argv[3]); cells = read_file<char>(argv[4]); refs = read_file<int32_t>(argv[5]);
-        g.c.set(top << shift, shift, lo, hi);
-        g.small = small != 0;
-        g.entries = reinterpret_cast<const Entry*>(entries.data());
-        g.cells = small ? nullptr : reinterpret_cast<const Cell*>(cells.data());
-        g.small_cells = small ? reinterpret_cast<const SmallCell*>(cells.data()) : nullptr;
-        g.num_cells = cells.size() / (small ? sizeof(SmallCell) : sizeof(Cell));
-        g.refs = refs.data(); g.num_refs = refs.size();
+        g.load(h, argv[3], argv[4], argv[5]);
     }
-    const std::vector<Tri> tris = read_file<Tri>(argv[walk ? 6 : 3]);
-    g.tris = tris.data(); g.num_tris = tris.size();
+    g.tris = read_file<Tri>(argv[walk ? 6 : 3]);
+    const std::vector<Tri>& tris = g.tris;
     const char* items_name = argv[walk ? 7 : 4];
     std::vector<Ray> rays;
     std::vector<float> points;

@@ -15,6 +15,12 @@ from hagrid_amd import scene
 ROOT = K.ROOT
 INC = K.INC
 
+# The column sums of the walk's per-query counters (cells visited, triangles tested, sub-blocks pruned) over the 4096 fixture queries, by (scene, expansion
+# mode); Cell and SmallCell grids give the same.  Taken at the parent of the commit that moved the descent into include/hagrid/block_walk.h: the order of
+# the visits is part of a counter, so a walk that visits in another order misses these.
+WALK_COUNTERS = {("soup", True): (50624, 55458, 453184), ("soup", False): (50606, 55426, 452402),
+                 ("mesh", True): (80358, 162644, 1602307), ("mesh", False): (79885, 161857, 1588694)}
+
 # 4 x the largest deviation measured for the operation order of include/hagrid/closest.h on the two fixture scenes (test_statement_against_float64)
 TOLERANCE = 4 * 3.76e-8
 
@@ -163,7 +169,8 @@ def test_statement_against_float64(fixture, scenes):
 @pytest.mark.parametrize("compress", [False, True])
 @pytest.mark.parametrize("scene_name", K.SCENES)
 def test_host_walk_reproduces_the_fixture(fixture, scenes, host, scene_name, compress, subset_only):
-    """id, feature and side equal, d2 and q bit-equal, for all 4096 queries, over Cell and SmallCell grids of the CPU oracle, both expansion modes"""
+    """id, feature and side equal, d2 and q bit-equal, for all 4096 queries, over Cell and SmallCell grids of the CPU oracle, both expansion modes; the
+    counters' sums are the pinned ones"""
     exe, d = host
     tris, q = scenes[scene_name]
     G = K.oracle_grid(tris, compress, subset_only)
@@ -172,6 +179,7 @@ def test_host_walk_reproduces_the_fixture(fixture, scenes, host, scene_name, com
     K.assert_results_equal(got, K.fixture_results(fixture, scene_name), f"{scene_name} compress={compress} subset_only={subset_only}")
     trivial = (q[:, 3] < 0) | np.isnan(q[:, 0:3]).any(axis=1)
     assert (counts[trivial] == 0).all() and (counts[~trivial, 0] >= 1).all()
+    assert tuple(int(v) for v in counts.sum(axis=0, dtype=np.int64)) == WALK_COUNTERS[scene_name, subset_only]
 
 
 def test_walk_is_no_brute_force(scenes, host):
@@ -185,6 +193,15 @@ def test_walk_is_no_brute_force(scenes, host):
     print("triangles tested per near-surface query:", mean, "cells:", counts[K.NEAR, 0].mean(), "pruned:", counts[K.NEAR, 2].mean())
     assert mean < tris.shape[0] / 10
     assert counts[K.NEAR, 2].sum() > 0
+
+
+def test_host_walk_under_sanitizers(fixture, scenes, tmp_path):
+    """the host program with -fsanitize=address,undefined as a stand-alone binary: the walk (its stack is an array indexed at run time) over a SmallCell grid,
+    the first 256 queries of the soup"""
+    exe = K.build_host(tmp_path, sanitize=True)
+    tris, q = scenes["soup"]
+    got, _ = K.host_walk(exe, tmp_path, K.oracle_grid_arrays(K.oracle_grid(tris, True, True)), tris, q[:256])
+    K.assert_results_equal(got, K.fixture_results(fixture, "soup")[:256], "sanitized walk")
 
 
 def test_records_and_entry_point(fixture):
@@ -204,7 +221,16 @@ def test_records_and_entry_point(fixture):
     assert r.returncode == 0, r.stderr
 
 
+def header_alone(name):
+    return subprocess.run(["g++", "-std=c++11", "-Wall", "-Werror", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC, "-fsyntax-only", "-x", "c++",
+                           os.path.join(INC, "hagrid", name)], capture_output=True, text=True)
+
+
 def test_closest_header_is_cxx11():
-    r = subprocess.run(["g++", "-std=c++11", "-Wall", "-Werror", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", INC, "-fsyntax-only", "-x", "c++",
-                        os.path.join(INC, "hagrid", "closest.h")], capture_output=True, text=True)
+    r = header_alone("closest.h")
+    assert r.returncode == 0, r.stderr
+
+
+def test_block_walk_header_is_cxx11():
+    r = header_alone("block_walk.h")
     assert r.returncode == 0, r.stderr

@@ -17,6 +17,16 @@ ROOT = V.ROOT
 INC = V.INC
 
 
+# The column sums of the walk's per-box counters (cells visited, tests evaluated, sub-blocks pruned) over the 4096 fixture boxes, by scene, for k = 8 and for
+# k = 1 with ANY; both cell formats and both expansion modes give the same.  Taken at the parent of the commit that moved the descent into
+# include/hagrid/block_walk.h: the order of the visits is part of a counter, so a walk that visits in another order misses these.
+WALK_COUNTERS = {"soup": ((2194470, 88109, 1689033), (10876, 10294, 182760)), "mesh": ((494334, 91860, 2461577), (14319, 17235, 822295))}
+
+
+def sums(totals):
+    return tuple(int(v) for v in totals.sum(axis=0, dtype=np.int64))
+
+
 @pytest.fixture(scope="module")
 def fixture():
     import __graft_entry__ as g
@@ -134,7 +144,7 @@ def test_fixture_semantics(fixture, scenes):
 @pytest.mark.parametrize("scene_name", V.SCENES)
 def test_host_walk_reproduces_the_fixture(fixture, scenes, unbounded, host, scene_name, compress, subset_only):
     """ids and counts equal for all 4096 boxes and the 384 with infinite bounds, for k = 1, 2, 3, 5, 8, over Cell and SmallCell grids of the CPU oracle,
-    both expansion modes; the list for k is a prefix of the list for k + 1"""
+    both expansion modes; the list for k is a prefix of the list for k + 1; the counters' sums for k = 8 and for ANY are the pinned ones"""
     exe, d = host
     tris, boxes = scenes[scene_name]
     G = V.oracle_grid(tris, compress, subset_only)
@@ -149,6 +159,8 @@ def test_host_walk_reproduces_the_fixture(fixture, scenes, unbounded, host, scen
         want_ids, want_counts = V.expected(fixture, scene_name, k)
         V.assert_answers_equal(ids, counts, want_ids, want_counts, f"{scene_name} compress={compress} subset_only={subset_only} k={k}")
         assert (totals[inactive] == 0).all() and inactive.sum() == 16
+        if k == V.KMAX:
+            assert sums(totals) == WALK_COUNTERS[scene_name][0]
         if prev is not None:
             assert (ids[:, :prev.shape[1]] == prev).all(), "the prefix property"
         prev = ids
@@ -159,6 +171,7 @@ def test_host_walk_reproduces_the_fixture(fixture, scenes, unbounded, host, scen
     ids, counts, totals = V.host_walk(exe, d, arrays, tris, boxes, 1, any_=True)
     sizes = fixture[scene_name + "_sizes"]
     assert ((ids[:, 0] >= 0) == (sizes > 0)).all() and (counts == (sizes > 0)).all()
+    assert sums(totals) == WALK_COUNTERS[scene_name][1]
     hit = ids[:, 0] >= 0
     assert scene.overlap_pairs(tris[ids[hit, 0]], scene.clip_boxes(boxes, glo, ghi)[hit]).all() and (ids[hit, 0] >= boxes[hit, 3].view(np.int32)).all()
 
@@ -228,6 +241,19 @@ def test_paging_reproduces_the_whole_list(scenes, host):
     assert live.size == 0
     for i in range(n):
         assert pages[i] == full[i].tolist(), f"box {pick[i]}"
+
+
+def test_host_walk_under_sanitizers(fixture, scenes, tmp_path):
+    """the host program with -fsanitize=address,undefined as a stand-alone binary: the walk (its stack is an array indexed at run time) over a SmallCell grid,
+    the first 256 boxes of the soup, k = 8 and ANY"""
+    exe = V.build_host(tmp_path, sanitize=True)
+    tris, boxes = scenes["soup"]
+    arrays = V.oracle_grid_arrays(V.oracle_grid(tris, True, True))
+    ids, counts, _ = V.host_walk(exe, tmp_path, arrays, tris, boxes[:256], V.KMAX)
+    want_ids, want_counts = V.expected(fixture, "soup", V.KMAX)
+    V.assert_answers_equal(ids, counts, want_ids[:256], want_counts[:256], "sanitized walk")
+    ids, counts, _ = V.host_walk(exe, tmp_path, arrays, tris, boxes[:256], 1, any_=True)
+    assert ((ids[:, 0] >= 0) == (want_counts[:256] > 0)).all() and (counts == (want_counts[:256] > 0)).all()
 
 
 def test_lattice_neighbours_share_their_faces():

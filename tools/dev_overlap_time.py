@@ -5,6 +5,7 @@
            k = 1, k = 8 and ANY
   lattice  a 256^3 lattice over the scene box: k = 1 and ANY
   sphere   what a caller has to use without the box query: hagrid_closest_points on the box centres with r = half the box's own diagonal
+  nearest  the control of tools/dev_closest_time.py: the nearest-hit launch over the same construction format on 1024 x 1024 primary rays
 
 ONE process, the launches alternating after a warm-up, every launch between its own pair of events on the context's stream and under its own time limit (a
 launch that does not come back within --limit seconds ends the process with status 3: nothing else is started on the device).  Per box launch one more with
@@ -48,11 +49,12 @@ mem.set_option("traverse.image", 0)
 result = {"tool": "tools/dev_overlap_time.py", "source_hash": _build.source_hash(), "device": mem.device_info(), "boxes": nb, "lattice": lat, "launches": launches,
           "warmup": warmup, "scenes": {}}
 nv = lat ** 3
+W = 1024
 for name in scenes:
     tris = scene.make_soup(1000000) if name == "soup" else scene.make_stadium()
     N = tris.shape[0]
     d_tris = mem.upload(tris)
-    grid = api.build_all(mem, d_tris, N)
+    grid = api.build_all(mem, d_tris, N); api.setup_traversal(grid)
     lo, hi = scene.tris_bbox(tris)
     diag = scene.bbox_diagonal(lo, hi)
     edge = np.float32(0.01) * diag
@@ -66,7 +68,11 @@ for name in scenes:
     d_ids = mem.alloc(4 * most); d_counts = mem.alloc(4 * max(nb, nv)); d_res = mem.alloc(32 * nb); d_tot = mem.alloc(32)
     origin = lo; size = ((hi - lo) / np.float32(lat)).astype(np.float32); n3 = (lat, lat, lat)
     ANY = api.OVERLAP_ANY
-    variants = [("sphere", lambda: api.closest_points(grid, d_tris, d_pts, d_res, nb)),
+    cam = scene.camera(grid.bbox_min, grid.bbox_max)
+    d_rays = mem.alloc(32 * W * W); d_hits = mem.alloc(16 * W * W)
+    api.gen_primary_rays(mem, cam, float(cam[4]), W, W, d_rays)
+    variants = [("nearest", lambda: api.traverse_grid(grid, d_tris, d_rays, d_hits, W * W)),
+                ("sphere", lambda: api.closest_points(grid, d_tris, d_pts, d_res, nb)),
                 ("boxes_k1", lambda: api.overlap_boxes(grid, d_tris, d_boxes, nb, 1, d_ids, d_counts)),
                 ("boxes_k8", lambda: api.overlap_boxes(grid, d_tris, d_boxes, nb, 8, d_ids, d_counts)),
                 ("boxes_any", lambda: api.overlap_boxes(grid, d_tris, d_boxes, nb, 1, d_ids, d_counts, 0, ANY)),
@@ -106,7 +112,7 @@ for name in scenes:
                               "cells_per_query": round(c[1] / nb, 3), "tris_per_query": round(c[2] / nb, 3), "pruned_per_query": round(c[3] / nb, 3)}
     result["scenes"][name] = row
     print(json.dumps({name: row}), flush=True)
-    for p in (d_boxes, d_pts, d_ids, d_counts, d_res, d_tot, d_tris):
+    for p in (d_boxes, d_pts, d_ids, d_counts, d_res, d_tot, d_rays, d_hits, d_tris):
         mem.free(p)
     grid.free()
 
