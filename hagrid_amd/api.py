@@ -411,6 +411,40 @@ def count_crossings(grid: Grid, tris: int, rays: int, records: int, num_rays: in
                                               C.c_void_p(counters or 0), int(flags)), "count_crossings")
 
 
+def list_crossings(grid: Grid, tris: int, rays: int, num_rays: int, entries: int, capacity: int, offsets: int = 0, stride: int = 0, records: int = 0, counters: int = 0):
+    """Extension (hagrid_list_crossings): the crossings of count_crossings THEMSELVES, sorted by (t, id), 8 bytes each: float32 t; int32 key = id * 2 + entering.
+    offsets: a device int64[num_rays + 1] -- ray i owns the slots [offsets[i], offsets[i+1]) of `entries` (capacity slots) -- or 0 with stride = S >= 1: ray i owns
+    [i * S, (i + 1) * S).  A ray writes its first min(m, room) entries and fills the rest of its slots with the empty entry (the bits of tmax, -1); a pair of
+    offsets that is negative, decreasing or beyond the capacity has room 0.  records: 0, or the records of count_crossings (record.id > room: the list did not
+    fit); counters: 0, or a device int64[6] added to (rays, cells, tests, flushes, entries written, rays that did not fit).  Device addresses; asynchronous on
+    the manager's stream.  scene.ray_crossing_lists and scene.crossing_slots state it in numpy."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_list_crossings(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(rays or 0), int(num_rays), C.c_void_p(offsets or 0), int(stride),
+                                             C.c_void_p(entries or 0), int(capacity), C.c_void_p(records or 0), C.c_void_p(counters or 0), 0), "list_crossings")
+
+
+def crossing_lists(grid: Grid, tris, rays, num_rays: int) -> dict:
+    """count, scan, fill on torch tensors: count_crossings, torch.cumsum of the counts into int64 offsets, ONE scalar to the host (the total, which sizes the
+    output), list_crossings.  tris, rays: torch tensors on the device (or device addresses).  The manager must run on torch's current stream
+    (mem.use_stream(torch.cuda.current_stream().cuda_stream)).  Returns "offsets" int64 (n + 1,), "t" float32, "tri" int32 and "entering" bool (total,): the
+    crossings of ray i are offsets[i] .. offsets[i+1], sorted by (t, id); "entries" int32 (total, 2), the raw words (t is a view of it), and "records" int32
+    (n, 4): count, the bits of t_first, the bits of length, winding."""
+    import torch
+    n = int(num_rays)
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    dev = rays.device if hasattr(rays, "device") else torch.device("cuda", torch.cuda.current_device())
+    records = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    count_crossings(grid, ptr(tris), ptr(rays), records.data_ptr(), n)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum(records[:, 0], 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[-1].item())
+    entries = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    list_crossings(grid, ptr(tris), ptr(rays), n, entries.data_ptr() if total else 0, total, offsets=offsets.data_ptr())
+    return {"offsets": offsets, "t": entries.view(torch.float32)[:, 0], "tri": entries[:, 1] >> 1, "entering": (entries[:, 1] & 1) != 0, "entries": entries,
+            "records": records}
+
+
 def points_inside(grid: Grid, tris: int, points: int, n: int, inside: int, dirs=None, records: int = 0, counters: int = 0, flags: int = 0):
     """Extension (hagrid_points_inside): for each of n points (16 bytes: x, y, z, reach -- POINT_QUERY_DTYPE) whether it lies inside the closed surface the
     triangles form: a ray per direction (dirs: None = the three of scene.CROSSING_DIRS, or 1 or 3 host directions) from the point to `reach` (+inf: no
@@ -632,4 +666,4 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
-           "count_crossings", "points_inside", "inside_lattice", "INSIDE_WINDING"]
+           "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "INSIDE_WINDING"]

@@ -9,6 +9,10 @@
 // buffer, point buffer or lattice constants), m, the directions, the vote rule and whether records are stored are kernel arguments, uniform over the
 // launch: ONE kernel (the product library's kernel budget, tests/test_abi.py).  The page (kPage entries of t and key, no u, v) and the accumulator live in
 // registers: every loop over the page runs over compile-time indices.  kPage was chosen by register count alone, not by timing.
+//
+// hagrid_list_crossings is a launch-uniform MODE of the same kernel (q.list), not a second one: the lane works out its slots once (hx::slot_range), the
+// header's sink stores every folded entry with position < room as one streaming 8-byte word, and after the walk the lane fills [min(m, room), room) with the
+// empty entry.  The other forms run with room 0 and a null target: the sink stores nothing and their records are the bits they were.
 #include "trav_common.h"
 #include "wave_prims.h"
 
@@ -30,18 +34,32 @@ struct CrossArgs {
     const float4* __restrict__ points;          // the point form; both null: the lattice form
     float4* __restrict__ records;               // may be null in the point and lattice forms
     int* __restrict__ inside;                   // null in the ray form
-    unsigned long long* __restrict__ counters;  // may be null
+    unsigned long long* __restrict__ counters;  // may be null; int64[4], in the list mode int64[6]
+    const long long* __restrict__ offsets;      // the list mode, CSR form: int64[n + 1]; null: the stride form
+    unsigned long long* __restrict__ entries;   // the list mode: `capacity` entries of 8 bytes, t in the low word and key in the high one
+    long long capacity;
+    int list, stride;
     int n, m, winding;
     float d0x, d0y, d0z, d1x, d1y, d1z, d2x, d2y, d2z;      // the directions of the point and lattice forms
     float ox, oy, oz, sx, sy, sz;               // lattice: origin, voxel size
     int nx, ny;                                 // lattice: voxels along x and y (x fastest)
 };
 
+// the sink of hx::crossings_walk in the list mode: entry `position` of the ray's sorted list into its slot, while there is room
+struct EntrySink {
+    unsigned long long* slots;      // the ray's first slot; never dereferenced with room 0
+    int room;                       // min(room, INT32_MAX): a position is a count, which fits 31 bits
+    __device__ __forceinline__ static unsigned long long word(float t, uint32_t key) { return (unsigned long long)__float_as_uint(t) | ((unsigned long long)key << 32); }
+    __device__ __forceinline__ void operator()(int position, float t, uint32_t key) const {
+        if (position < room) __builtin_nontemporal_store(word(t, key), slots + position);
+    }
+};
+
 __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, const CrossArgs q, const int small_cells) {
     const int lane = threadIdx.x;
     const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
     const bool live = id < q.n;
-    int n_cells = 0, n_tests = 0, n_flushes = 0;
+    int n_cells = 0, n_tests = 0, n_flushes = 0, n_written = 0, n_short = 0;
     if (live) {
         vec3 org, ray_dir(0.0f, 0.0f, 0.0f);
         float tmin = 0.0f, tmax;
@@ -62,6 +80,10 @@ __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, con
             active = hx::point_active(org, tmax);
         }
 
+        long long first = 0, room = 0;
+        if (q.list) hx::slot_range(q.offsets, q.stride, q.capacity, id, first, room);
+        const EntrySink sink{q.entries + first, int(room < 0x7fffffffLL ? room : 0x7fffffffLL)};
+
         int votes = 0;
 #pragma unroll 1
         for (int d = 0; d < q.m; d++) {
@@ -70,18 +92,30 @@ __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, con
             if (active) {
                 hx::Counts n;
                 const RayGrid g(a, small_cells);
-                rec = hx::crossings_walk<kPage>(g, Ray(org, tmin, dir, tmax), kPage, n);
+                rec = hx::crossings_walk<kPage>(g, Ray(org, tmin, dir, tmax), kPage, n, sink);
                 n_cells += n.cells; n_tests += n.tests; n_flushes += n.flushes;
             }
             votes += hx::vote(rec, q.winding != 0);
             if (q.records) nt_store4(q.records + size_t(id) * size_t(q.m) + size_t(d), __int_as_float(rec.id), rec.t, rec.u, rec.v);
+            if (q.list) {           // (m = 1) the slots the list left over get the empty entry
+                n_written = rec.id < sink.room ? rec.id : sink.room;
+                n_short = rec.id > sink.room ? 1 : 0;
+                const unsigned long long none = EntrySink::word(tmax, 0xffffffffu);
+                for (long long p = n_written; p < room; p++) __builtin_nontemporal_store(none, sink.slots + p);
+            }
         }
         if (q.inside) __builtin_nontemporal_store(active ? (2 * votes > q.m ? 1 : 0) : -1, q.inside + id);
     }
-    if (q.counters) add_batch_counters(q.counters, lane, live ? 1 : 0, n_cells, n_tests, n_flushes);
+    if (q.counters) {
+        add_batch_counters(q.counters, lane, live ? 1 : 0, n_cells, n_tests, n_flushes);
+        if (q.list) {               // entries written (without empty ones), rays whose list did not fit
+            const unsigned long long sw = wave_sum_u64((unsigned)n_written), ss = wave_sum_u64((unsigned)n_short);
+            if (lane == 0) { atomicAdd(q.counters + 4, sw); atomicAdd(q.counters + 5, ss); }
+        }
+    }
 }
 
-// what the three entry points check and do; q holds the source and n
+// what the four entry points check and do; q holds the source and n, in the list mode the slots as well
 int launch(hagrid_ctx* ctx, const char* who, bool ray_form, const hagrid_grid* grid, const void* tris, CrossArgs q, const float* dirs, int num_dirs, void* inside, void* records,
            void* counters, uint32_t flags, uint32_t known_flags) {
     const std::string w(who);
@@ -105,12 +139,12 @@ int launch(hagrid_ctx* ctx, const char* who, bool ray_form, const hagrid_grid* g
         q.d0x = d[0]; q.d0y = d[1]; q.d0z = d[2]; q.d1x = d[3]; q.d1y = d[4]; q.d1z = d[5]; q.d2x = d[6]; q.d2y = d[7]; q.d2z = d[8];
         if (int64_t(q.n) * int64_t(q.m) > int64_t(INT32_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, (w + ": num_points * num_dirs does not fit 31 bits").c_str());
     }
-    if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the counters must be 8-byte aligned").c_str());
+    if (!aligned(counters, 8) || !aligned(q.offsets, 8) || !aligned(q.entries, 8)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": counters, offsets and entries must be 8-byte aligned").c_str());
     if (!aligned(inside, 4)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": inside must be 4-byte aligned").c_str());
     if (!aligned(tris, 16) || !aligned(q.rays, 16) || !aligned(q.points, 16) || !aligned(records, 16)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": triangles, rays, points and records must be 16-byte aligned").c_str());
     if (q.n == 0) return HAGRID_OK;
     if (!tris) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null triangle buffer").c_str());
-    if (ray_form ? !records : !inside) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null output buffer").c_str());
+    if (q.list ? (!q.entries && q.capacity > 0) : (ray_form ? !records : !inside)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null output buffer").c_str());
     HG_HIP(ctx, hipSetDevice(ctx->device));
     a.tris = static_cast<const float4*>(tris);
     a.num_rays = q.n;
@@ -134,6 +168,23 @@ extern "C" int hagrid_count_crossings(hagrid_ctx* ctx, const hagrid_grid* grid, 
     q.rays = static_cast<const float4*>(rays);
     q.n = num_rays; q.m = 1; q.nx = 1; q.ny = 1;
     return launch(ctx, "count_crossings", true, grid, tris, q, nullptr, 0, nullptr, records, counters, flags, 0u);
+}
+
+extern "C" int hagrid_list_crossings(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* rays, int num_rays, const void* offsets, int stride, void* entries,
+                                     int64_t capacity, void* records, void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (num_rays < 0) HG_FAIL(ctx, HAGRID_EINVAL, "list_crossings: negative num_rays");
+    if (capacity < 0) HG_FAIL(ctx, HAGRID_EINVAL, "list_crossings: negative capacity");
+    if (stride < 0 || (offsets != nullptr) == (stride >= 1)) HG_FAIL(ctx, HAGRID_EINVAL, "list_crossings: either offsets (CSR form, stride 0) or a stride >= 1 with offsets == NULL");
+    if (num_rays > 0 && !rays) HG_FAIL(ctx, HAGRID_EINVAL, "list_crossings: null ray buffer");
+    if (!offsets && int64_t(num_rays) * int64_t(stride) > capacity) HG_FAIL(ctx, HAGRID_ERANGE, "list_crossings: num_rays * stride is beyond the capacity");
+    CrossArgs q = {};
+    q.rays = static_cast<const float4*>(rays);
+    q.n = num_rays; q.m = 1; q.nx = 1; q.ny = 1;
+    q.list = 1; q.stride = stride; q.capacity = capacity;
+    q.offsets = static_cast<const long long*>(offsets);
+    q.entries = static_cast<unsigned long long*>(entries);
+    return launch(ctx, "list_crossings", true, grid, tris, q, nullptr, 0, nullptr, records, counters, flags, 0u);
 }
 
 extern "C" int hagrid_points_inside(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points, const float* dirs, int num_dirs, void* inside,

@@ -840,16 +840,12 @@ def ray_tri_pairs(tris: np.ndarray, rays: np.ndarray) -> dict:
     return {"accept": ok & adm, "t": t, "entering": neg}
 
 
-def ray_crossings(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 << 21) -> np.ndarray:
-    """The definition of hagrid_count_crossings by brute force: rays (n, 8) float32 -> HIT_DTYPE records.  With the crossings of a ray sorted by (t, id):
-    id = their number m, t = the first t (the bits of tmax when m = 0), u = length = the sequential float32 sum of t[2p+1] - t[2p] over the pairs,
-    v = the int32 bits of winding = #leaving - #entering.  Every ray against every triangle, a chunk of rays at a time."""
+def _sorted_crossings(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int):
+    """every ray against every triangle, a chunk of rays at a time: (the admitted rays R, then parallel arrays ray, triangle, t, entering of the accepted pairs
+    sorted by ray, then t, then id) -- what ray_crossings condenses and ray_crossing_lists writes out"""
     T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
     R, adm = admit_rays(rays)
     n, N = R.shape[0], T.shape[0]
-    out = np.zeros(n, dtype=HIT_DTYPE)
-    out["t"] = R[:, 7]
-    winding = np.zeros(n, dtype=np.int32)
     cols = [T[None, :, i] for i in range(12)]
     m = max(1, chunk_pairs // max(N, 1))
     ray_idx, tri_idx, ts, neg = [], [], [], []
@@ -860,10 +856,23 @@ def ray_crossings(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 << 21
             ok = ok & adm[o:o + m, None]
             rows, col = np.nonzero(ok)
             ray_idx.append(rows + o); tri_idx.append(col); ts.append(t[rows, col]); neg.append(ng[rows, col])
-    if ray_idx:
-        r = np.concatenate(ray_idx); j = np.concatenate(tri_idx); t = np.concatenate(ts); ng = np.concatenate(neg)
-        order = np.lexsort((j, t, r))                  # by ray, then t, then id
-        r, t, ng = r[order], t[order], ng[order]
+    if not ray_idx:
+        return R, np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros(0, bool)
+    r = np.concatenate(ray_idx); j = np.concatenate(tri_idx); t = np.concatenate(ts); ng = np.concatenate(neg)
+    order = np.lexsort((j, t, r))                  # by ray, then t, then id
+    return R, r[order], j[order], t[order], ng[order]
+
+
+def ray_crossings(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 << 21) -> np.ndarray:
+    """The definition of hagrid_count_crossings by brute force: rays (n, 8) float32 -> HIT_DTYPE records.  With the crossings of a ray sorted by (t, id):
+    id = their number m, t = the first t (the bits of tmax when m = 0), u = length = the sequential float32 sum of t[2p+1] - t[2p] over the pairs,
+    v = the int32 bits of winding = #leaving - #entering.  Every ray against every triangle, a chunk of rays at a time."""
+    R, r, _, t, ng = _sorted_crossings(tris, rays, chunk_pairs)
+    n = R.shape[0]
+    out = np.zeros(n, dtype=HIT_DTYPE)
+    out["t"] = R[:, 7]
+    winding = np.zeros(n, dtype=np.int32)
+    if r.size:
         count = np.bincount(r, minlength=n).astype(np.int32)
         first = np.cumsum(count) - count
         has = count > 0
@@ -878,6 +887,42 @@ def ray_crossings(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 << 21
                 length[sel] = length[sel] + (t[a + 1] - t[a])
         out["u"] = length
     out["v"] = winding.view(np.float32)
+    return out
+
+
+def ray_crossing_lists(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 << 21) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The definition of hagrid_list_crossings by brute force: rays (n, 8) float32 -> (offsets int64 (n + 1,), t float32 (total,), key int32 (total,)).  The
+    crossings of ray i, sorted by (t, id), are the entries offsets[i] .. offsets[i+1]: key = id * 2 + entering.  The same sorted pairs ray_crossings condenses."""
+    R, r, j, t, ng = _sorted_crossings(tris, rays, chunk_pairs)
+    offsets = np.zeros(R.shape[0] + 1, dtype=np.int64)
+    np.cumsum(np.bincount(r, minlength=R.shape[0]), out=offsets[1:])
+    return offsets, t.astype(np.float32), (j * 2 + ng).astype(np.int32)
+
+
+def crossing_slots(offsets_or_stride, capacity: int, lists, tmax) -> dict:
+    """What hagrid_list_crossings leaves in every one of `capacity` slots.  offsets_or_stride: int64 (n + 1,) offsets (the CSR form) or an int S >= 1 (the
+    stride form: ray i owns [i * S, (i + 1) * S)); lists: (offsets, t, key) of ray_crossing_lists; tmax (n,) float32.  The room of ray i is 0 when its pair
+    of offsets is negative, decreasing or beyond the capacity; its first min(m, room) entries go to its first slots and every slot left over gets the empty
+    entry (the bits of tmax, -1).  Returns "t" uint32 bits, "key" int32 and "written" bool (capacity,), "count" = entries written and "short" = rays with m > room."""
+    lo, lt, lk = lists
+    tb = np.ascontiguousarray(tmax, dtype=np.float32).view(np.uint32)
+    n = tb.size
+    if np.ndim(offsets_or_stride) == 0:
+        first = np.arange(n, dtype=np.int64) * int(offsets_or_stride); room = np.full(n, int(offsets_or_stride), dtype=np.int64)
+    else:
+        o = np.asarray(offsets_or_stride, dtype=np.int64)
+        first = o[:-1].copy(); room = o[1:] - o[:-1]
+        room[(first < 0) | (room < 0) | (o[1:] > capacity)] = 0
+    out = {"t": np.zeros(capacity, np.uint32), "key": np.zeros(capacity, np.int32), "written": np.zeros(capacity, bool), "count": 0, "short": 0}
+    ltb = np.ascontiguousarray(lt, dtype=np.float32).view(np.uint32)
+    for i in np.flatnonzero(room > 0):
+        m = int(lo[i + 1] - lo[i]); k = min(m, int(room[i])); a = int(first[i])
+        assert not out["written"][a:a + room[i]].any(), "two rays own a slot"
+        out["t"][a:a + k] = ltb[lo[i]:lo[i] + k]; out["key"][a:a + k] = lk[lo[i]:lo[i] + k]
+        out["t"][a + k:a + room[i]] = tb[i]; out["key"][a + k:a + room[i]] = -1
+        out["written"][a:a + room[i]] = True
+    m_all = (lo[1:] - lo[:-1])
+    out["count"] = int(np.minimum(m_all, room).sum()); out["short"] = int((m_all > room).sum())
     return out
 
 

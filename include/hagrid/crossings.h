@@ -1,5 +1,5 @@
-// hagrid/crossings.h -- crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_points_inside, hagrid_inside_lattice): ALL the surfaces
-// a ray crosses, condensed into one 16-byte record, and from that whether a point lies inside a closed surface.  No counterpart in the
+// hagrid/crossings.h -- crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice): ALL the
+// surfaces a ray crosses, condensed into one 16-byte record or written out as a sorted list, and from that whether a point lies inside a closed surface.  No counterpart in the
 // reference, which answers with the nearest hit only.
 //
 // Everything is float32 without contraction (-ffp-contract=off), every sum in the order written.  The same code serves the gfx950 kernel
@@ -60,6 +60,23 @@
 // with E's list tested again, until D was folded.  So no crossing is left behind a cell the walk has stepped past.
 // The record does not depend on P: crossings_brute_force over ALL triangles defines it, the walk reproduces it.
 //
+// ---- the list: what a sink sees ---------------------------------------------------------------------------------------------------
+// Page::flush, PageVisitor, crossings_walk and crossings_brute_force take a SINK: sink(position, t, key), called once per folded entry, in the order of
+// the folds, with position = acc.count before the fold.  Each crossing is folded once and none is lost (above), and a flush folds a sorted page whose every
+// entry sorts after the cursor, the last entry of the page before it: so the folds of a ray, over all its flushes, run through c_0 .. c_{m-1} in (t, id)
+// order.  So the sink sees the sorted list of the ray, entry p at position p, whatever P is -- and the list is a by-product of the count, not a second walk.
+// The default sink (NoSink) does nothing: the record alone, as before.
+//   An ENTRY of the list is 8 bytes: float t; int32 key, key = id * 2 + entering, the page's own key (id = key >> 1, entering = key & 1).  The EMPTY entry is
+//   t = the bits of the ray's tmax, key = -1.
+//   CSR form: offsets is int64[num_rays + 1]; ray i owns the slots [offsets[i], offsets[i+1]) of `entries`, which holds `capacity` of them.  Its ROOM is
+//   offsets[i+1] - offsets[i]; the room is 0 when that difference is negative, when offsets[i] < 0 or when offsets[i+1] > capacity: such a ray writes nothing,
+//   whatever the offsets say (slot_range below).  Stride form: no offsets, a stride S >= 1; ray i owns [i * S, (i + 1) * S), and capacity >= num_rays * S is
+//   the caller's to check (the entry point does, on the host).
+//   A ray writes its first min(m, room) entries into the first slots of its range, and the empty entry into every slot that is left when room > m.  Nothing
+//   outside its range is written, and the content for room r is a prefix of the content for room r + 1.  With offsets made from the counts of
+//   hagrid_count_crossings over the same rays and grid every slot is written exactly once and there is no empty entry.  A ray that is not admissible or not
+//   active has m = 0 and takes no cell step: its slots, if any, get empty entries.  Truncation shows in the record: record.id = m > room.
+//
 // ---- points ---------------------------------------------------------------------------------------------------------------------
 // A point record is 16 bytes: x, y, z, reach.  For each of m in {1, 3} directions d the ray is org = p, tmin = 0, dir = d, tmax = reach (+inf is
 // allowed and the normal case).  The VOTE of d is count & 1, with HAGRID_INSIDE_WINDING it is winding != 0; inside = 1 when 2 * votes > m,
@@ -110,6 +127,22 @@ struct Accum {
     HOST DEVICE Hit record() const { return Hit(count, t_first, length, as<float>(winding)); }
 };
 
+/// the sink that keeps nothing: the record alone
+struct NoSink {
+    HOST DEVICE void operator()(int, float, uint32_t) const {}
+};
+
+/// the slots of ray i in the list forms (above): first slot and room; room 0 for a pair of offsets that is negative, decreasing or beyond the capacity
+HOST DEVICE inline void slot_range(const long long* offsets, int stride, long long capacity, int i, long long& first, long long& room) {
+    first = 0; room = 0;
+    if (offsets) {
+        const long long b = offsets[i], e = offsets[size_t(i) + 1];
+        if (b >= 0 && e >= b && e <= capacity) { first = b; room = e - b; }
+    } else {
+        first = (long long)i * stride; room = stride;
+    }
+}
+
 /// the P smallest crossings after the cursor, sorted, each triangle once.  key = id * 2 + entering (ids fit 31 bits); an empty slot has kEmpty.
 template <int PMAX>
 struct Page {
@@ -157,11 +190,14 @@ struct Page {
         return true;
     }
 
-    /// fold the entries, in order, into the accumulator; the cursor moves to the last of them; the page is empty afterwards
-    HOST DEVICE void flush(Accum& acc) {
+    /// fold the entries, in order, into the accumulator, each one shown to the sink first (position = the count before the fold); the cursor moves to the
+    /// last of them; the page is empty afterwards
+    template <typename S = NoSink>
+    HOST DEVICE void flush(Accum& acc, const S& sink = S()) {
         HAGRID_UNROLL
         for (int j = 0; j < PMAX; j++)
             if (j < cap && key[j] != kEmpty) {
+                sink(acc.count, t[j], key[j]);
                 acc.fold(t[j], (key[j] & 1u) != 0);
                 has_cursor = true; cur_key = key[j]; cur_t = t[j];
             }
@@ -171,9 +207,9 @@ struct Page {
 
 /// The definition: every triangle against the ray, a page of PMAX over ALL triangles, again and again until a page comes back not full.  tri_at(j) -> Tri.
 /// No grid, no cell, no stop rule: a pass offers everything, so each page is the PMAX smallest crossings after the cursor; the record does not depend on
-/// PMAX (a host program takes a large one: a ray with m crossings costs m / PMAX + 1 passes).
-template <int PMAX = kMaxPage, typename F>
-HOST DEVICE inline Hit crossings_brute_force(F tri_at, int num_tris, const Ray& ray_in) {
+/// PMAX (a host program takes a large one: a ray with m crossings costs m / PMAX + 1 passes), nor does the list the sink sees.
+template <int PMAX = kMaxPage, typename F, typename S = NoSink>
+HOST DEVICE inline Hit crossings_brute_force(F tri_at, int num_tris, const Ray& ray_in, const S& sink = S()) {
     vec3 dir = ray_in.dir;
     const bool admitted = admit_ray(ray_in.org, dir, ray_in.tmin, ray_in.tmax);
     const Ray ray(ray_in.org, ray_in.tmin, dir, ray_in.tmax);
@@ -188,7 +224,7 @@ HOST DEVICE inline Hit crossings_brute_force(F tri_at, int num_tris, const Ray& 
             if (crosses(tri_at(j), ray, t, entering)) page.insert(t, (uint32_t(j) << 1) | (entering ? 1u : 0u));
         }
         const bool more = page.full();
-        page.flush(acc);
+        page.flush(acc, sink);
         if (!more) break;
     }
     return acc.record();
@@ -202,9 +238,9 @@ using walk::CellRec;
 
 /// What the crossing walk does with a cell (the visitor of walk::walk_cells): every reference of the list against the ray's own window into the page; when
 /// the page is full and its last entry is not beyond the cell's exit (or the ray leaves the grid) the page is flushed and the SAME list tested once more.
-template <int PMAX, typename G>
+template <int PMAX, typename G, typename S = NoSink>
 struct PageVisitor {
-    const G& g; const Ray& ray; Page<PMAX>& page; Accum& acc; Counts& n;
+    const G& g; const Ray& ray; Page<PMAX>& page; Accum& acc; Counts& n; const S& sink;
     HOST DEVICE bool operator()(const walk::RefList<G>& list, float texit, bool outside) {
         n.cells++;
         for (;;) {
@@ -216,16 +252,17 @@ struct PageVisitor {
                 if (crosses(g.tri(ref), ray, t, entering)) page.insert(t, (uint32_t(ref) << 1) | (entering ? 1u : 0u));
             }
             if (!(page.full() && (page.last_t <= texit || outside))) return false;
-            page.flush(acc);          // and this cell's list once more
+            page.flush(acc, sink);    // and this cell's list once more
             n.flushes++;
         }
     }
 };
 
 /// The walk of cell_walk.h with pages: the record of one ray over the grid g, equal to crossings_brute_force over all triangles.
-/// G: the accessor of cell_walk.h -- c (WalkConsts), small, cell_at(vx, vy, vz) -> CellRec, ref(i) -- and tri(id).  P: the page capacity.  The kernel (crossings.hip) and tests/cpp/crossings_host.cpp both run this function.
-template <int PMAX, typename G>
-HOST DEVICE inline Hit crossings_walk(const G& g, const Ray& ray_in, int P, Counts& n) {
+/// G: the accessor of cell_walk.h -- c (WalkConsts), small, cell_at(vx, vy, vz) -> CellRec, ref(i) -- and tri(id).  P: the page capacity.  sink: sees the sorted
+/// list, entry by entry.  The kernel (crossings.hip) and the host programs tests/cpp/crossings_host.cpp and crossing_lists_host.cpp all run this function.
+template <int PMAX, typename G, typename S = NoSink>
+HOST DEVICE inline Hit crossings_walk(const G& g, const Ray& ray_in, int P, Counts& n, const S& sink = S()) {
     const walk::RaySetup s(g.c, ray_in.org, ray_in.dir, ray_in.tmin, ray_in.tmax);
     Accum acc;
     acc.init(ray_in.tmax);
@@ -234,9 +271,9 @@ HOST DEVICE inline Hit crossings_walk(const G& g, const Ray& ray_in, int P, Coun
 
     Page<PMAX> page;
     page.init(P);
-    PageVisitor<PMAX, G> visit{g, s.ray, page, acc, n};
+    PageVisitor<PMAX, G, S> visit{g, s.ray, page, acc, n, sink};
     walk::walk_cells(g, s, visit);
-    if (!page.empty()) { page.flush(acc); n.flushes++; }
+    if (!page.empty()) { page.flush(acc, sink); n.flushes++; }
     return acc.record();
 }
 
@@ -256,6 +293,6 @@ HOST DEVICE inline float lattice_centre(float origin, int c, float size) { retur
 } // namespace crossings
 } // namespace hagrid
 
-// The C++ shim over the entry points (count_crossings, points_inside, inside_lattice) is with its neighbours in traverse.h.
+// The C++ shim over the entry points (count_crossings, list_crossings, points_inside, inside_lattice) is with its neighbours in traverse.h.
 
 #endif // HAGRID_CROSSINGS_H

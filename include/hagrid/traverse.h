@@ -67,11 +67,19 @@ inline void overlap_lattice(const Grid& grid, const Tri* tris, const vec3& origi
     detail::check(detail::current_ctx(), hagrid_overlap_lattice(detail::current_ctx(), &p, tris, o, s, m, k, ids, counts, counters, any ? HAGRID_OVERLAP_ANY : 0u));
 }
 
-/// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_points_inside, hagrid_inside_lattice; the record, the paging and the walk:
+/// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice; the record, the paging and the walk:
 /// crossings.h).  records: num_rays Hit-shaped records (count, t_first, length, winding bits); counters: nullptr or int64[4] -- DEVICE pointers.  Asynchronous.
 inline void count_crossings(const Grid& grid, const Tri* tris, const Ray* rays, Hit* records, int num_rays, void* counters = nullptr) {
     hagrid_grid p = detail::to_pod(grid);
     detail::check(detail::current_ctx(), hagrid_count_crossings(detail::current_ctx(), &p, tris, rays, records, num_rays, counters, 0u));
+}
+/// The crossings themselves, sorted by (t, id), 8 bytes each (float t; int32 key = id * 2 + entering): offsets = DEVICE int64[num_rays + 1] (CSR form, stride 0) or
+/// nullptr with stride >= 1 (ray i owns stride slots); entries: `capacity` entries; records: nullptr or the records of count_crossings; counters: nullptr or
+/// int64[6] -- DEVICE pointers.  Slots a list leaves over get (tmax, -1).  The semantics are in crossings.h and hagrid_amd.h (hagrid_list_crossings).  Asynchronous.
+inline void list_crossings(const Grid& grid, const Tri* tris, const Ray* rays, int num_rays, const int64_t* offsets, int stride, void* entries, int64_t capacity,
+                           Hit* records = nullptr, void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_list_crossings(detail::current_ctx(), &p, tris, rays, num_rays, offsets, stride, entries, capacity, records, counters, 0u));
 }
 /// points: num_points records x, y, z, reach; dirs: nullptr (the three defaults) or num_dirs * 3 HOST floats; inside: num_points int32; records: nullptr or
 /// num_points * m Hit-shaped records, direction fastest.

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_list_crossings was ADDED, nothing else moved; 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -347,6 +347,24 @@ int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void*
  * (null buffers are then fine). */
 int hagrid_count_crossings(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* rays, void* records,
                            int num_rays, void* counters, uint32_t flags);
+/* hagrid_list_crossings: the crossings THEMSELVES, all of them, sorted (Open3D's list_intersections; the all-hits query of Embree and OptiX users): layered
+ * transparency beyond eight layers, per-layer thickness, line integrals with a material per segment, ray stabbing, hole and overlap diagnosis.  The list of ray i
+ * is c_0 .. c_{m-1} above.  An ENTRY is 8 bytes: float32 t; int32 key = id * 2 + entering (id = key >> 1, entering = key & 1).  The EMPTY entry is t = the bits
+ * of the ray's tmax, key = -1.  `entries` holds `capacity` entries (DEVICE, 8-byte aligned; NULL only with capacity 0).
+ *   CSR form: offsets = DEVICE int64[num_rays + 1], 8-byte aligned, stride = 0.  Ray i owns the slots [offsets[i], offsets[i+1]); its ROOM is their number, and 0
+ *   if that is negative, if offsets[i] < 0 or if offsets[i+1] > capacity -- such a ray writes nothing, whatever the offsets say.
+ *   Stride form: offsets = NULL, stride = S >= 1.  Ray i owns [i * S, (i + 1) * S); num_rays * S <= capacity is checked on the host.  This is multi-hit without
+ *   the bound of eight, and what a caller without a scan uses.
+ * A ray writes its first min(m, room) entries into the first slots of its range and the empty entry into every slot left over; nothing outside its range is
+ * written, and what room r gets is a prefix of what room r + 1 gets.  With offsets = the exclusive sums of the counts hagrid_count_crossings gave for the same
+ * rays and grid, every slot is written exactly once and there is no empty entry: count, scan, fill.  A ray that is not admissible or inactive has m = 0: its
+ * slots, if any, get empty entries.  records: NULL, or DEVICE num_rays records, 16-byte aligned -- exactly those of hagrid_count_crossings, bit for bit; a list
+ * that did not fit shows as record.id > room.  counters: NULL, or DEVICE int64[6], ADDED to: the four above, then entries written (without empty ones) and rays
+ * with m > room.  The list does not depend on the page: the brute force of include/hagrid/crossings.h with the same sink defines it.  Asynchronous on the
+ * context's stream; the traversal image, ray binning and the hints are neither used nor touched.  HAGRID_EINVAL: as above, and a negative capacity, both or
+ * neither of offsets and stride >= 1, misaligned offsets or entries, any flag.  HAGRID_ERANGE: num_rays * stride > capacity.  num_rays = 0 is HAGRID_OK. */
+int hagrid_list_crossings(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* rays, int num_rays,
+                          const void* offsets, int stride, void* entries, int64_t capacity, void* records, void* counters, uint32_t flags);
 #define HAGRID_INSIDE_WINDING 1u
 int hagrid_points_inside(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points,
                          const float* dirs, int num_dirs, void* inside, void* records, void* counters, uint32_t flags);
