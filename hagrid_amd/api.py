@@ -72,6 +72,13 @@ class MemManager:
     def use_stream(self, stream: int | None):
         """Enqueue all further work on a hipStream_t given as an integer (e.g. torch's cuda_stream)."""
         _check(self, self._L.hagrid_ctx_set_stream(self._ctx, C.c_void_p(stream or 0)), "set_stream")
+        self._stream = int(stream or 0)
+
+    def torch_stream(self):
+        """the manager's stream as a torch stream: torch work queued under `with torch.cuda.stream(mem.torch_stream())` is ordered with the manager's launches"""
+        import torch
+        s = getattr(self, "_stream", 0)
+        return torch.cuda.ExternalStream(s, device=self.device) if s else torch.cuda.default_stream(self.device)
 
     def synchronize(self):
         """Waits for everything queued on this manager's stream (hagrid_ctx_synchronize)."""
@@ -387,6 +394,40 @@ def voxelize(grid: Grid, tris: int, origin, size, n, k: int, ids: int, counts: i
                                               C.c_void_p(counters or 0), int(flags)), "voxelize")
 
 
+def overlap_tris(grid: Grid, tris: int, queries: int, n: int, k: int, ids: int, counts: int = 0, counters: int = 0, flags: int = 0, first: int = 0,
+                 query_labels: int = 0, tri_labels: int = 0):
+    """Extension (hagrid_overlap_tris): CONTACT queries -- for each of n query triangles (48-byte Tri records) the k smallest ids >= first[i] of the scene
+    triangles it touches, into ids and counts exactly as overlap_boxes writes them (ANY likewise).  Two triangles touch when no axis of the separating-axis
+    test separates them (include/hagrid/tri_tri.h; scene.tri_tri_pairs) and the scene triangle meets the query's bounding box grown by the grid's margin.
+    first: 0, or a device int32[n].  query_labels (int32[3 n]) and tri_labels (int32[3 per scene triangle]): both or neither; a pair that shares a label
+    >= 0 is left out -- a mesh's index triples (MeshScene.vertex_labels) leave out the triangle itself and every neighbour that shares a vertex, body ids
+    the contacts inside one body.  Scene triangles with a stored normal of 0 take no part; a query that is not finite or has a stored normal of 0 gets
+    count 0.  `queries` may be `tris`.  counters: as for overlap_boxes; the third total counts the pairs offered to the triangle / triangle test.  All
+    arguments are device addresses; asynchronous on the manager's stream.  scene.overlap_tris states the results in numpy.  Walks the construction
+    format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_overlap_tris(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(queries or 0), int(n), C.c_void_p(first or 0),
+                                           C.c_void_p(query_labels or 0), C.c_void_p(tri_labels or 0), int(k), C.c_void_p(ids or 0), C.c_void_p(counts or 0),
+                                           C.c_void_p(counters or 0), int(flags)), "overlap_tris")
+
+
+def self_intersections(grid: Grid, tris, labels, k: int = MAX_OVERLAP_IDS):
+    """The triangles of a scene that touch each other though they are no neighbours: overlap_tris with the scene's own triangles as queries, `labels` for
+    both sides and first[i] = i + 1, so every pair is reported once, at its smaller id.  tris: a torch float32 tensor (N, 12) on the device, the array the
+    grid was built over; labels: a torch int32 tensor (N, 3) (MeshScene.vertex_labels).  Returns (ids (N, k) int32, counts (N,) int32) as torch tensors;
+    counts[i] = k + 1 says "more": ask overlap_tris again with first = ids[i, k - 1] + 1."""
+    import torch
+    mem = grid.mem or _current
+    n = int(tris.shape[0])
+    with torch.cuda.stream(mem.torch_stream()):
+        first = torch.arange(1, n + 1, dtype=torch.int32, device=tris.device)
+        ids = torch.empty((n, int(k)), dtype=torch.int32, device=tris.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=tris.device)
+        overlap_tris(grid, tris.data_ptr(), tris.data_ptr(), n, k, ids.data_ptr(), counts.data_ptr(), first=first.data_ptr(), query_labels=labels.data_ptr(),
+                     tri_labels=labels.data_ptr())
+    return ids, counts
+
+
 INSIDE_WINDING = 1       # HAGRID_INSIDE_WINDING
 
 
@@ -582,6 +623,8 @@ class MeshScene:
         h = C.c_void_p()
         _check(mem, mem._L.hagrid_scene_create(mem._ctx, recs, len(meshes), inst, n_inst, C.byref(h)), "scene_create")
         self._scene = h
+        self._meshes = [(int(m[1]), int(m[2] or 0), int(m[3])) for m in meshes]                  # (vertices, address of the indices, triangles)
+        self._instance_mesh = list(range(len(meshes))) if instance_mesh is None else [int(k) for k in instance_mesh]
         self.num_instances = n_inst
         self.num_tris = self.first_tri(n_inst)
 
@@ -593,6 +636,28 @@ class MeshScene:
         """One launch on the manager's stream: transforms (12 float32 per instance, or 0) and the meshes' buffers in, num_tris Tri records (48 bytes
         each, 16-byte aligned) out; origins (or 0): int32 pairs (instance, triangle within its mesh) per output triangle."""
         _check(self.mem, self.mem._L.hagrid_scene_assemble(self.mem._ctx, self._scene, C.c_void_p(transforms or 0), C.c_void_p(tris or 0), C.c_void_p(origins or 0)), "scene_assemble")
+
+    def vertex_labels(self):
+        """The labels of the assembled triangles for overlap_tris / self_intersections: a torch int32 tensor (num_tris, 3) on the device, per triangle its
+        mesh's index triple (3p, 3p + 1, 3p + 2 for a mesh without indices) plus an offset per INSTANCE -- the vertices of the instances before it -- so
+        that triangles share a label exactly when they share a vertex of one instance.  Made on the device from the index buffers as they are now
+        (copies and additions on the manager's stream, no host round trip).  A triangle with an index outside its mesh keeps that index: it has no
+        surface and takes no part in a query."""
+        import torch
+        mem = self.mem
+        with torch.cuda.stream(mem.torch_stream()):
+            out = torch.empty((self.num_tris, 3), dtype=torch.int32, device=f"cuda:{mem.device}")
+            offset = 0
+            for i, k in enumerate(self._instance_mesh):
+                nv, idx, nt = self._meshes[k]
+                a = self.first_tri(i)
+                if nt and idx:
+                    mem.copy_d2d(out[a:a + nt].data_ptr(), idx, 12 * nt)
+                    out[a:a + nt] += offset
+                elif nt:
+                    out[a:a + nt] = torch.arange(offset, offset + 3 * nt, dtype=torch.int32, device=out.device).view(nt, 3)
+                offset += nv
+        return out
 
     def bad_indices(self) -> int:
         """Output triangles of the assemble() calls since the last query that named a vertex outside their mesh (each became the degenerate
@@ -666,4 +731,5 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
+           "overlap_tris", "self_intersections",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "INSIDE_WINDING"]

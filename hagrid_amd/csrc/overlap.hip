@@ -10,6 +10,11 @@
 // LDS, laid out [level][lane]: a lane only ever touches its own column, so there is nothing to synchronise, 64 lanes at one level read 64 consecutive
 // words (no bank conflict) and no register array is indexed at run time (no scratch).  8 KB of LDS per wavefront: 20 wavefronts per CU by LDS
 // (DESIGN.md 4.7).  Boxes are processed in buffer order: no binning, no traversal image, no hints -- each answer depends on its box alone.
+//
+// The CONTACT form (hagrid_overlap_tris) is a launch-uniform mode of the same kernel: the lane forms its box from its query's Tri record
+// (overlap.h: query_box) and every triangle that has met the box passes the pair filter -- labels, surface, tri_meets of hagrid/tri_tri.h -- before the list
+// takes it.  The query record is read again for every such candidate instead of being held across the walk, and the 17 axes are evaluated one at a time in
+// rolled loops; the kernel is compiled for four wavefronts per SIMD (amdgpu_waves_per_eu), which the allocator meets with 128 VGPRs and no scratch.
 #include "trav_common.h"
 #include "wave_prims.h"
 
@@ -33,12 +38,37 @@ struct OverlapArgs {
     int* __restrict__ ids;
     int* __restrict__ counts;                // may be null
     unsigned long long* __restrict__ counters;   // may be null
+    const float4* __restrict__ queries;      // not null: the contact form -- Tri records ask, `boxes` is null
+    const int* __restrict__ first;           // contact form: `first` per query, may be null
+    const int* __restrict__ query_labels;    // contact form: three labels per query and per scene triangle, both given or both null
+    const int* __restrict__ tri_labels;
     int n, k, any;
     float ox, oy, oz, sx, sy, sz;            // lattice: origin, voxel size
     int nx, ny;                              // lattice: voxels along x and y (x fastest)
 };
 
-__global__ void __launch_bounds__(64) overlap_boxes_kernel(const OverlapGrid g, const OverlapArgs a) {
+// the query of overlap.h's TriFilter for one lane: the record and the labels are read again for every candidate that has met the box -- few do, the
+// lines stay in the vector L1, and nothing of the query but the box is live across the walk
+struct DevQuery {
+    const float4* __restrict__ queries;      // the launch's arrays (uniform) and this lane's query: addresses are formed where they are used
+    const int* __restrict__ labels;          // of the queries, or null
+    const int* __restrict__ tri_labels;
+    int i;
+    __device__ __forceinline__ Tri tri() const { return load_tri(queries, i); }
+    __device__ __forceinline__ bool labelled() const { return labels != nullptr; }
+    __device__ __forceinline__ int label(int j) const { return labels[3 * size_t(i) + j]; }
+    __device__ __forceinline__ int tri_label(int id, int j) const { return tri_labels[3 * size_t(id) + j]; }
+};
+
+// the pair filter of the launch: nothing for boxes, TriFilter for the contact form (uniform over the launch)
+struct DevFilter {
+    ho::TriFilter<DevQuery> f;
+    bool on;
+    __device__ __forceinline__ bool counts_box_tests() const { return !on; }
+    __device__ __forceinline__ bool accept(int id, const Tri& t, int& tests) const { return !on || f.accept(id, t, tests); }
+};
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) overlap_boxes_kernel(const OverlapGrid g, const OverlapArgs a) {
     __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
     const int lane = threadIdx.x;
     const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
@@ -48,7 +78,15 @@ __global__ void __launch_bounds__(64) overlap_boxes_kernel(const OverlapGrid g, 
     if (live) {
         vec3 lo, hi;
         int first = 0;
-        if (a.boxes) {
+        bool active = true;
+        DevFilter filter;
+        filter.on = a.queries != nullptr;
+        filter.f.q.queries = a.queries; filter.f.q.labels = a.query_labels; filter.f.q.tri_labels = a.tri_labels;
+        filter.f.q.i = id;
+        if (a.queries) {
+            active = ho::query_box(filter.f.q.tri(), g.c.eps, lo, hi);
+            if (a.first) first = __builtin_nontemporal_load(a.first + id);
+        } else if (a.boxes) {
             const float4 b0 = nt_load4(a.boxes + 2 * size_t(id)), b1 = nt_load4(a.boxes + 2 * size_t(id) + 1);
             lo = vec3(b0.x, b0.y, b0.z); hi = vec3(b1.x, b1.y, b1.z);
             first = __float_as_int(b0.w);
@@ -61,7 +99,7 @@ __global__ void __launch_bounds__(64) overlap_boxes_kernel(const OverlapGrid g, 
         st.w_ = &s_w[0][lane]; st.i_ = &s_i[0][lane];
         ho::IdList<ho::kMaxIds> list;
         list.init(a.k, first);
-        ho::overlap_query(g, st, lo, hi, a.any != 0, list, cnt);
+        if (active) ho::overlap_query(g, st, lo, hi, a.any != 0, list, cnt, filter);
         int* out = a.ids + size_t(id) * size_t(a.k);
         if (a.k == 8) {         // the base is 16-byte aligned (checked on the host): two streaming stores
             nt_store4(reinterpret_cast<float4*>(out), __int_as_float(list.id[0]), __int_as_float(list.id[1]), __int_as_float(list.id[2]), __int_as_float(list.id[3]));
@@ -91,7 +129,7 @@ int launch(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid, const void
     if (!aligned(counts, 4)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the counts must be 4-byte aligned").c_str());
     if (a.n == 0) return HAGRID_OK;
     if (!tris || !ids) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": null triangle or id buffer").c_str());
-    if (!aligned(tris, 16) || !aligned(a.boxes, 16)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": triangles and boxes must be 16-byte aligned").c_str());
+    if (!aligned(tris, 16) || !aligned(a.boxes, 16) || !aligned(a.queries, 16)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": triangles, boxes and queries must be 16-byte aligned").c_str());
     // k = 4 and k = 8 store their ids 16 bytes at a time, every other k one id at a time
     if (!aligned(ids, (a.k == 4 || a.k == 8) ? 16 : 4)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the ids must be 16-byte aligned for k = 4 and k = 8, 4-byte aligned otherwise").c_str());
     HG_HIP(ctx, hipSetDevice(ctx->device));
@@ -134,4 +172,21 @@ extern "C" int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, 
     a.sx = size[0]; a.sy = size[1]; a.sz = size[2];
     a.nx = n[0]; a.ny = n[1];
     return launch(ctx, "overlap_lattice", grid, tris, a, ids, counts, counters, flags);
+}
+
+extern "C" int hagrid_overlap_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* queries, int num_queries, const void* first,
+                                   const void* query_labels, const void* tri_labels, int k, void* ids, void* counts, void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (num_queries < 0) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_tris: negative num_queries");
+    if (num_queries > 0 && !queries) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_tris: null query buffer");
+    if ((query_labels != nullptr) != (tri_labels != nullptr)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_tris: query_labels and tri_labels are given together or not at all");
+    if (!aligned(first, 4) || !aligned(query_labels, 4) || !aligned(tri_labels, 4)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_tris: first and the labels must be 4-byte aligned");
+    OverlapArgs a = {};
+    a.queries = static_cast<const float4*>(queries);
+    a.first = static_cast<const int*>(first);
+    a.query_labels = static_cast<const int*>(query_labels);
+    a.tri_labels = static_cast<const int*>(tri_labels);
+    a.n = num_queries; a.k = k;
+    a.nx = 1; a.ny = 1;
+    return launch(ctx, "overlap_tris", grid, tris, a, ids, counts, counters, flags);
 }

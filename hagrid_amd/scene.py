@@ -789,6 +789,119 @@ def lattice_boxes(origin, size, n) -> np.ndarray:
     return out
 
 
+# ---- contact queries: the numpy statement of include/hagrid/tri_tri.h and of the query form of overlap.h (same operations, same order, same truth values) ----
+
+def _tri_tri(A, B):
+    """tri_meets of tri_tri.h on broadcastable float32 arrays: A, B = the 12 columns of the Tri records of the pair"""
+    def verts(T):
+        v0 = (T[0], T[1], T[2])
+        return v0, _sub3(v0, (T[4], T[5], T[6])), (v0[0] + T[8], v0[1] + T[9], v0[2] + T[10])
+
+    va, vb = verts(A), verts(B)
+    na, nb = (A[3], A[7], A[11]), (B[3], B[7], B[11])
+    ea = (_sub3(va[0], va[1]), _sub3(va[2], va[0]), _sub3(va[2], va[1]))
+    eb = (_sub3(vb[0], vb[1]), _sub3(vb[2], vb[0]), _sub3(vb[2], vb[1]))
+
+    def separates(ax):
+        pa = [_dot3(ax, v) for v in va]; pb = [_dot3(ax, v) for v in vb]
+        min_a = np.fmin(pa[0], np.fmin(pa[1], pa[2])); max_a = np.fmax(pa[0], np.fmax(pa[1], pa[2]))
+        min_b = np.fmin(pb[0], np.fmin(pb[1], pb[2])); max_b = np.fmax(pb[0], np.fmax(pb[1], pb[2]))
+        return (min_a > max_b) | (min_b > max_a)
+
+    axes = [na] + [_cross3(na, e) for e in ea] + [nb] + [_cross3(nb, e) for e in eb] + [_cross3(e, f) for e in ea for f in eb]
+    ok = ~separates(axes[0])
+    for ax in axes[1:]:
+        ok = ok & ~separates(ax)
+    return ok
+
+
+def tri_tri_pairs(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Triangle a[i] against triangle b[i] ((n, 12) float32 Tri rows): do they MEET -- tri_meets of include/hagrid/tri_tri.h, the separating-axis test
+    over 17 axes (the two stored normals, the six in-plane edge normals, the nine edge cross products) on the vertices v0, v0 - e1, v0 + e2."""
+    A = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 12); B = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 12)
+    with np.errstate(all="ignore"):
+        return _tri_tri([A[:, i] for i in range(12)], [B[:, i] for i in range(12)])
+
+
+def tri_vertices(tris: np.ndarray) -> np.ndarray:
+    """(n, 3, 3) float32: v0, v0 - e1, v0 + e2 as Tri::bbox forms them"""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    with np.errstate(all="ignore"):
+        return np.stack([T[:, 0:3], (T[:, 0:3] - T[:, 4:7]).astype(np.float32), (T[:, 0:3] + T[:, 8:11]).astype(np.float32)], axis=1)
+
+
+def tris_admissible(tris: np.ndarray) -> np.ndarray:
+    """tri_admissible of prims.h: the twelve floats and the two derived vertices are finite"""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    return np.isfinite(T).all(axis=1) & np.isfinite(tri_vertices(T)).all(axis=(1, 2))
+
+
+def tris_have_surface(tris: np.ndarray) -> np.ndarray:
+    """false: the stored normal is (0, 0, 0)"""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    return ~((T[:, 3] == 0) & (T[:, 7] == 0) & (T[:, 11] == 0))
+
+
+def query_boxes(queries: np.ndarray, grid_lo, grid_hi) -> np.ndarray:
+    """query_box of overlap.h: (n, 8) float32 box rows -- the bounding box of every query triangle grown by eps = 2^-16 of the largest |coordinate| of the
+    grid box on every side, first = 0; an INACTIVE query (not admissible, or stored normal 0) gets the inactive box min = 1, max = 0.  Not clipped yet."""
+    Q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 12)
+    glo = np.asarray(grid_lo, np.float32); ghi = np.asarray(grid_hi, np.float32)
+    eps = np.float32(max(np.abs(glo).max(), np.abs(ghi).max())) * np.float32(1.52587890625e-05)
+    with np.errstate(all="ignore"):
+        V = tri_vertices(Q)
+        B = np.zeros((Q.shape[0], 8), dtype=np.float32)
+        B[:, 0:3] = np.fmin(V[:, 0], np.fmin(V[:, 1], V[:, 2])) - eps
+        B[:, 4:7] = np.fmax(V[:, 0], np.fmax(V[:, 1], V[:, 2])) + eps
+    off = ~(tris_admissible(Q) & tris_have_surface(Q))
+    B[off, 0:3] = np.float32(1.0); B[off, 4:7] = np.float32(0.0)
+    return B
+
+
+def labels_shared(query_labels: np.ndarray, tri_labels: np.ndarray) -> np.ndarray:
+    """labels_shared of overlap.h per pair of rows ((n, 3) int32 each): does a label >= 0 of the query equal a label of the triangle?"""
+    q = np.asarray(query_labels, np.int32).reshape(-1, 3); t = np.asarray(tri_labels, np.int32).reshape(-1, 3)
+    return ((q[:, :, None] >= 0) & (q[:, :, None] == t[:, None, :])).any(axis=(1, 2))
+
+
+def overlap_tris(tris: np.ndarray, queries: np.ndarray, k: int = 8, first=None, query_labels=None, tri_labels=None, grid=None, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of hagrid_overlap_tris by brute force.  With box(A) = query_boxes, clipped (clip_boxes) to the box of the grid the query runs over
+    (`grid` = (min, max), None: grid_box(tris)), S_i = {j >= first[i] : no label >= 0 of query i is a label of triangle j, triangle j has a surface,
+    triangle j meets box(A_i) (overlap_pairs), tri_tri_pairs(A_i, triangle j)}: "ids" (n, k) int32 = the min(k, |S|) smallest ids ascending, unused slots
+    -1; "counts" = min(|S|, k + 1); "sizes" = |S|.  first: None or (n,) int32; query_labels (n, 3) and tri_labels (N, 3) int32: both or neither.
+    Pairs whose bounding intervals miss each other are left out before the tests: the triangle / box test says the same of them."""
+    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
+    glo, ghi = grid_box(tris) if grid is None else grid
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); Q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 12)
+    B = clip_boxes(query_boxes(Q, glo, ghi), glo, ghi)
+    n, N = Q.shape[0], T.shape[0]
+    first = np.zeros(n, np.int64) if first is None else np.asarray(first).astype(np.int64)
+    ids = np.full((n, k), -1, dtype=np.int32); sizes = np.zeros(n, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        V = tri_vertices(T)
+        tmin = np.fmin(V[:, 0], np.fmin(V[:, 1], V[:, 2])); tmax = np.fmax(V[:, 0], np.fmax(V[:, 1], V[:, 2]))
+        surface = tris_have_surface(T)
+        tid = np.arange(N, dtype=np.int64)[None, :]
+        m = max(1, chunk_pairs // max(N, 1))
+        for o in range(0, n if N else 0, m):
+            b = B[o:o + m]
+            active = (b[:, 0:3] <= b[:, 4:7]).all(axis=1)
+            near = ~((tmin[None, :, :] > b[:, None, 4:7]) | (tmax[None, :, :] < b[:, None, 0:3])).any(axis=2)      # the bounds check of the triangle / box test
+            near &= active[:, None] & surface[None, :] & (tid >= first[o:o + m, None])
+            rows, col = np.nonzero(near)                       # by row, then by id ascending
+            if query_labels is not None:
+                keep = ~labels_shared(np.asarray(query_labels).reshape(-1, 3)[o + rows], np.asarray(tri_labels).reshape(-1, 3)[col])
+                rows, col = rows[keep], col[keep]
+            keep = overlap_pairs(T[col], b[rows]) & tri_tri_pairs(Q[o + rows], T[col])
+            rows, col = rows[keep], col[keep]
+            sz = np.bincount(rows, minlength=b.shape[0])
+            sizes[o:o + b.shape[0]] = sz
+            pos = np.arange(rows.size) - (np.cumsum(sz) - sz)[rows]
+            sel = pos < k
+            ids[o + rows[sel], pos[sel]] = col[sel]
+    return {"ids": ids, "counts": np.minimum(sizes, k + 1).astype(np.int32), "sizes": sizes}
+
+
 # ---- crossing queries: the numpy statement of include/hagrid/crossings.h (same operations, same order, same bits) ---------------------------
 
 INSIDE_WINDING = 1

@@ -56,6 +56,13 @@
 //       leaf of that voxel is reached, because the integer range of every sub-block above it contains the voxel; by (a) the cell of the
 //       leaf lists the triangle.
 // Three counts per box: cells visited, triangle / box tests evaluated, sub-blocks pruned.
+//
+// ---- contact queries (hagrid_amd.h: hagrid_overlap_tris) ----------------------------------------------------------
+// A query may be a TRIANGLE A instead of a box: S = {j >= first : no label >= 0 of A is a label of j, j has a surface, j meets box(A), tri_meets(A, j)} with
+// tri_meets of tri_tri.h and box(A) = A's bounding box grown by eps on every side, then clipped as every box is (query_box).  Everything above stays as it
+// is: test_cell, brute_force and overlap_query take a PAIR FILTER that a triangle which meets the box must pass as well (NoFilter, the default, lets
+// everything pass); TriFilter is the filter of this query, tris_query and tris_brute_force the two ends.  The walk is sound by (a) - (c) as they stand,
+// because every member of S meets a box.  The second count is then of the pairs offered to tri_meets.
 #ifndef HAGRID_OVERLAP_H
 #define HAGRID_OVERLAP_H
 
@@ -63,6 +70,7 @@
 #include "grid.h"
 #include "multi_hit.h"
 #include "prims.h"
+#include "tri_tri.h"
 #include "vec.h"
 
 namespace hagrid {
@@ -154,16 +162,25 @@ struct IdList {
     }
 };
 
+/// The pair filter of a query: what a triangle that meets the box must pass as well to be a member of S.  accept(id, tri, tests) -> bool, where `tests`
+/// is the query's count of tests evaluated; counts_box_tests() says whether that count is of the triangle / box tests (a filter that says no counts its
+/// own).  This one lets everything pass: the box queries.
+struct NoFilter {
+    HOST DEVICE bool counts_box_tests() const { return true; }
+    HOST DEVICE bool accept(int, const Tri&, int&) const { return true; }
+};
+
 /// the definition: every triangle, in order, against the clipped box.  tri_at(j) -> Tri.  Returns the number of tests evaluated.
-template <typename F, typename L>
-HOST DEVICE inline int brute_force(F tri_at, int num_tris, const Clip& clip, const vec3& box_lo, const vec3& box_hi, bool any, L& list) {
+template <typename F, typename L, typename P = NoFilter>
+HOST DEVICE inline int brute_force(F tri_at, int num_tris, const Clip& clip, const vec3& box_lo, const vec3& box_hi, bool any, L& list, const P& filter = P()) {
     int sats = 0;
     vec3 lo = box_lo, hi = box_hi;
     if (!clip.apply(lo, hi)) return sats;
     for (int j = 0; j < num_tris; j++) {
         if (!list.wants(j)) continue;
-        sats++;
-        if (meets(tri_at(j), lo, hi)) {
+        if (filter.counts_box_tests()) sats++;
+        const Tri t = tri_at(j);
+        if (meets(t, lo, hi) && filter.accept(j, t, sats)) {
             list.take(j);
             if (any) break;
         }
@@ -200,8 +217,8 @@ HOST DEVICE inline bool misses(const VoxelRange& r, int x, int y, int z, int s) 
 }
 
 /// the list of one cell.  G: c (GridConsts), clip (Clip), word(i), cell(i) -> CellRec, ref(i), tri(id)
-template <typename G, typename L>
-HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bool any, uint32_t index, L& list, Counts& n) {
+template <typename G, typename L, typename P = NoFilter>
+HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bool any, uint32_t index, L& list, Counts& n, const P& filter = P()) {
     const CellRec c = g.cell(index);
     n.cells++;
     if (c.begin < 0) return;
@@ -209,8 +226,9 @@ HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bo
         const int ref = g.ref(i);
         if (ref < 0) break;
         if (!list.wants(ref)) continue;
-        n.sats++;
-        if (meets(g.tri(ref), lo, hi)) {
+        if (filter.counts_box_tests()) n.sats++;
+        const Tri t = g.tri(ref);
+        if (meets(t, lo, hi) && filter.accept(ref, t, n.sats)) {
             list.take(ref);
             if (any) return;
         }
@@ -218,9 +236,9 @@ HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bo
 }
 
 /// one top-level cell of the range: descend its sub-blocks (block_walk.h) while their voxel ranges meet the box's
-template <typename G, typename S, typename L>
+template <typename G, typename S, typename L, typename P = NoFilter>
 HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3& hi, bool any, const VoxelRange& r, int tx, int ty, int tz, uint32_t& last_cell,
-                                  L& list, Counts& n) {
+                                  L& list, Counts& n, const P& filter = P()) {
     const GridConsts& c = g.c;
     auto prune = [&](int x, int y, int z, int s) {
         const bool out = misses(r, x, y, z, s);
@@ -230,7 +248,7 @@ HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3&
     auto leaf = [&](uint32_t ci) {                      // true: ANY has its triangle
         if (ci == last_cell) return false;
         last_cell = ci;
-        test_cell(g, lo, hi, any, ci, list, n);
+        test_cell(g, lo, hi, any, ci, list, n, filter);
         return any && list.found();
     };
     const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
@@ -240,8 +258,8 @@ HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3&
 
 /// the answer for the box [lo, hi] over the grid g: equal to brute_force over all triangles (with ANY: some member of S, or none).
 /// `list` arrives initialised (init(k, first)).
-template <typename G, typename S, typename L>
-HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, const vec3& box_hi, bool any, L& list, Counts& n) {
+template <typename G, typename S, typename L, typename P = NoFilter>
+HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, const vec3& box_hi, bool any, L& list, Counts& n, const P& filter = P()) {
     const GridConsts& c = g.c;
     n.cells = 0; n.sats = 0; n.pruned = 0;
     vec3 lo = box_lo, hi = box_hi;
@@ -253,9 +271,59 @@ HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, con
     for (int z = z0; z <= z1; z++)
         for (int y = y0; y <= y1; y++)
             for (int x = x0; x <= x1; x++) {
-                visit_top(g, st, lo, hi, any, r, x, y, z, last_cell, list, n);
+                visit_top(g, st, lo, hi, any, r, x, y, z, last_cell, list, n, filter);
                 if (any && list.found()) return;
             }
+}
+
+// ---- contact queries: a triangle asks -------------------------------------------------------------------------------------------
+
+/// The box of a query triangle: its bounding box grown by eps (the grid's absolute margin) on every side.  false: the query is INACTIVE -- not
+/// admissible (a coordinate or a derived vertex that is not finite), or without a surface (stored normal 0).
+HOST DEVICE inline bool query_box(const Tri& q, float eps, vec3& lo, vec3& hi) {
+    if (!tri_admissible(q) || !tri_has_surface(q)) return false;
+    const BBox b = q.bbox();
+    lo = vec3(b.min.x - eps, b.min.y - eps, b.min.z - eps);
+    hi = vec3(b.max.x + eps, b.max.y + eps, b.max.z + eps);
+    return true;
+}
+
+/// Does a label >= 0 of the query equal a label of the triangle?
+HOST DEVICE inline bool labels_shared(int q0, int q1, int q2, int t0, int t1, int t2) {
+    return (q0 >= 0 && (q0 == t0 || q0 == t1 || q0 == t2)) || (q1 >= 0 && (q1 == t0 || q1 == t1 || q1 == t2)) || (q2 >= 0 && (q2 == t0 || q2 == t1 || q2 == t2));
+}
+
+/// The pair filter of a contact query.  Q: tri() -> the query triangle, labelled() -> bool, label(i) -> label i of the query, tri_label(id, i) -> label i of
+/// scene triangle id.  A pair that shares a label is skipped; a triangle without a surface takes no part; the rest is offered to tri_meets and counted.
+template <typename Q>
+struct TriFilter {
+    Q q;
+    HOST DEVICE bool counts_box_tests() const { return false; }
+    HOST DEVICE bool accept(int id, const Tri& t, int& tests) const {
+        if (q.labelled() && labels_shared(q.label(0), q.label(1), q.label(2), q.tri_label(id, 0), q.tri_label(id, 1), q.tri_label(id, 2))) return false;
+        if (!tri_has_surface(t)) return false;
+        tests++;
+        return tri_meets(q.tri(), t);
+    }
+};
+
+/// the definition of the contact query: every triangle, in order.  `eps`: the grid's absolute margin.  Returns the number of pairs offered to tri_meets.
+template <typename F, typename L, typename Q>
+HOST DEVICE inline int tris_brute_force(F tri_at, int num_tris, const Clip& clip, float eps, const Q& q, bool any, L& list) {
+    vec3 lo, hi;
+    if (!query_box(q.tri(), eps, lo, hi)) return 0;
+    TriFilter<Q> f = {q};
+    return brute_force(tri_at, num_tris, clip, lo, hi, any, list, f);
+}
+
+/// the contact query over the grid g: equal to tris_brute_force over all triangles.  `list` arrives initialised (init(k, first)).
+template <typename G, typename S, typename L, typename Q>
+HOST DEVICE inline void tris_query(const G& g, S& st, const Q& q, bool any, L& list, Counts& n) {
+    n.cells = 0; n.sats = 0; n.pruned = 0;
+    vec3 lo, hi;
+    if (!query_box(q.tri(), g.c.eps, lo, hi)) return;
+    TriFilter<Q> f = {q};
+    overlap_query(g, st, lo, hi, any, list, n, f);
 }
 
 } // namespace overlap

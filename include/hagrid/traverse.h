@@ -66,6 +66,15 @@ inline void overlap_lattice(const Grid& grid, const Tri* tris, const vec3& origi
     const int m[3] = {n.x, n.y, n.z};
     detail::check(detail::current_ctx(), hagrid_overlap_lattice(detail::current_ctx(), &p, tris, o, s, m, k, ids, counts, counters, any ? HAGRID_OVERLAP_ANY : 0u));
 }
+/// Extension: contact queries (hagrid_amd.h: hagrid_overlap_tris; the pair: tri_tri.h, the query: overlap.h).  queries: num_queries Tri records (may be
+/// `tris`), first: nullptr or num_queries int32, query_labels (3 per query) and tri_labels (3 per scene triangle): both or neither; ids, counts, counters and
+/// any as for overlap_boxes -- all DEVICE pointers.  Asynchronous on the context's stream.
+inline void overlap_tris(const Grid& grid, const Tri* tris, const Tri* queries, int num_queries, int k, int* ids, int* counts = nullptr, void* counters = nullptr, bool any = false,
+                         const int* first = nullptr, const int* query_labels = nullptr, const int* tri_labels = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_overlap_tris(detail::current_ctx(), &p, tris, queries, num_queries, first, query_labels, tri_labels, k, ids, counts, counters,
+                                                             any ? HAGRID_OVERLAP_ANY : 0u));
+}
 
 /// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice; the record, the paging and the walk:
 /// crossings.h).  records: num_rays Hit-shaped records (count, t_first, length, winding bits); counters: nullptr or int64[4] -- DEVICE pointers.  Asynchronous.

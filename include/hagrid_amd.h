@@ -318,6 +318,25 @@ int hagrid_overlap_boxes(hagrid_ctx* ctx, const hagrid_grid* grid, const void* t
 int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, int k,
                            void* ids, void* counts, void* counters, uint32_t flags);
 
+/* Extension (no reference counterpart): CONTACT queries -- for every triangle of a batch, which triangles of the scene it touches (collision between two
+ * meshes: Embree's rtcCollide; self-intersection diagnosis).  A query is a 48-byte Tri record A.  Triangles a and b MEET exactly when tri_meets(a, b) of
+ * include/hagrid/tri_tri.h says so: no axis of the separating-axis test -- the two stored normals, the nine cross products of an edge of a with an edge of b,
+ * the six in-plane edge normals -- strictly separates their projections; float32 without contraction in the expression order of that header.  With
+ *   S_i = {j >= first[i] : pair (i, j) is not skipped, triangle j has a surface, triangle j meets box(A_i), tri_meets(A_i, triangle j)},
+ * m = |S_i| and 1 <= k <= HAGRID_MAX_OVERLAP_IDS, ids, counts, paging and HAGRID_OVERLAP_ANY are those of hagrid_overlap_boxes.  box(A) is A's bounding box
+ * grown by the grid's margin (2^-16 of the largest |coordinate| of the grid box) on every side and clipped as every box is; "meets box" is the test of
+ * hagrid_overlap_boxes.  In exact arithmetic the precondition removes nothing (a shared point lies in A's box and in the grid); it makes the walk's answer
+ * the brute force's and huge query triangles legal.  first: NULL (0 everywhere) or DEVICE int32[num_queries]; first[i] = i + 1 with the
+ * scene's own array as queries reports every pair once.  query_labels: DEVICE int32[3 * num_queries], tri_labels: DEVICE int32[3 per scene triangle], both
+ * given or both NULL: pair (i, j) is SKIPPED when a label >= 0 of query i equals a label of triangle j -- with a mesh's index triples as labels a triangle
+ * itself and every neighbour that shares a vertex with it, with body ids as labels the contacts inside one body.  A scene triangle whose stored normal is
+ * (0, 0, 0) has no surface and takes no part; a query that is not admissible (a float or a derived vertex that is not finite) or whose stored normal is
+ * (0, 0, 0) is INACTIVE: count 0, ids -1.  `queries` may be the scene's own array.  counters: as for boxes; the third total counts the pairs offered to
+ * tri_meets.  HAGRID_EINVAL: as for hagrid_overlap_boxes (queries 16-byte aligned, first and the labels 4), and one label array without the other.
+ * num_queries = 0 is HAGRID_OK. */
+int hagrid_overlap_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* queries, int num_queries, const void* first,
+                        const void* query_labels, const void* tri_labels, int k, void* ids, void* counts, void* counters, uint32_t flags);
+
 /* Extension (no reference counterpart): CROSSING queries -- ALL the surfaces a ray crosses, and from that whether a point lies inside a closed surface
  * (thickness and path length through a solid, signed distance = hagrid_closest_points + inside, solid voxelization = hagrid_overlap_lattice + inside;
  * Embree's rtcIntersect with a collecting filter, Open3D's compute_occupancy).  Ray i CROSSES triangle j exactly when intersect_prim_ray of
