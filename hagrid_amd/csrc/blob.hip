@@ -31,6 +31,8 @@ int fill_header(hagrid_ctx* ctx, const hagrid_grid* g, int num_tris, hagrid_blob
     if (!g || !g->entries || !g->ref_ids || (!g->cells && !g->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: incomplete grid");
     if (num_tris < 0 || g->num_cells < 0 || g->num_entries < 0 || g->num_refs < 0 || g->num_offsets < 0 || g->num_offsets > HAGRID_MAX_LEVELS)
         HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: bad counts");
+    // what check_header refuses is not written: a grid of 16 to 23 levels is built, and no traversal, query or blob call takes it
+    if (g->shift < 0 || g->shift > 15) HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: bad shift or dimensions");
     memset(&h, 0, sizeof(h));
     h.magic = kBlobMagic; h.version = 1;
     for (int i = 0; i < 3; i++) { h.dims[i] = g->dims[i]; h.bbox_min[i] = g->bbox_min[i]; h.bbox_max[i] = g->bbox_max[i]; }
@@ -59,7 +61,7 @@ int check_header(hagrid_ctx* ctx, const hagrid_blob_header& h, size_t bytes) {
     HG_TRY(fill_header(ctx, &g, h.num_tris, want));
     if (want.off_entries != h.off_entries || want.off_cells != h.off_cells || want.off_refs != h.off_refs || want.off_tris != h.off_tris ||
         want.total_bytes != h.total_bytes || h.total_bytes > bytes) HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: inconsistent section table");
-    if (h.shift < 0 || h.shift > 15 || h.dims[0] <= 0 || h.dims[1] <= 0 || h.dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: bad dimensions");
+    if (h.shift < 0 || h.shift > 15 || h.dims[0] <= 0 || h.dims[1] <= 0 || h.dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: bad shift or dimensions");
     // the top level of the voxel map is one entry per top-level cell and comes first; offsets[] are the cumulative entry counts
     const long long top = (long long)h.dims[0] * h.dims[1] * h.dims[2];
     if (top > h.num_entries) HG_FAIL(ctx, HAGRID_EINVAL, "grid blob: fewer entries than top-level cells");

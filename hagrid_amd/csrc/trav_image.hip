@@ -543,7 +543,7 @@ __global__ void __launch_bounds__(kBlock) max_ref_kernel(const int* __restrict__
 int hagrid_impl::trav_image_build(hagrid_ctx* ctx, const hagrid_grid* g) {
     trav_image_drop(ctx);
     if (!ctx->opt_image || !g->entries || (!g->cells && !g->small_cells) || !g->ref_ids || g->num_cells <= 0) return HAGRID_OK;
-    if (g->shift < 0 || g->shift > 15) return HAGRID_OK;
+    if (g->shift < 0 || g->shift > 15) return HAGRID_OK;       // (not reached through hagrid_setup_traversal: make_args has refused such a grid)
     for (int i = 0; i < 3; i++)
         if (g->dims[i] <= 0 || (long long)g->dims[i] << g->shift > 65535) return HAGRID_OK;
     const long long num_top = (long long)g->dims[0] * g->dims[1] * g->dims[2];
@@ -594,6 +594,7 @@ int hagrid_impl::trav_image_build(hagrid_ctx* ctx, const hagrid_grid* g) {
 
 extern "C" int hagrid_grid_release_for_traversal(hagrid_ctx* ctx, hagrid_grid* grid) {
     if (!ctx || !grid) return HAGRID_EINVAL;
+    if (grid->shift < 0 || grid->shift > 15) HG_FAIL(ctx, HAGRID_EINVAL, "release_for_traversal: bad shift");
     TravImageCache& img = ctx->image;
     if (!trav_image_matches(ctx, grid) || img.detached) HG_FAIL(ctx, HAGRID_EINVAL, "release_for_traversal: call hagrid_setup_traversal for this grid first");
     if (img.borrowed) HG_FAIL(ctx, HAGRID_EINVAL, "release_for_traversal: this context only borrows the traversal image (hagrid_share_traversal); release the grid in the context that built it");

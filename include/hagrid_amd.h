@@ -143,7 +143,9 @@ float hagrid_profile_end(hagrid_ctx* ctx);
  * scene-box extent is not finite, for a top-level grid, a level's references or cells, or the totals beyond 2^30 - 1 (true totals: a sum of 2^32 or
  * more is seen), and for 24 levels or more.  A scene whose box has no volume (a quad, a ground plane, coincident points) is built in a box widened
  * to 2^-10 of the scene's scale on its thin axes; that box is grid->bbox.  After a refusal *grid is as it was, the context stays usable and the pool's
- * usage is unchanged. */
+ * usage is unchanged.  Grids of 16 to 23 levels (grid->shift > 15) are built, and hagrid_merge_grid, hagrid_flatten_grid and hagrid_expand_grid accept
+ * them; hagrid_compress_grid returns 0, and every traversal, query and blob call -- hagrid_setup_traversal, hagrid_grid_release_for_traversal,
+ * hagrid_grid_pack and hagrid_grid_save included -- answers HAGRID_EINVAL ("bad shift") before it launches or writes anything. */
 int hagrid_build_grid(hagrid_ctx* ctx, const void* tris, int num_tris, hagrid_grid* grid,
                       float top_density, float snd_density);
 /* merge_grid (merge.cu:331-377).  On an error the grid is gone: cells and ref_ids are released and NULL in the descriptor
