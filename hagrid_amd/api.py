@@ -509,6 +509,33 @@ def inside_lattice(grid: Grid, tris: int, origin, size, n, inside: int, dirs=Non
                                              C.c_void_p(counters or 0), int(flags)), "inside_lattice")
 
 
+def fill_lattice(grid: Grid, tris: int, origin, size, n, inside: int, axes: int = 7, workspace: int = 0, records: int = 0, counters: int = 0, flags: int = 0):
+    """Extension (hagrid_fill_lattice): the inside of a closed surface on the lattice of inside_lattice by scan lines -- ONE ray per voxel row of every axis in
+    `axes` (1 = x, 2 = y, 4 = z; 0 means 7) instead of one to three per voxel.  A row's vote for voxel c is its state over the crossings before the voxel's centre
+    (count & 1; flags INSIDE_WINDING, the recommended rule: leaving minus entering != 0); a row that ends inside abstains; inside (int32 per voxel, x fastest) is 1
+    when most usable rows vote inside, else 0, -1 where no row was usable.  workspace: one byte per voxel on the device, needed with more than one axis.  records:
+    0, or the records of the row rays (count_crossings), axis after axis; counters: 0, or a device int64[5] added to (rows, cells, tests, flushes, rows that
+    abstained).  Device addresses; asynchronous on the manager's stream.  scene.fill_lattice states the results in numpy."""
+    mem = grid.mem or _current
+    o = (C.c_float * 3)(*[float(v) for v in origin]); s = (C.c_float * 3)(*[float(v) for v in size]); k = (C.c_int * 3)(*[int(v) for v in n])
+    _check(mem, mem._L.hagrid_fill_lattice(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), o, s, k, int(axes), C.c_void_p(inside or 0), C.c_void_p(workspace or 0),
+                                           C.c_void_p(records or 0), C.c_void_p(counters or 0), int(flags)), "fill_lattice")
+
+
+def solid_voxels(grid: Grid, tris, origin, size, n, axes: int = 7, winding: bool = True):
+    """The solid voxelization of a closed surface: fill_lattice on torch's current stream (the manager must run on it: mem.use_stream(
+    torch.cuda.current_stream().cuda_stream)), the workspace allocated here.  tris: a torch tensor on the device (or a device address).  Returns a torch.int32
+    tensor of shape (nz, ny, nx): 1 inside, 0 outside, -1 where no row was usable."""
+    import torch
+    nx, ny, nz = (int(v) for v in n)
+    dev = tris.device if hasattr(tris, "device") else torch.device("cuda", torch.cuda.current_device())
+    inside = torch.empty((nz, ny, nx), dtype=torch.int32, device=dev)
+    work = torch.empty(nx * ny * nz, dtype=torch.uint8, device=dev)
+    fill_lattice(grid, tris.data_ptr() if hasattr(tris, "data_ptr") else int(tris or 0), origin, size, (nx, ny, nz), inside.data_ptr(), axes=axes, workspace=work.data_ptr(),
+                 flags=INSIDE_WINDING if winding else 0)
+    return inside
+
+
 def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, steps: int = 0) -> dict:
     mem = grid.mem or _current
     st = TraversalStats()
@@ -732,4 +759,4 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
            "overlap_tris", "self_intersections",
-           "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "INSIDE_WINDING"]
+           "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

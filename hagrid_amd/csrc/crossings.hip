@@ -13,6 +13,14 @@
 // hagrid_list_crossings is a launch-uniform MODE of the same kernel (q.list), not a second one: the lane works out its slots once (hx::slot_range), the
 // header's sink stores every folded entry with position < room as one streaming 8-byte word, and after the walk the lane fills [min(m, room), room) with the
 // empty entry.  The other forms run with room 0 and a null target: the sink stores nothing and their records are the bits they were.
+//
+// hagrid_fill_lattice is the ROW form, a fourth source beside ray, point and lattice and again a launch-uniform mode (q.row = 1 + axis): one lane per voxel row
+// of one axis, one launch per requested axis on the context's stream, x, y, z.  The lane's ray is the header's row_ray, its sink the header's RowSink over the
+// emitter below: between two crossings the state is constant, so a run of voxels gets it at once.  A pass that is not the last keeps its vote in the workspace
+// byte (hx::row_bits: two bits per pass), the last pass reads the byte and writes `inside`; a lane whose row ends inside goes over its row once more with
+// valid = 0.  Inside one launch every voxel belongs to exactly one lane, so the launch order is the only synchronisation.  Rows along x are contiguous: there a
+// run is stored four voxels at a time where the address allows (one 16-byte store of `inside`, one dword of the workspace); rows along y and z lie one x apart
+// in neighbouring lanes and store element by element.
 #include "trav_common.h"
 #include "wave_prims.h"
 
@@ -43,31 +51,93 @@ struct CrossArgs {
     float d0x, d0y, d0z, d1x, d1y, d1z, d2x, d2y, d2z;      // the directions of the point and lattice forms
     float ox, oy, oz, sx, sy, sz;               // lattice: origin, voxel size
     int nx, ny;                                 // lattice: voxels along x and y (x fastest)
+    int nz;                                     // the row form: voxels along z
+    int row, row_pass, row_last;                // the row form: 1 + axis (0: another form); the pass (0, 1, 2) and whether it is the last
+    int row_n, row_stride; float row_o, row_s;  // the row form: voxels along a row, their element stride, origin and voxel size of the axis (hx::row_of's, made on the host)
+    unsigned char* __restrict__ ws;             // the row form: one byte per voxel; null when the only pass is the last
+    long long rec_base;                         // the row form: the first record of this axis
 };
 
-// the sink of hx::crossings_walk in the list mode: entry `position` of the ray's sorted list into its slot, while there is room
+// an entry of the list mode: t in the low word and the key in the high one
 struct EntrySink {
-    unsigned long long* slots;      // the ray's first slot; never dereferenced with room 0
-    int room;                       // min(room, INT32_MAX): a position is a count, which fits 31 bits
     __device__ __forceinline__ static unsigned long long word(float t, uint32_t key) { return (unsigned long long)__float_as_uint(t) | ((unsigned long long)key << 32); }
-    __device__ __forceinline__ void operator()(int position, float t, uint32_t key) const {
-        if (position < room) __builtin_nontemporal_store(word(t, key), slots + position);
+};
+
+// the emitter of hx::RowSink: `length` voxels from element `first` on, `stride` apart, get the row's vote (valid = 0: the row abstains).  hx::row_put says what a
+// voxel gets.  Rows along x (stride 1) are always pass 0 -- x is the lowest axis --, so what their voxels get is read from nowhere and the same for the whole run:
+// four voxels whose target is aligned go as one store, a 16-byte one of `inside` when x is the only axis, a dword of the workspace otherwise.
+struct RowEmit {
+    unsigned char* ws; int* inside;
+    int pass, last, valid;
+    __device__ __forceinline__ void operator()(int first, int stride, int length, int state) const {
+        int e = first;
+        int left = length;
+        asm volatile("" : "+v"(e));         // addresses are made here, from the index: made ahead they would be carried through the whole walk, two registers each
+        if (stride == 1 && pass == 0) {
+            const unsigned b = hx::row_bits(0u, 0, valid, state);
+            if (last) {
+                const int v = hx::row_answer(b);
+#pragma clang loop unroll(disable) vectorize(disable)
+                for (; left > 0 && (reinterpret_cast<uintptr_t>(inside + e) & 15u); left--, e++) inside[e] = v;
+#pragma clang loop unroll(disable) vectorize(disable)
+                for (; left >= 4; left -= 4, e += 4) *reinterpret_cast<int4*>(inside + e) = make_int4(v, v, v, v);
+            } else {
+#pragma clang loop unroll(disable) vectorize(disable)
+                for (; left > 0 && (reinterpret_cast<uintptr_t>(ws + e) & 3u); left--, e++) ws[e] = (unsigned char)b;
+#pragma clang loop unroll(disable) vectorize(disable)
+                for (; left >= 4; left -= 4, e += 4) *reinterpret_cast<unsigned*>(ws + e) = b * 0x01010101u;
+            }
+        }
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (; left > 0; left--, e += stride) hx::row_put(ws, inside, e, pass, last != 0, valid, state);
     }
 };
 
-__global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, const CrossArgs q, const int small_cells) {
+// The one sink of the kernel: the list mode's entries or the row form's voxels, by the launch.  A lane is in one mode or the other, so what it carries through
+// the walk shares three registers: the list mode keeps its first slot in the words the row form uses for base and cursor, and its room in the row form's sum.
+struct Sink {
+    hx::RowSink<RowEmit> row;
+    unsigned long long* entries;
+    int is_row;
+    __device__ __forceinline__ void set_list(long long first, int room) { row.base = int(first); row.c = int(first >> 32); row.sum = room; }
+    __device__ __forceinline__ int room() const { return row.sum; }
+    __device__ __forceinline__ unsigned long long* slots() const { return entries + ((long long)(unsigned)row.base | ((long long)row.c << 32)); }
+    __device__ __forceinline__ void operator()(int position, float t, uint32_t key) const {
+        if (is_row) row(position, t, key);
+        else if (position < row.sum) __builtin_nontemporal_store(EntrySink::word(t, key), slots() + position);
+    }
+};
+
+} // namespace
+
+template <>
+struct hagrid::crossings::SinkTraits<Sink> {
+    __device__ __forceinline__ static bool serial(const Sink& s) { return s.is_row != 0; }
+};
+
+namespace {
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) crossings_kernel(const TraverseArgs a, const CrossArgs q, const int small_cells) {
     const int lane = threadIdx.x;
     const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
     const bool live = id < q.n;
-    int n_cells = 0, n_tests = 0, n_flushes = 0, n_written = 0, n_short = 0;
+    int n_cells = 0, n_tests = 0, n_flushes = 0, n_written = 0, n_short = 0, n_abstained = 0;
     if (live) {
         vec3 org, ray_dir(0.0f, 0.0f, 0.0f);
         float tmin = 0.0f, tmax;
         bool active = true;
+        int row_base = 0;
         if (q.rays) {
             const float4 r0 = nt_load4(q.rays + 2 * size_t(id)), r1 = nt_load4(q.rays + 2 * size_t(id) + 1);
             org = vec3(r0.x, r0.y, r0.z); ray_dir = vec3(r1.x, r1.y, r1.z);
             tmin = r0.w; tmax = r1.w;
+        } else if (q.row) {
+            const int axis = q.row - 1;
+            const hx::Row w = hx::row_of(axis, id, q.nx, q.ny, q.nz);
+            row_base = w.base;
+            org = vec3(hx::lattice_centre(q.ox, w.x, q.sx), hx::lattice_centre(q.oy, w.y, q.sy), hx::lattice_centre(q.oz, w.z, q.sz));
+            ray_dir = vec3(axis == 0 ? 1.0f : 0.0f, axis == 1 ? 1.0f : 0.0f, axis == 2 ? 1.0f : 0.0f);
+            tmin = -__builtin_inff(); tmax = __builtin_inff();
         } else {
             if (q.points) {
                 const float4 p = nt_load4(q.points + size_t(id));
@@ -82,12 +152,17 @@ __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, con
 
         long long first = 0, room = 0;
         if (q.list) hx::slot_range(q.offsets, q.stride, q.capacity, id, first, room);
-        const EntrySink sink{q.entries + first, int(room < 0x7fffffffLL ? room : 0x7fffffffLL)};
+        Sink sink;
+        sink.entries = q.entries;
+        sink.is_row = q.row;
+        sink.row.emit = RowEmit{q.ws, q.inside, q.row_pass, q.row_last, 1};
+        sink.row.init(hx::Row{0, 0, 0, q.row_n, row_base, q.row_stride}, q.row_o, q.row_s, q.winding != 0);
+        if (!q.row) sink.set_list(first, int(room < 0x7fffffffLL ? room : 0x7fffffffLL));
 
         int votes = 0;
 #pragma unroll 1
         for (int d = 0; d < q.m; d++) {
-            const vec3 dir = q.rays ? ray_dir : (d == 0 ? vec3(q.d0x, q.d0y, q.d0z) : d == 1 ? vec3(q.d1x, q.d1y, q.d1z) : vec3(q.d2x, q.d2y, q.d2z));
+            const vec3 dir = (q.rays || q.row) ? ray_dir : (d == 0 ? vec3(q.d0x, q.d0y, q.d0z) : d == 1 ? vec3(q.d1x, q.d1y, q.d1z) : vec3(q.d2x, q.d2y, q.d2z));
             Hit rec(0, tmax, 0.0f, 0.0f);          // an inactive point takes no cell step
             if (active) {
                 hx::Counts n;
@@ -96,21 +171,38 @@ __global__ void __launch_bounds__(64) crossings_kernel(const TraverseArgs a, con
                 n_cells += n.cells; n_tests += n.tests; n_flushes += n.flushes;
             }
             votes += hx::vote(rec, q.winding != 0);
-            if (q.records) nt_store4(q.records + size_t(id) * size_t(q.m) + size_t(d), __int_as_float(rec.id), rec.t, rec.u, rec.v);
+            if (q.records) nt_store4(q.records + size_t(q.rec_base) + size_t(id) * size_t(q.m) + size_t(d), __int_as_float(rec.id), rec.t, rec.u, rec.v);
             if (q.list) {           // (m = 1) the slots the list left over get the empty entry
-                n_written = rec.id < sink.room ? rec.id : sink.room;
-                n_short = rec.id > sink.room ? 1 : 0;
+                n_written = rec.id < sink.room() ? rec.id : sink.room();
+                n_short = rec.id > sink.room() ? 1 : 0;
                 const unsigned long long none = EntrySink::word(tmax, 0xffffffffu);
-                for (long long p = n_written; p < room; p++) __builtin_nontemporal_store(none, sink.slots + p);
+                int again = id;
+                asm volatile("" : "+v"(again));         // the range once more, from the ray's number: neither it nor its address is carried through the walk
+                hx::slot_range(q.offsets, q.stride, q.capacity, again, first, room);
+                for (long long p = n_written; p < room; p++) __builtin_nontemporal_store(none, q.entries + first + p);
+            }
+            if (q.row) {            // (m = 1) the voxels behind the last crossing; a row that ends inside once more, as "abstains"
+                asm volatile("" : "+v"(sink.row.base));         // (as in RowEmit: nothing made from the base before the walk is carried through it)
+                sink.row.finish();
+                if (sink.row.state()) {
+                    n_abstained = 1;
+                    RowEmit abstains = sink.row.emit;
+                    abstains.valid = 0;
+                    abstains(sink.row.base, sink.row.stride, sink.row.n, 0);
+                }
             }
         }
-        if (q.inside) __builtin_nontemporal_store(active ? (2 * votes > q.m ? 1 : 0) : -1, q.inside + id);
+        if (q.inside && !q.row) __builtin_nontemporal_store(active ? (2 * votes > q.m ? 1 : 0) : -1, q.inside + id);
     }
     if (q.counters) {
         add_batch_counters(q.counters, lane, live ? 1 : 0, n_cells, n_tests, n_flushes);
         if (q.list) {               // entries written (without empty ones), rays whose list did not fit
             const unsigned long long sw = wave_sum_u64((unsigned)n_written), ss = wave_sum_u64((unsigned)n_short);
             if (lane == 0) { atomicAdd(q.counters + 4, sw); atomicAdd(q.counters + 5, ss); }
+        }
+        if (q.row) {                // rows that abstained
+            const unsigned long long sa = wave_sum_u64((unsigned)n_abstained);
+            if (lane == 0) atomicAdd(q.counters + 4, sa);
         }
     }
 }
@@ -144,7 +236,7 @@ int launch(hagrid_ctx* ctx, const char* who, bool ray_form, const hagrid_grid* g
     if (!aligned(tris, 16) || !aligned(q.rays, 16) || !aligned(q.points, 16) || !aligned(records, 16)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": triangles, rays, points and records must be 16-byte aligned").c_str());
     if (q.n == 0) return HAGRID_OK;
     if (!tris) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null triangle buffer").c_str());
-    if (q.list ? (!q.entries && q.capacity > 0) : (ray_form ? !records : !inside)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null output buffer").c_str());
+    if (q.list ? (!q.entries && q.capacity > 0) : ((ray_form && !q.row) ? !records : !inside)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null output buffer").c_str());
     HG_HIP(ctx, hipSetDevice(ctx->device));
     a.tris = static_cast<const float4*>(tris);
     a.num_rays = q.n;
@@ -209,4 +301,34 @@ extern "C" int hagrid_inside_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, c
     q.sx = size[0]; q.sy = size[1]; q.sz = size[2];
     q.nx = n[0]; q.ny = n[1];
     return launch(ctx, "inside_lattice", false, grid, tris, q, dirs, num_dirs, inside, records, counters, flags, HAGRID_INSIDE_WINDING);
+}
+
+extern "C" int hagrid_fill_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n, uint32_t axes, void* inside,
+                                   void* workspace, void* records, void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    int total = 0;
+    HG_TRY(check_lattice(ctx, "fill_lattice", origin, size, n, &total));
+    if (axes & ~7u) HG_FAIL(ctx, HAGRID_EINVAL, "fill_lattice: axes is a mask of 1 (x), 2 (y) and 4 (z)");
+    if (axes == 0) axes = 7u;
+    int passes = 0, last_axis = 0;
+    for (int a = 0; a < 3; a++)
+        if (axes & (1u << a)) { passes++; last_axis = a; }
+    if (passes > 1 && !workspace) HG_FAIL(ctx, HAGRID_EINVAL, "fill_lattice: more than one axis needs the workspace (one byte per voxel)");
+    CrossArgs q = {};
+    q.ox = origin[0]; q.oy = origin[1]; q.oz = origin[2];
+    q.sx = size[0]; q.sy = size[1]; q.sz = size[2];
+    q.nx = n[0]; q.ny = n[1]; q.nz = n[2];
+    q.m = 1;
+    q.ws = passes > 1 ? static_cast<unsigned char*>(workspace) : nullptr;
+    for (int a = 0; a < 3; a++) {
+        if (!(axes & (1u << a))) continue;
+        q.n = int(hx::num_rows(a, n[0], n[1], n[2]));          // rows <= voxels, which fit 31 bits
+        q.row = 1 + a; q.row_last = a == last_axis ? 1 : 0;
+        const hx::Row w = hx::row_of(a, 0, n[0], n[1], n[2]);
+        q.row_n = w.n; q.row_stride = w.stride; q.row_o = origin[a]; q.row_s = size[a];
+        HG_TRY(launch(ctx, "fill_lattice", true, grid, tris, q, nullptr, 0, inside, records, counters, flags, HAGRID_INSIDE_WINDING));
+        q.rec_base += q.n;
+        q.row_pass++;
+    }
+    return HAGRID_OK;
 }

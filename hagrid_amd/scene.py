@@ -1074,6 +1074,67 @@ def lattice_centres(origin, size, n) -> np.ndarray:
     return out
 
 
+def lattice_row_rays(origin, size, n, axis: int) -> np.ndarray:
+    """The row rays of hagrid_fill_lattice along `axis` (0, 1, 2) as (rows, 8) float32, the lower remaining axis fastest: org = the centre of the row's voxel 0
+    (origin + (float(c) + 0.5) * size on all three axes), dir = +e_axis, tmin = -inf, tmax = +inf."""
+    origin = np.asarray(origin, np.float32); size = np.asarray(size, np.float32)
+    dims = [int(v) for v in n]
+    lo, hi = [a for a in range(3) if a != axis]
+    slow, fast = np.meshgrid(np.arange(dims[hi]), np.arange(dims[lo]), indexing="ij")
+    c = [None, None, None]
+    c[axis] = np.zeros(fast.size, np.int64); c[lo] = fast.reshape(-1); c[hi] = slow.reshape(-1)
+    rays = np.zeros((fast.size, 8), dtype=np.float32)
+    for a in range(3):
+        rays[:, a] = origin[a] + (c[a].astype(np.float32) + np.float32(0.5)) * size[a]
+    rays[:, 3] = -np.inf; rays[:, 4 + axis] = 1.0; rays[:, 7] = np.inf
+    return rays
+
+
+def fill_lattice(tris: np.ndarray, origin, size, n, axes: int = 7, winding: bool = False, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of hagrid_fill_lattice by brute force (include/hagrid/crossings.h, "the fill"): one ray per voxel ROW of every requested axis (mask: 1 = x,
+    2 = y, 4 = z; 0 means 7), lattice_row_rays.  Voxel c of a row lies at tc(c) = centre(c) - centre(0) in float32; the state before c is taken over the
+    crossings with t < tc(c) -- searchsorted(t, tc, "left") of ray_crossing_lists: that count & 1, with winding (#leaving - #entering) != 0 --, the final state
+    over all of them.  A row whose final state is 1 abstains; otherwise it votes its state.  Returns "inside" int32 (nx * ny * nz,), x fastest: -1 when no row
+    through the voxel was usable, else 2 * votes > valid; "records" HIT_DTYPE, the records of the row rays (ray_crossings), axis after axis, and "abstained"
+    bool per row in the same order."""
+    origin = np.asarray(origin, np.float32); size = np.asarray(size, np.float32)
+    nx, ny, nz = (int(v) for v in n)
+    axes = int(axes) or 7
+    dims = (nx, ny, nz)
+    strides = (1, nx, nx * ny)
+    valid = np.zeros(nx * ny * nz, np.int32); votes = np.zeros(nx * ny * nz, np.int32)
+    records, abstained = [], []
+    for a in range(3):
+        if not axes & (1 << a):
+            continue
+        rays = lattice_row_rays(origin, size, n, a)
+        records.append(ray_crossings(tris, rays, chunk_pairs))
+        o, t, key = ray_crossing_lists(tris, rays, chunk_pairs)
+        c = np.arange(dims[a])
+        with np.errstate(all="ignore"):
+            centre = origin[a] + (c.astype(np.float32) + np.float32(0.5)) * size[a]
+            tc = (centre - centre[0]).astype(np.float32)
+        lo, hi = [b for b in range(3) if b != a]
+        out = np.zeros(rays.shape[0], bool)
+        for r in range(rays.shape[0]):
+            tr = t[o[r]:o[r + 1]]
+            if winding:
+                run = np.concatenate([[0], np.cumsum(np.where(key[o[r]:o[r + 1]] & 1, -1, 1))])
+                state = run != 0
+            else:
+                state = (np.arange(tr.size + 1) & 1) != 0
+            out[r] = state[-1]
+            if out[r]:
+                continue
+            k = np.searchsorted(tr, tc, "left")
+            e = (r % dims[lo]) * strides[lo] + (r // dims[lo]) * strides[hi] + c * strides[a]
+            valid[e] += 1
+            votes[e] += state[k]
+        abstained.append(out)
+    inside = np.where(valid == 0, -1, (2 * votes > valid).astype(np.int32)).astype(np.int32)
+    return {"inside": inside, "records": np.concatenate(records), "abstained": np.concatenate(abstained)}
+
+
 def generate_parallel(gen, first: int, count: int, chunk: int = 1 << 20, threads: int | None = None) -> np.ndarray:
     """gen(first, count) -> (count, 8) float32 for any slice (the generators above are counter-based): builds
     [first, first + count) from chunks made on a thread pool (numpy releases the GIL inside its loops)."""

@@ -1,4 +1,4 @@
-// hagrid/crossings.h -- crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice): ALL the
+// hagrid/crossings.h -- crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice, hagrid_fill_lattice): ALL the
 // surfaces a ray crosses, condensed into one 16-byte record or written out as a sorted list, and from that whether a point lies inside a closed surface.  No counterpart in the
 // reference, which answers with the nearest hit only.
 //
@@ -95,6 +95,12 @@
 #include "ray.h"
 #include "vec.h"
 
+#if defined(__clang__)
+#define HAGRID_NO_UNROLL _Pragma("clang loop unroll(disable) vectorize(disable)")
+#else
+#define HAGRID_NO_UNROLL
+#endif
+
 namespace hagrid {
 namespace crossings {
 
@@ -130,6 +136,14 @@ struct Accum {
 /// the sink that keeps nothing: the record alone
 struct NoSink {
     HOST DEVICE void operator()(int, float, uint32_t) const {}
+};
+
+/// How Page::flush hands its entries to a sink.  Default: from the unrolled loop over the page's slots, the sink's code once per slot -- right for a sink of a few
+/// instructions.  A sink with loops and stores of its own (RowSink below) is called from ONE place instead, in a loop that picks slot j by selects: SERIAL.  The
+/// entries, their order and the positions are the same; a kernel's sink may decide by a launch-uniform value.
+template <typename S>
+struct SinkTraits {
+    HOST DEVICE static bool serial(const S&) { return false; }
 };
 
 /// the slots of ray i in the list forms (above): first slot and room; room 0 for a pair of offsets that is negative, decreasing or beyond the capacity
@@ -194,6 +208,20 @@ struct Page {
     /// last of them; the page is empty afterwards
     template <typename S = NoSink>
     HOST DEVICE void flush(Accum& acc, const S& sink = S()) {
+        if (SinkTraits<S>::serial(sink)) {
+            HAGRID_NO_UNROLL
+            for (int j = 0; j < cap; j++) {         // (a page is sorted with its empty slots last)
+                uint32_t kj = key[0]; float tj = t[0];
+                HAGRID_UNROLL
+                for (int i = 1; i < PMAX; i++) { kj = i == j ? key[i] : kj; tj = i == j ? t[i] : tj; }
+                if (kj == kEmpty) break;
+                sink(acc.count, tj, kj);
+                acc.fold(tj, (kj & 1u) != 0);
+                has_cursor = true; cur_key = kj; cur_t = tj;
+            }
+            clear();
+            return;
+        }
         HAGRID_UNROLL
         for (int j = 0; j < PMAX; j++)
             if (j < cap && key[j] != kEmpty) {
@@ -290,9 +318,104 @@ HOST DEVICE inline int vote(const Hit& rec, bool winding) { return winding ? (as
 /// the centre of voxel c of a lattice along one axis
 HOST DEVICE inline float lattice_centre(float origin, int c, float size) { return origin + (float(c) + 0.5f) * size; }
 
+// ---- the fill: one ray per voxel ROW (hagrid_fill_lattice) ------------------------------------------------------------------------
+// For every requested axis a (mask bit 1 << a), every row of the lattice along a gets ONE ray: org = the centre of the row's voxel 0 (lattice_centre on all three
+// axes), dir = +e_a, tmin = -inf, tmax = +inf.  Voxel c of the row lies at tc(c) = lattice_centre(o_a, c, s_a) - lattice_centre(o_a, 0, s_a) (row_tc: one
+// subtraction; non-decreasing in c, since every operation is monotone in c).  The STATE BEFORE c is taken over the crossings with t < tc(c), strictly: their
+// count & 1, with winding (#leaving - #entering) != 0 -- counting from -inf, so a brick that begins inside the solid is right.  The row's FINAL state is the same
+// expression over all its crossings.  A row whose final state is 1 ends inside a surface that should be closed: one of its crossings was miscounted (a ray through
+// an edge, a vertex), or the surface is open.  That row ABSTAINS: no vote for any of its voxels.  Otherwise its vote for voxel c is the state before c.
+// inside[voxel] = combine(valid, votes): -1 when valid = 0, else 2 * votes > valid; valid = the requested axes whose row through the voxel did not abstain, votes
+// = those of them that vote 1.  A row admit_ray refuses has no crossings and votes 0.
+// Rows of an axis are numbered with the lower remaining axis fastest (row_of); the records of the row rays are those of crossings_walk over the row ray.
+// RowSink is a sink (above): between two crossings the state is constant, so on entry (t, key) it hands the current state to every voxel with tc(c) <= t as ONE
+// run, then folds the entry; finish() hands out the rest.  The sink interface is const: cursor and running sums are mutable.
+
+/// where voxel c of a row lies on the row's ray
+HOST DEVICE inline float row_tc(float origin, int c, float size) { return lattice_centre(origin, c, size) - lattice_centre(origin, 0, size); }
+
+/// the answer for a voxel from the rows through it
+HOST DEVICE inline int combine_votes(int valid, int votes) { return valid == 0 ? -1 : (2 * votes > valid ? 1 : 0); }
+
+/// What a PASS (one requested axis; passes run one after another, numbered 0, 1, 2 in ascending axis order) does with the vote of its row for voxel e.  The
+/// workspace byte keeps two bits per pass: bit 2k = the row of pass k did not abstain, bit 2k + 1 = it votes 1.  Pass 0 overwrites the byte (its content before
+/// is unspecified), a later pass replaces its own two bits, the LAST pass does not write the byte: it writes inside[e] from the byte and its own vote.  A
+/// row that abstains calls this again with valid = 0: its contribution is replaced, nobody else's is touched.  ws may be null when pass 0 is the last.
+HOST DEVICE inline unsigned row_bits(unsigned before, int pass, int valid, int vote) {
+    return (before & ~(3u << (2 * pass))) | (unsigned((valid ? 1 : 0) | ((valid && vote) ? 2 : 0)) << (2 * pass));
+}
+HOST DEVICE inline int row_answer(unsigned b) {
+    const int valid = int(b & 1u) + int((b >> 2) & 1u) + int((b >> 4) & 1u), votes = int((b >> 1) & 1u) + int((b >> 3) & 1u) + int((b >> 5) & 1u);
+    return combine_votes(valid, votes);
+}
+HOST DEVICE inline void row_put(unsigned char* ws, int* inside, int e, int pass, bool last, int valid, int vote) {
+    const unsigned b = row_bits(pass == 0 ? 0u : ws[e], pass, valid, vote);
+    if (last) inside[e] = row_answer(b);
+    else ws[e] = (unsigned char)b;
+}
+
+/// row r of axis a (0, 1, 2) of an nx * ny * nz lattice: the voxel it starts at, the index of that voxel (x fastest), the element stride and the voxels along it
+struct Row { int x, y, z, n, base, stride; };          // (an element index fits 31 bits: check_lattice)
+HOST DEVICE inline Row row_of(int axis, int r, int nx, int ny, int nz) {
+    Row w;
+    if (axis == 0)      { w.x = 0; w.y = r % ny; w.z = r / ny; w.n = nx; w.stride = 1; }
+    else if (axis == 1) { w.x = r % nx; w.y = 0; w.z = r / nx; w.n = ny; w.stride = nx; }
+    else                { w.x = r % nx; w.y = r / nx; w.z = 0; w.n = nz; w.stride = nx * ny; }
+    w.base = (w.z * ny + w.y) * nx + w.x;
+    return w;
+}
+/// the rows along axis a
+HOST DEVICE inline long long num_rows(int axis, int nx, int ny, int nz) { return axis == 0 ? (long long)ny * nz : axis == 1 ? (long long)nx * nz : (long long)nx * ny; }
+
+/// the ray of a row: from the centre of its voxel 0 along +e_axis, the whole line
+HOST DEVICE inline Ray row_ray(const Row& w, int axis, const float* origin, const float* size) {
+    const float inf = as<float>(uint32_t(0x7f800000u));
+    const vec3 org(lattice_centre(origin[0], w.x, size[0]), lattice_centre(origin[1], w.y, size[1]), lattice_centre(origin[2], w.z, size[2]));
+    return Ray(org, -inf, vec3(axis == 0 ? 1.0f : 0.0f, axis == 1 ? 1.0f : 0.0f, axis == 2 ? 1.0f : 0.0f), inf);
+}
+
+/// The row as a consumer of the sorted crossings.  E: emit(first, stride, length, state) -- `length` voxels from element `first` on, `stride` apart, get `state`.
+template <typename E>
+struct RowSink {
+    E emit;
+    int base, stride;               ///< the row's first element and element stride
+    int n; float o, s;              ///< voxels along the row; origin and voxel size of the row's axis
+    bool use_winding;
+    mutable int c, sum;             ///< the cursor: voxels [0, c) have their state; the crossings folded so far: their number, with winding #leaving - #entering
+
+    HOST DEVICE void init(const Row& w, float origin, float size, bool wind) {
+        base = w.base; stride = w.stride; n = w.n; o = origin; s = size; use_winding = wind; c = 0; sum = 0;
+    }
+    HOST DEVICE int state() const { return use_winding ? (sum != 0 ? 1 : 0) : (sum & 1); }
+    HOST DEVICE void operator()(int, float t, uint32_t key) const {
+        int e = c;
+        HAGRID_NO_UNROLL
+        while (e < n && row_tc(o, e, s) <= t) e++;
+        if (e > c) { emit(base + c * stride, stride, e - c, state()); c = e; }
+        sum += (use_winding && (key & 1u)) ? -1 : 1;
+    }
+    /// after the walk: the voxels behind the last crossing; state() is then the row's final state
+    HOST DEVICE void finish() const {
+        if (n > c) { emit(base + c * stride, stride, n - c, state()); c = n; }
+    }
+};
+
+template <typename E>
+struct SinkTraits<RowSink<E>> {
+    HOST DEVICE static bool serial(const RowSink<E>&) { return true; }
+};
+
+/// The definition of one row: the brute force over ALL triangles with the row as the sink.  Returns the record of the row ray; sink.state() is the final state.
+template <int PMAX = kMaxPage, typename F, typename E>
+HOST DEVICE inline Hit fill_row(F tri_at, int num_tris, const Ray& row, const RowSink<E>& sink) {
+    const Hit rec = crossings_brute_force<PMAX>(tri_at, num_tris, row, sink);
+    sink.finish();
+    return rec;
+}
+
 } // namespace crossings
 } // namespace hagrid
 
-// The C++ shim over the entry points (count_crossings, list_crossings, points_inside, inside_lattice) is with its neighbours in traverse.h.
+// The C++ shim over the entry points (count_crossings, list_crossings, points_inside, inside_lattice, fill_lattice) is with its neighbours in traverse.h.
 
 #endif // HAGRID_CROSSINGS_H

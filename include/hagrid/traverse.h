@@ -76,7 +76,7 @@ inline void overlap_tris(const Grid& grid, const Tri* tris, const Tri* queries, 
                                                              any ? HAGRID_OVERLAP_ANY : 0u));
 }
 
-/// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice; the record, the paging and the walk:
+/// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice, hagrid_fill_lattice; the record, the paging and the walk:
 /// crossings.h).  records: num_rays Hit-shaped records (count, t_first, length, winding bits); counters: nullptr or int64[4] -- DEVICE pointers.  Asynchronous.
 inline void count_crossings(const Grid& grid, const Tri* tris, const Ray* rays, Hit* records, int num_rays, void* counters = nullptr) {
     hagrid_grid p = detail::to_pod(grid);
@@ -106,6 +106,17 @@ inline void inside_lattice(const Grid& grid, const Tri* tris, const vec3& origin
     const int m[3] = {n.x, n.y, n.z};
     detail::check(detail::current_ctx(), hagrid_inside_lattice(detail::current_ctx(), &p, tris, o, s, m, dirs, num_dirs, inside, records, counters,
                                                                winding ? HAGRID_INSIDE_WINDING : 0u));
+}
+/// The inside of a closed surface on the lattice by scan lines, one ray per voxel row of every axis in `axes` (1 = x, 2 = y, 4 = z): hagrid_fill_lattice.  inside: one
+/// int32 per voxel (1, 0, or -1 where no row was usable); workspace: one byte per voxel, needed with more than one axis; records: nullptr or the records of the row
+/// rays; counters: nullptr or int64[5] -- DEVICE pointers.  winding (the recommended rule) counts leaving minus entering instead of the parity.
+inline void fill_lattice(const Grid& grid, const Tri* tris, const vec3& origin, const vec3& size, const ivec3& n, int* inside, void* workspace, unsigned axes = 7u,
+                         bool winding = true, Hit* records = nullptr, void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {size.x, size.y, size.z};
+    const int m[3] = {n.x, n.y, n.z};
+    detail::check(detail::current_ctx(), hagrid_fill_lattice(detail::current_ctx(), &p, tris, o, s, m, axes, inside, workspace, records, counters,
+                                                             winding ? HAGRID_INSIDE_WINDING : 0u));
 }
 
 /// Extension: independent batches in flight.  Every MemManager is a context with a stream of its own (hagrid_ctx_set_stream on

@@ -391,6 +391,23 @@ int hagrid_points_inside(hagrid_ctx* ctx, const hagrid_grid* grid, const void* t
                          const float* dirs, int num_dirs, void* inside, void* records, void* counters, uint32_t flags);
 int hagrid_inside_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n,
                           const float* dirs, int num_dirs, void* inside, void* records, void* counters, uint32_t flags);
+/* hagrid_fill_lattice: the inside of a closed surface on a lattice by SCAN LINES -- one ray per voxel ROW instead of one to three per voxel (solid voxelization,
+ * the sign of a distance field on a lattice).  origin, size, n: as for hagrid_inside_lattice, the same checks, the same voxel order (x fastest).  axes: a mask, 1 = x,
+ * 2 = y, 4 = z; 0 means 7.  For every requested axis a, every row of the lattice along a gets ONE ray: org = the centre of the row's voxel 0, dir = +e_a, tmin = -inf,
+ * tmax = +inf.  Voxel c of the row lies at tc(c) = centre_a(c) - centre_a(0) (float32, one subtraction).  The row's state BEFORE c is taken over the crossings of the
+ * row ray with t < tc(c), strictly: their count & 1, with HAGRID_INSIDE_WINDING (#leaving - #entering) != 0; its FINAL state is the same expression over all its
+ * crossings.  A row whose final state is 1 ends inside a surface that should be closed (a miscounted crossing, or an open surface): it ABSTAINS.  Otherwise its vote
+ * for voxel c is the state before c.  inside[voxel] (int32, 4-byte aligned) is 1 when 2 * votes > valid, else 0, and -1 when valid = 0: valid = the requested axes
+ * whose row through the voxel did not abstain, votes = those of them that vote 1.  A row whose ray is not admissible (overflowed centres) has no crossings and votes
+ * 0.  The answer means something for CLOSED surfaces only; a centre ON the surface gets what the formula gives.  HAGRID_INSIDE_WINDING is the recommended rule: a row
+ * through an edge that two triangles of one face share is accepted by both, which parity counts as no surface at all and the winding number counts right
+ * (DESIGN.md 4.11).  workspace: DEVICE, one byte per voxel, required when more than one axis is requested, else it may be NULL; its content afterwards is
+ * unspecified.  records: NULL, or DEVICE records of the row rays (16-byte aligned), bit for bit those of hagrid_count_crossings: axis after axis in ascending order,
+ * within an axis the lower remaining axis fastest.  counters: NULL, or DEVICE int64[5], ADDED to: rows, cells visited, triangle tests, pages flushed, rows that
+ * abstained.  One launch per requested axis, asynchronous on the context's stream; the traversal image, ray binning and the hints are neither used nor touched.
+ * HAGRID_EINVAL: as for hagrid_inside_lattice, and an axes bit beyond 7, a missing workspace with more than one axis, a misaligned inside. */
+int hagrid_fill_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n,
+                        uint32_t axes, void* inside, void* workspace, void* records, void* counters, uint32_t flags);
 
 /* Extension (no reference counterpart): spatial binning of the ray batch before traversal.  mode 0 (default): rays
  * are traversed in buffer order, as the reference does.  mode 1: each hagrid_traverse_grid call first bins the rays by
