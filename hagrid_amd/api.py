@@ -356,6 +356,35 @@ def traverse_grid_multi(grid: Grid, tris: int, rays: int, hits: int, num_rays: i
     _check(mem, mem._L.hagrid_traverse_grid_multi(mem._ctx, C.byref(grid.pod), C.c_void_p(tris), C.c_void_p(rays), C.c_void_p(hits), int(num_rays), int(k), int(flags)), "traverse_grid_multi")
 
 
+RAY_MASK_ALL = 0xFFFFFFFF  # HAGRID_RAY_MASK_ALL
+
+
+def traverse_grid_filtered(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, k: int, filters: int = 0, tri_masks: int = 0, flags: int = 0):
+    """Extension (hagrid_traverse_grid_filtered): traverse_grid_multi over the triangles that TAKE PART for each ray -- triangle j for ray i exactly
+    when (mask_i & tri_masks[j]) != 0 and j != skip_i.  filters: 0 (every ray sees everything) or the address of num_rays records of 8 bytes, int32 pairs
+    (mask, skip) -- what skip_filters makes; skip < 0 skips nothing.  tri_masks: 0 (all ones) or one 32-bit mask per triangle -- what
+    MeshScene.instance_masks makes.  hits: num_rays * k Hit records, the layout and order of traverse_grid_multi.  flags: 0 | UVS | ANY_HIT; ANY_HIT
+    needs k = 1 and reports SOME candidate, not a promised one (occlusion rays: skip = the triangle the ray starts on, tmin = 0).  Asynchronous on the manager's stream."""
+    mem = grid.mem
+    _check(mem, mem._L.hagrid_traverse_grid_filtered(mem._ctx, C.byref(grid.pod), C.c_void_p(tris), C.c_void_p(rays), C.c_void_p(filters or 0), C.c_void_p(tri_masks or 0),
+                                                     C.c_void_p(hits), int(num_rays), int(k), int(flags)), "traverse_grid_filtered")
+
+
+def skip_filters(hits, mask: int = RAY_MASK_ALL, mem: MemManager | None = None):
+    """The filter records that make every ray skip the triangle of a hit: hits is a torch tensor of n Hit records as 4 x int32 (shape (n, 4), or anything
+    that views as it: the output of traverse_grid on the device); returns the (n, 2) int32 tensor (mask, skip = hits.id) for traverse_grid_filtered -- a
+    miss (id -1) skips nothing.  Torch operations on the manager's stream, no kernel of this library."""
+    import torch
+    mem = mem or _current
+    m = int(mask) & 0xFFFFFFFF
+    with torch.cuda.stream(mem.torch_stream()):
+        h = hits.view(torch.int32).reshape(-1, 4)
+        out = torch.empty((h.shape[0], 2), dtype=torch.int32, device=h.device)
+        out[:, 0] = m - (1 << 32) if m >= (1 << 31) else m
+        out[:, 1] = h[:, 0]
+    return out
+
+
 def closest_points(grid: Grid, tris: int, points: int, results: int, n: int, counters: int = 0):
     """Extension (hagrid_closest_points): for each of n points (16 bytes: x, y, z, r -- POINT_QUERY_DTYPE) the nearest triangle within r: 32 bytes
     per query into `results` (CLOSEST_DTYPE: q, d2, id, feature, side); nothing within r: id -1, d2 = r * r, q = p.  counters: 0, or a device int64[4]
@@ -686,6 +715,20 @@ class MeshScene:
                 offset += nv
         return out
 
+    def instance_masks(self, masks):
+        """The triangle masks of traverse_grid_filtered for the assembled triangles: masks holds one 32-bit mask per INSTANCE; returns a torch int32 tensor
+        (num_tris,) on the device in which every triangle carries its instance's mask (the bits of the uint32).  Fills on the manager's stream."""
+        import torch
+        mem = self.mem
+        masks = [int(m) & 0xFFFFFFFF for m in masks]
+        if len(masks) != self.num_instances:
+            raise ValueError(f"instance_masks: {len(masks)} masks for {self.num_instances} instances")
+        with torch.cuda.stream(mem.torch_stream()):
+            out = torch.empty((self.num_tris,), dtype=torch.int32, device=f"cuda:{mem.device}")
+            for i, m in enumerate(masks):
+                out[self.first_tri(i):self.first_tri(i + 1)] = m - (1 << 32) if m >= (1 << 31) else m
+        return out
+
     def bad_indices(self) -> int:
         """Output triangles of the assemble() calls since the last query that named a vertex outside their mesh (each became the degenerate
         triangle on vertex 0); waits for the stream and resets the count."""
@@ -757,6 +800,7 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "Camera", "gen_primary_rays", "gen_bounce_rays", "shade_hits", "accumulate_occlusion", "shade_occlusion", "frame_workspace_bytes",
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
+           "traverse_grid_filtered", "skip_filters", "RAY_MASK_ALL",
            "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
            "overlap_tris", "self_intersections",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

@@ -1012,6 +1012,42 @@ def ray_crossing_lists(tris: np.ndarray, rays: np.ndarray, chunk_pairs: int = 1 
     return offsets, t.astype(np.float32), (j * 2 + ng).astype(np.int32)
 
 
+RAY_MASK_ALL = 0xFFFFFFFF
+
+
+def takes_part(ray_idx, tri_idx, filters=None, tri_masks=None) -> np.ndarray:
+    """ray_filter.h on parallel index arrays: triangle tri_idx[p] TAKES PART for ray ray_idx[p] exactly when (mask & tri_masks[tri]) != 0 and tri != skip.
+    filters: None (every ray sees everything) or (n, 2) integers (mask, skip), the mask read as 32 bits; tri_masks: None (all ones) or one mask per triangle."""
+    ray_idx = np.asarray(ray_idx, dtype=np.int64); tri_idx = np.asarray(tri_idx, dtype=np.int64)
+    if filters is None:
+        mask = np.full(ray_idx.shape, RAY_MASK_ALL, dtype=np.int64); skip = np.full(ray_idx.shape, -1, dtype=np.int64)
+    else:
+        f = np.asarray(filters).reshape(-1, 2).astype(np.int64)
+        mask = f[ray_idx, 0] & RAY_MASK_ALL; skip = f[ray_idx, 1]
+    tm = np.full(tri_idx.shape, RAY_MASK_ALL, dtype=np.int64) if tri_masks is None else np.asarray(tri_masks).reshape(-1).astype(np.int64)[tri_idx] & RAY_MASK_ALL
+    return ((mask & tm) != 0) & (tri_idx != skip)
+
+
+def filtered_hits(tris: np.ndarray, rays: np.ndarray, k: int, filters=None, tri_masks=None, chunk_pairs: int = 1 << 21) -> tuple[np.ndarray, np.ndarray]:
+    """The definition of hagrid_traverse_grid_filtered by brute force: rays (n, 8) float32 -> (ids int32 (n, k), t float32 (n, k)).  Of the sorted (ray,
+    triangle, t) pairs every ray crosses (_sorted_crossings: intersect_prim_ray with the ray's own window, by ray, then t, then id) those whose triangle takes
+    part for the ray (takes_part) are the candidates; ray i gets its first min(k, m), unused slots id -1 and the bits of its tmax.  Without filters these are
+    the lists of hagrid_traverse_grid_multi."""
+    R, r, j, t, _ = _sorted_crossings(tris, rays, chunk_pairs)
+    n = R.shape[0]
+    keep = takes_part(r, j, filters, tri_masks)
+    r, j, t = r[keep], j[keep], t[keep]
+    ids = np.full((n, k), -1, dtype=np.int32)
+    out_t = np.repeat(np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)[:, 7:8], k, axis=1)
+    if r.size:
+        first = np.searchsorted(r, np.arange(n))
+        slot = np.arange(r.size) - first[r]
+        sel = slot < k
+        ids[r[sel], slot[sel]] = j[sel]
+        out_t[r[sel], slot[sel]] = t[sel]
+    return ids, out_t
+
+
 def crossing_slots(offsets_or_stride, capacity: int, lists, tmax) -> dict:
     """What hagrid_list_crossings leaves in every one of `capacity` slots.  offsets_or_stride: int64 (n + 1,) offsets (the CSR form) or an int S >= 1 (the
     stride form: ray i owns [i * S, (i + 1) * S)); lists: (offsets, t, key) of ray_crossing_lists; tmax (n,) float32.  The room of ray i is 0 when its pair

@@ -43,6 +43,16 @@ inline void traverse_grid_multi(const Grid& grid, const Tri* tris, const Ray* ra
     detail::check(detail::current_ctx(), hagrid_traverse_grid_multi(detail::current_ctx(), &p, tris, rays, hits, num_rays, k, with_uvs ? HAGRID_TRAVERSE_UVS : 0u));
 }
 
+/// Extension: traverse_grid_multi over the triangles that TAKE PART for each ray (hagrid_amd.h: hagrid_traverse_grid_filtered; the rule: ray_filter.h).
+/// filters: nullptr or one 8-byte record per ray (uint32 mask, int32 skip -- RayFilter of ray_filter.h); tri_masks: nullptr or one uint32 per triangle;
+/// both DEVICE pointers.  any_hit needs k = 1: the ray stops at the first candidate the walk meets (occlusion rays with self-exclusion).
+inline void traverse_grid_filtered(const Grid& grid, const Tri* tris, const Ray* rays, const void* filters, const uint32_t* tri_masks, Hit* hits,
+                                   int num_rays, int k, bool with_uvs = false, bool any_hit = false) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_traverse_grid_filtered(detail::current_ctx(), &p, tris, rays, filters, tri_masks, hits, num_rays, k,
+                                                                       (with_uvs ? HAGRID_TRAVERSE_UVS : 0u) | (any_hit ? HAGRID_TRAVERSE_ANY_HIT : 0u)));
+}
+
 /// Extension: nearest-surface queries (hagrid_amd.h: hagrid_closest_points; the arithmetic and the walk: closest.h).  points: num_points records of
 /// 16 bytes (x, y, z, r), results: 32 bytes each ({qx, qy, qz, d2}, {int id, int feature, float side, 0}), counters: nullptr or int64[4] -- all DEVICE
 /// pointers, 16-byte aligned.  Asynchronous on the context's stream.

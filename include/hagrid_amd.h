@@ -260,7 +260,8 @@ int hagrid_traverse_grid_stats(hagrid_ctx* ctx, const hagrid_grid* grid, const v
  *   - k = 1 is NOT promised to equal hagrid_traverse_grid bit for bit: the nearest-hit walk shrinks tmax in its scaled comparison and
  *     breaks ties in t by list order (the two differ in a ray or two of ten thousand on a mesh);
  *   - calling hagrid_traverse_grid k times with tmin = nextafter(t) is NOT this query: intersect_prim_ray compares t with
- *     abs_det * tmin in the scaled domain, so the triangle just found is accepted again.
+ *     abs_det * tmin in the scaled domain, so the triangle just found is accepted again.  (hagrid_traverse_grid_filtered below continues a
+ *     ray past a hit: tmin = t and skip = the triangle just found.)
  * flags: 0 or HAGRID_TRAVERSE_UVS.  Asynchronous on the context's stream.  One launch walks the CONSTRUCTION format in buffer order
  * with the list in registers (hagrid_amd/csrc/trav_multi.hip): the traversal image, hagrid_set_ray_binning, tile packets and the
  * learned tile order are not applied, and the hints kept for the nearest-hit path stay untouched.  HAGRID_EINVAL: k < 1 or
@@ -270,6 +271,34 @@ int hagrid_traverse_grid_stats(hagrid_ctx* ctx, const hagrid_grid* grid, const v
 #define HAGRID_MAX_HITS 8
 int hagrid_traverse_grid_multi(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
                                const void* rays, void* hits, int num_rays, int k, uint32_t flags);
+
+/* Extension (no reference counterpart): FILTERED traversal -- hagrid_traverse_grid_multi in which every ray says which triangles it sees
+ * (Embree's ray mask, the visibility masks of OptiX / DXR, "ignore the primitive I start on"): shadow rays that leave from a surface with
+ * tmin = 0 and no epsilon, a ray continued past the hit it just reported, a sensor that does not see its own body.
+ *   filters    DEVICE, 8 bytes per ray, 8-byte aligned: uint32 mask, int32 skip.  NULL: mask = HAGRID_RAY_MASK_ALL and no skip for every
+ *              ray.  skip < 0 (any negative value) skips nothing, and so does a skip that names no triangle.
+ *   tri_masks  DEVICE, uint32 per triangle of the array the grid was built over, 4-byte aligned.  NULL: all ones.  Its length is the
+ *              caller's business, as with tris.
+ * Triangle j TAKES PART for ray i exactly when (mask_i & tri_masks[j]) != 0 and j != skip_i (include/hagrid/ray_filter.h).  The CANDIDATES of
+ * ray i are the intersections of hagrid_traverse_grid_multi -- the same acceptance, the ray's own, unshrunk window -- with the triangles that
+ * take part.  hits has exactly that entry point's layout: ray i gets k records, the min(k, m) smallest of its m candidates in the order
+ * (t ascending, then id ascending), unused slots id = -1, t = tmax, u = v = 0.  So:
+ *   - the list for k is a prefix of the list for k + 1;
+ *   - the answer equals the unfiltered answer over the scene with the triangles that take no part deleted, ids unchanged;
+ *   - a ray with mask == 0 takes no cell step and gets k empty slots; inactive and inadmissible rays are treated as in multi-hit;
+ *   - with filters == NULL, tri_masks == NULL and no HAGRID_TRAVERSE_ANY_HIT the output is that of hagrid_traverse_grid_multi, bit for bit.
+ * flags: HAGRID_TRAVERSE_UVS and HAGRID_TRAVERSE_ANY_HIT.  Any-hit needs k = 1: the ray stops behind the first cell in which the walk met a
+ * candidate; hits[i].id >= 0 exactly when the candidate set is not empty, and id and t are those of SOME candidate, t that pair's own t bit for
+ * bit (the contract of HAGRID_OVERLAP_ANY: which candidate is not promised).  It is the occlusion ray with self-exclusion: skip = the triangle the ray starts on, tmin = 0.
+ * A mode of the multi-hit kernel (hagrid_amd/csrc/trav_multi.hip), asynchronous on the context's stream: the traversal image, ray binning,
+ * tile packets, the learned tile order and the hints kept for the nearest-hit path are neither used nor touched.  Errors: everything
+ * hagrid_traverse_grid_multi refuses, with the same codes (k < 1 or k > HAGRID_MAX_HITS, a released grid, "traverse.id_is_steps" = 1,
+ * HAGRID_ERANGE for num_rays * k beyond 2^31 - 1, the level limit of the grid); HAGRID_EINVAL in addition for HAGRID_TRAVERSE_ANY_HIT with
+ * k != 1, an unknown flag, misaligned filters or tri_masks.  num_rays = 0 is HAGRID_OK. */
+#define HAGRID_RAY_MASK_ALL 0xFFFFFFFFu
+int hagrid_traverse_grid_filtered(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
+                                  const void* rays, const void* filters, const void* tri_masks,
+                                  void* hits, int num_rays, int k, uint32_t flags);
 
 /* Extension (no reference counterpart): NEAREST-SURFACE queries -- for every point of a batch the triangle nearest to it, how far it is and where
  * on it (distance fields, contact and collision in simulation loops, snapping points to a surface; Embree's rtcPointQuery, Open3D's
