@@ -565,6 +565,40 @@ def solid_voxels(grid: Grid, tris, origin, size, n, axes: int = 7, winding: bool
     return inside
 
 
+def distance_lattice(grid: Grid, tris: int, origin, size, n, band: float, workspace: int, ids: int = 0, d2: int = 0, records: int = 0, counters: int = 0):
+    """Extension (hagrid_distance_lattice): closest_points over the voxel centres of the lattice of inside_lattice with r = band (finite, >= 0), made by scatter:
+    every triangle visits the voxels within the band of it and takes the minimum into the voxel's slot.  workspace: 8 bytes per voxel on the device (initialised
+    by the call); ids (int32), d2 (float32), records (CLOSEST_DTYPE, 32 bytes): one per voxel, x fastest, each may be 0 but not all three.  Nothing within the band:
+    id -1, d2 = band * band, q = the centre.  counters: 0, or a device int64[4] added to (triangles with a voxel box, tasks, pairs within the band, voxels with an
+    answer).  Device addresses; on the manager's stream.  scene.distance_lattice states the results in numpy, bit for bit."""
+    mem = grid.mem or _current
+    o = (C.c_float * 3)(*[float(v) for v in origin]); s = (C.c_float * 3)(*[float(v) for v in size]); k = (C.c_int * 3)(*[int(v) for v in n])
+    _check(mem, mem._L.hagrid_distance_lattice(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), o, s, k, C.c_float(float(band)), C.c_void_p(workspace or 0),
+                                               C.c_void_p(ids or 0), C.c_void_p(d2 or 0), C.c_void_p(records or 0), C.c_void_p(counters or 0), 0), "distance_lattice")
+
+
+def signed_distance_lattice(grid: Grid, tris, origin, size, n, band: float, axes: int = 7) -> dict:
+    """A narrow-band signed distance field of a closed surface on the lattice: distance_lattice for the magnitude and fill_lattice (winding rule) for the sign, on
+    torch's current stream (the manager must run on it: mem.use_stream(torch.cuda.current_stream().cuda_stream)), the workspaces allocated here.  tris: a torch
+    tensor on the device (or a device address).  Returns torch tensors of shape (nz, ny, nx): "sdf" float32 = sqrt(d2), negative where inside == 1, so +-band where
+    no triangle lies within the band; "d2" float32; "ids" int32 (-1: none); "inside" int32 (1, 0, or -1 where no row was usable: such voxels keep the positive
+    sign).  The sign is fill_lattice's: not robust for centres ON the surface."""
+    import torch
+    nx, ny, nz = (int(v) for v in n)
+    dev = tris.device if hasattr(tris, "device") else torch.device("cuda", torch.cuda.current_device())
+    d_tris = tris.data_ptr() if hasattr(tris, "data_ptr") else int(tris or 0)
+    ids = torch.empty((nz, ny, nx), dtype=torch.int32, device=dev)
+    d2 = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    inside = torch.empty((nz, ny, nx), dtype=torch.int32, device=dev)
+    slots = torch.empty(nx * ny * nz, dtype=torch.int64, device=dev)
+    work = torch.empty(nx * ny * nz, dtype=torch.uint8, device=dev)
+    distance_lattice(grid, d_tris, origin, size, (nx, ny, nz), band, slots.data_ptr(), ids=ids.data_ptr(), d2=d2.data_ptr())
+    fill_lattice(grid, d_tris, origin, size, (nx, ny, nz), inside.data_ptr(), axes=axes, workspace=work.data_ptr(), flags=INSIDE_WINDING)
+    sdf = torch.sqrt(d2)
+    sdf = torch.where(inside == 1, -sdf, sdf)
+    return {"sdf": sdf, "d2": d2, "ids": ids, "inside": inside}
+
+
 def traverse_grid_stats(grid: Grid, tris: int, rays: int, hits: int, num_rays: int, steps: int = 0) -> dict:
     mem = grid.mem or _current
     st = TraversalStats()

@@ -763,6 +763,14 @@ struct PlainOut {
 
 using Temps = PoolTemps;
 
+} // namespace
+
+int hagrid_impl::scan_plain(hagrid_ctx* ctx, const int* in, int* out, int n, int* total, int* too_large) {
+    return ctx_scan<int>(ctx, PlainIn{in}, PlainOut{out, too_large}, n, (int*)nullptr, (const int*)nullptr, total) ? HAGRID_OK : HAGRID_ENOMEM;
+}
+
+namespace {
+
 // ---- the level loop and the concatenation (host side) --------------------------------------------------------------------------------------------------
 struct GLevel {
     int2* refs = nullptr; int num_refs = 0;     // {reference, cell}, grouped by cell, in cell order

@@ -1,6 +1,6 @@
 // frame.hip -- a frame on the device: primary rays, bounce rays, shading, ambient occlusion (include/hagrid_amd.h "frames on the device").
 //
-// Four streaming kernels (the two ambient-occlusion steps are one, with a mode argument; so are the picture of hits and the layered picture of multi-hit lists), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
+// Three streaming kernels (the two ray generators are one, with a mode argument; so are the two ambient-occlusion steps, and the picture of hits and the layered picture of multi-hit lists), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
 // host program calls); the kernels only move the records: a Ray is two float4 and a Hit one, loaded and stored as such (16-byte accesses,
 // what the traversal kernels read: rays[2 * i], rays[2 * i + 1]), a pixel is one 32-bit word.  Mode, miss rule and flags are kernel
 // arguments, not template parameters: one kernel each.  hagrid_render_frame strings them together with hagrid_traverse_grid_ex on the
@@ -24,31 +24,37 @@ __device__ inline void store_ray(float4* __restrict__ rays, int i, const Ray& r)
     rays[2 * size_t(i) + 1] = make_float4(r.dir.x, r.dir.y, r.dir.z, r.tmax);
 }
 
-__global__ void __launch_bounds__(kBlock) frame_primary_rays_kernel(hf::Camera cam, float clip, int w, int h, long long first, int count, float4* __restrict__ rays) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= count) return;
-    store_ray(rays, i, hf::primary_ray(cam, clip, w, h, first + i));
-}
+// The two ray generators share one kernel (the product library's kernel budget): `hits` is launch-uniform.  hits == nullptr: the primary ray
+// of pixel first + i (hagrid_gen_primary_rays; cam, clip, w, h); else the bounce ray of hit i (hagrid_gen_bounce_rays; tris: 12 floats per triangle, the
+// normal in words 3, 7, 11 -- the only gather of this file).  The arithmetic is hf::primary_ray / hf::bounce_ray either way: the rays are the bits they were.
+struct RayGenArgs {
+    hf::Camera cam; float clip; int w, h;                                   // primary
+    const float* __restrict__ tris; const float4* __restrict__ rays; const float4* __restrict__ hits;      // bounce
+    unsigned long long seed; vec3 lo, hi; float tmax; unsigned flags;
+    unsigned long long first; int n;
+    float4* __restrict__ out;
+};
 
-// tris: 12 floats per triangle, the normal in words 3, 7, 11 -- the only gather of this file
-__global__ void __launch_bounds__(kBlock) frame_bounce_rays_kernel(const float* __restrict__ tris, const float4* __restrict__ rays, const float4* __restrict__ hits, int n,
-                                                                   unsigned long long seed, unsigned long long first, vec3 lo, vec3 hi, float tmax, unsigned flags,
-                                                                   float4* __restrict__ out) {
+__global__ void __launch_bounds__(kBlock) frame_rays_kernel(const RayGenArgs a) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 hv = hits[i];
-    const int id = __float_as_int(hv.x);
+    if (i >= a.n) return;
     Ray r;
-    if (id >= 0) {
-        const float4 a = rays[2 * size_t(i)], b = rays[2 * size_t(i) + 1];
-        const float* t = tris + 12 * size_t(id);
-        r = hf::bounce_ray(Ray(vec3(a.x, a.y, a.z), a.w, vec3(b.x, b.y, b.z), b.w), hv.y, vec3(t[3], t[7], t[11]), seed, first + uint64_t(i), tmax);
-    } else if (flags & HAGRID_BOUNCE_REDRAW_MISSES) {
-        r = hf::incoherent_ray(lo, hi, seed ^ 0x6D69737300000000ull, first + uint64_t(i), 0.0f, FLT_MAX);
+    if (!a.hits) {
+        r = hf::primary_ray(a.cam, a.clip, a.w, a.h, (long long)a.first + i);
     } else {
-        r = hf::inactive_ray();
+        const float4 hv = a.hits[i];
+        const int id = __float_as_int(hv.x);
+        if (id >= 0) {
+            const float4 p = a.rays[2 * size_t(i)], q = a.rays[2 * size_t(i) + 1];
+            const float* t = a.tris + 12 * size_t(id);
+            r = hf::bounce_ray(Ray(vec3(p.x, p.y, p.z), p.w, vec3(q.x, q.y, q.z), q.w), hv.y, vec3(t[3], t[7], t[11]), a.seed, a.first + uint64_t(i), a.tmax);
+        } else if (a.flags & HAGRID_BOUNCE_REDRAW_MISSES) {
+            r = hf::incoherent_ray(a.lo, a.hi, a.seed ^ 0x6D69737300000000ull, a.first + uint64_t(i), 0.0f, FLT_MAX);
+        } else {
+            r = hf::inactive_ray();
+        }
     }
-    store_ray(out, i, r);
+    store_ray(a.out, i, r);
 }
 
 // The two shading entry points share one kernel (the product library's kernel budget): `k` is launch-uniform.
@@ -104,9 +110,10 @@ extern "C" int hagrid_gen_primary_rays(hagrid_ctx* ctx, const hagrid_camera* cam
     if (first < 0 || first + int64_t(count) > int64_t(width) * int64_t(height)) HG_FAIL(ctx, HAGRID_EINVAL, "gen_primary_rays: the pixel range [first, first + count) leaves the image");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, rays, size_t(count) * 32);
-    hf::Camera c;
-    memcpy(&c, cam, sizeof(c));
-    frame_primary_rays_kernel<<<grid_blocks(count, kBlock), kBlock, 0, ctx->stream>>>(c, clip, width, height, (long long)first, count, static_cast<float4*>(rays));
+    RayGenArgs a = {};
+    memcpy(&a.cam, cam, sizeof(a.cam));
+    a.clip = clip; a.w = width; a.h = height; a.first = (unsigned long long)first; a.n = count; a.out = static_cast<float4*>(rays);
+    frame_rays_kernel<<<grid_blocks(count, kBlock), kBlock, 0, ctx->stream>>>(a);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -123,9 +130,11 @@ extern "C" int hagrid_gen_bounce_rays(hagrid_ctx* ctx, const void* tris, const v
     if (flags & ~HAGRID_BOUNCE_REDRAW_MISSES) HG_FAIL(ctx, HAGRID_EINVAL, "gen_bounce_rays: unknown flag");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, out_rays, size_t(num_rays) * 32);
-    frame_bounce_rays_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(
-        static_cast<const float*>(tris), static_cast<const float4*>(rays), static_cast<const float4*>(hits), num_rays, seed, first,
-        vec3(bbox_min[0], bbox_min[1], bbox_min[2]), vec3(bbox_max[0], bbox_max[1], bbox_max[2]), tmax, flags, static_cast<float4*>(out_rays));
+    RayGenArgs a = {};
+    a.tris = static_cast<const float*>(tris); a.rays = static_cast<const float4*>(rays); a.hits = static_cast<const float4*>(hits);
+    a.seed = seed; a.lo = vec3(bbox_min[0], bbox_min[1], bbox_min[2]); a.hi = vec3(bbox_max[0], bbox_max[1], bbox_max[2]); a.tmax = tmax; a.flags = flags;
+    a.first = first; a.n = num_rays; a.out = static_cast<float4*>(out_rays);
+    frame_rays_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(a);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

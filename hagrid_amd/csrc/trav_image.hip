@@ -538,7 +538,21 @@ __global__ void __launch_bounds__(kBlock) max_ref_kernel(const int* __restrict__
     m = wave_max(m);
     if (lane_id() == 0 && m >= 0) atomicMax(out, m);
 }
+int read_max_ref(hagrid_ctx* ctx, const hagrid_grid* g, int* max_ref) {
+    int* word = ctx->dscratch + kScrMaxRef;
+    HG_HIP(ctx, hipMemsetAsync(word, 0xff, sizeof(int), ctx->stream));
+    max_ref_kernel<<<std::min(grid_blocks(g->num_refs, kBlock), 2048), kBlock, 0, ctx->stream>>>(static_cast<const int*>(g->ref_ids), g->num_refs, word); HG_DBG(ctx);
+    return read_back(ctx, word, max_ref, sizeof(int));
+}
 } // namespace
+
+int hagrid_impl::grid_max_ref(hagrid_ctx* ctx, const hagrid_grid* g, int* max_ref) {
+    *max_ref = -1;
+    if (trav_image_matches(ctx, g) && !trav_image_stale(ctx)) { *max_ref = ctx->image.max_ref; return HAGRID_OK; }
+    if (!g->ref_ids || g->num_refs <= 0) return HAGRID_OK;
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+    return read_max_ref(ctx, g, max_ref);
+}
 
 int hagrid_impl::trav_image_build(hagrid_ctx* ctx, const hagrid_grid* g) {
     trav_image_drop(ctx);
@@ -578,10 +592,7 @@ int hagrid_impl::trav_image_build(hagrid_ctx* ctx, const hagrid_grid* g) {
     img.dims[0] = g->dims[0]; img.dims[1] = g->dims[1]; img.dims[2] = g->dims[2];
     if (img.valid) img.alive = std::make_shared<std::atomic<bool>>(true);
     if (img.valid && g->num_refs > 0) {
-        int* word = ctx->dscratch + kScrMaxRef;
-        HG_HIP(ctx, hipMemsetAsync(word, 0xff, sizeof(int), ctx->stream));
-        max_ref_kernel<<<std::min(grid_blocks(g->num_refs, kBlock), 2048), kBlock, 0, ctx->stream>>>(static_cast<const int*>(g->ref_ids), g->num_refs, word); HG_DBG(ctx);
-        const int rb = read_back(ctx, word, &img.max_ref, sizeof(int));
+        const int rb = read_max_ref(ctx, g, &img.max_ref);
         if (rb != HAGRID_OK) {                     // img is not the context's yet: its buffers go back here
             hagrid_mem_free(ctx, img.blocks); hagrid_mem_free(ctx, img.table);
             return rb;

@@ -146,6 +146,7 @@ SIGNATURES = {
     "hagrid_points_inside": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, C.POINTER(C.c_float), _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_inside_lattice": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float), _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_fill_lattice": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "hagrid_distance_lattice": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_set_ray_binning": (_i32, [_vp, _i32]),
     "hagrid_set_option": (_i32, [_vp, C.c_char_p, _i32]),
     "hagrid_traversal_image_info": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(_i64)]),

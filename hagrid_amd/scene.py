@@ -1110,6 +1110,13 @@ def lattice_centres(origin, size, n) -> np.ndarray:
     return out
 
 
+def distance_lattice(tris: np.ndarray, origin, size, n, band: float, chunk_pairs: int = 1 << 21) -> np.ndarray:
+    """The definition of hagrid_distance_lattice: closest_points over lattice_centres with r = band (finite, >= 0) -> CLOSEST_DTYPE records, x fastest."""
+    pts = lattice_centres(origin, size, n)
+    pts["r"] = np.float32(band)
+    return closest_points(tris, pts, chunk_pairs)
+
+
 def lattice_row_rays(origin, size, n, axis: int) -> np.ndarray:
     """The row rays of hagrid_fill_lattice along `axis` (0, 1, 2) as (rows, 8) float32, the lower remaining axis fastest: org = the centre of the row's voxel 0
     (origin + (float(c) + 0.5) * size on all three axes), dir = +e_axis, tmin = -inf, tmax = +inf."""

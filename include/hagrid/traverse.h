@@ -128,6 +128,16 @@ inline void fill_lattice(const Grid& grid, const Tri* tris, const vec3& origin, 
     detail::check(detail::current_ctx(), hagrid_fill_lattice(detail::current_ctx(), &p, tris, o, s, m, axes, inside, workspace, records, counters,
                                                              winding ? HAGRID_INSIDE_WINDING : 0u));
 }
+/// Extension: the distance lattice by scatter (hagrid_amd.h: hagrid_distance_lattice; the key, the voxel box and its margin, tasks: distance.h): for every voxel
+/// centre the answer of closest_points with r = band.  workspace: 8 bytes per voxel; ids (int32), d2 (float32), records (32 bytes, those of closest_points): one
+/// per voxel, each may be nullptr but not all; counters: nullptr or int64[4] -- DEVICE pointers.
+inline void distance_lattice(const Grid& grid, const Tri* tris, const vec3& origin, const vec3& size, const ivec3& n, float band, void* workspace, int* ids, float* d2,
+                             void* records = nullptr, void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    const float o[3] = {origin.x, origin.y, origin.z}, s[3] = {size.x, size.y, size.z};
+    const int m[3] = {n.x, n.y, n.z};
+    detail::check(detail::current_ctx(), hagrid_distance_lattice(detail::current_ctx(), &p, tris, o, s, m, band, workspace, ids, d2, records, counters, 0u));
+}
 
 /// Extension: independent batches in flight.  Every MemManager is a context with a stream of its own (hagrid_ctx_set_stream on
 /// mem.context()); `share_traversal(dst, src)` lets `dst` traverse with the traversal image setup_traversal built in `src`, and the

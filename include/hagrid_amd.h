@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_list_crossings was ADDED, nothing else moved; 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_distance_lattice was ADDED, nothing else moved; 3 (still): hagrid_list_crossings was ADDED, nothing else moved; 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -437,6 +437,28 @@ int hagrid_inside_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* 
  * HAGRID_EINVAL: as for hagrid_inside_lattice, and an axes bit beyond 7, a missing workspace with more than one axis, a misaligned inside. */
 int hagrid_fill_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n,
                         uint32_t axes, void* inside, void* workspace, void* records, void* counters, uint32_t flags);
+
+/* Extension (no reference counterpart): the DISTANCE LATTICE by scatter -- the magnitude of a narrow-band distance field on a lattice, made by the triangles
+ * instead of by one walk per voxel (a signed field = this + hagrid_fill_lattice; Open3D's compute_distance on a voxel grid, the narrow band of a level set).
+ * origin, size, n: as for hagrid_inside_lattice, the same checks, the same voxel order (x fastest), the same centres.  band: finite, >= 0.  The answer of voxel
+ * e is EXACTLY the answer of hagrid_closest_points for the query (centre(e), r = band): among the triangles with a surface and d2 <= band * band the smallest
+ * in (d2, id); none: id -1, d2 = band * band, q = the centre.  Every triangle visits the voxels whose centres can lie within the band of its bounding box (the
+ * rule and why it is conservative in float32: include/hagrid/distance.h) in tasks of at most 2048 voxels and takes the minimum of the key
+ * (bits of d2) << 32 | id into the voxel's slot by a 64-bit atomic; a minimum does not depend on the order of arrival, so the result is deterministic.
+ *   grid       supplies the triangle count (the largest id it refers to), the scene box for the margin and the promise that the scene is admissible; its
+ *              cells are not walked.  A grid released by hagrid_grid_release_for_traversal is refused.
+ *   workspace  DEVICE, 8 bytes per voxel, 8-byte aligned, required.  The call initialises it; its content afterwards is unspecified.
+ *   ids, d2    DEVICE int32 / float32 per voxel, 4-byte aligned; either may be NULL.
+ *   records    NULL, or DEVICE 32 bytes per voxel, 16-byte aligned: the records of hagrid_closest_points, bit for bit (q, feature and side made again for the
+ *              winner by point_tri / tri_side).  At least one of ids, d2 and records must be given.
+ *   counters   NULL, or DEVICE int64[4], ADDED to: triangles whose voxel box is not empty, tasks, (triangle, voxel) pairs with d2 <= band * band, voxels
+ *              with an answer.  None depends on timing.
+ * On the context's stream.  With the traversal image of this grid in the context (hagrid_setup_traversal) there is no host round trip; without it one word (the
+ * largest id) is read back first.  One temporary of 4 bytes per triangle comes from the context's pool.
+ * HAGRID_EINVAL: the lattice errors of hagrid_inside_lattice; a null, released or incomplete grid; a band that is negative, NaN or infinite; a null or
+ * misaligned workspace; ids, d2 and records all NULL; misaligned buffers (triangles and records 16 bytes, ids and d2 4, counters 8); any flag. */
+int hagrid_distance_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n,
+                            float band, void* workspace, void* ids, void* d2, void* records, void* counters, uint32_t flags);
 
 /* Extension (no reference counterpart): spatial binning of the ray batch before traversal.  mode 0 (default): rays
  * are traversed in buffer order, as the reference does.  mode 1: each hagrid_traverse_grid call first bins the rays by
