@@ -99,6 +99,12 @@ class MemManager:
         else:
             _check(self, self._K.hagrid_kat_set_option(self._ctx, key.encode(), int(value)), f"kat_set_option({key})")
 
+    def scan_epoch(self) -> int:
+        """tests: the epoch of the look-back scans' status words (csrc/kat/hagrid_amd_kat.h: hagrid_kat_scan_epoch; "scan.epoch" sets it)"""
+        e = C.c_int32(-1)
+        _check(self, self._K.hagrid_kat_scan_epoch(self._ctx, C.byref(e)), "scan_epoch")
+        return int(e.value)
+
     def forget_hints(self):
         """dev tools: the context forgets every ray buffer it has traversed (csrc/kat/hagrid_amd_kat.h: hagrid_kat_forget_hints)"""
         _check(self, self._K.hagrid_kat_forget_hints(self._ctx), "forget_hints")

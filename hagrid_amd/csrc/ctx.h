@@ -108,6 +108,9 @@ struct hagrid_ctx {
     int opt_merge_narrow = 1;    // merge_grid: 16-byte working cell records between the passes (0: the 32-byte record throughout)
     int opt_expand_voxel_map = 1;     // expand_grid: the voxel map resolved into one word per voxel for the passes' look-ups (expand.hip); 0: the chain through the levels
     int opt_expand_subset_only = 1;   // expand_grid: 1 = the reference's compiled setting, 0 = precise (compute_overlap)
+    int opt_expand_listed = 1;        // expand_grid, tests: 0 = the optional list of cells is not taken, as if its allocation had failed (every iteration is an all-cells pass)
+    int opt_expand_max_listed = 48;   // expand_grid, tests: listed passes before the all-cells pass takes over again (0 .. 48: their counts live in dscratch[160 .. 208))
+    int opt_distance_by_triangle = 0; // distance_lattice, tests: 1 = the splat takes triangles, as when the sum of the task counts leaves 31 bits
     int opt_image_width = 0;    // tile packets: -1 off, 0 detect the row length on the device, > 0 row length given by the caller
     int opt_band_rows = 0;      // tile packets: rows of super-tiles per band; 0 = as many as make the in-flight tiles a square block of the image
     int opt_super_log2 = 3;     // tile packets: 2^k x 2^k tiles per super-tile (Z order inside); round-3 sweep: 3 (profiles/dev_r3_tile_params.txt)

@@ -164,6 +164,7 @@ extern "C" int hagrid_distance_lattice(hagrid_ctx* ctx, const hagrid_grid* grid,
         a.mode = kSize;
         distance_kernel<<<std::min(grid_blocks(a.num_tris, 64), waves), 64, 0, st>>>(a); HG_DBG(ctx);
         HG_TRY(scan_plain(ctx, a.sizes, a.sizes, a.num_tris, dsc + 0, dsc + 1));
+        if (ctx->opt_distance_by_triangle) HG_HIP(ctx, hipMemsetAsync(dsc + 1, 0x01, sizeof(int), st));      // (tests: the word a sum beyond 31 bits leaves)
         a.mode = kSplat;
         distance_kernel<<<waves, 64, 0, st>>>(a); HG_DBG(ctx);
     }

@@ -305,14 +305,14 @@ extern "C" int hagrid_expand_grid(hagrid_ctx* ctx, hagrid_grid* grid, const void
     const Entry* entries = static_cast<const Entry*>(grid->entries);
     const int* refs = static_cast<const int*>(grid->ref_ids);
     const int blocks = grid_blocks(n, kBlock);
-    int* list = iters > 1 ? pool_try_alloc<int>(ctx, size_t(n)) : nullptr;      // (without it the later iterations fall back to the all-cells pass)
+    int* list = iters > 1 && ctx->opt_expand_listed ? pool_try_alloc<int>(ctx, size_t(n)) : nullptr;      // (without it the later iterations fall back to the all-cells pass)
     const long long voxels = (long long)k.dims.x * k.dims.y * k.dims.z;
     int* voxel_cells = (ctx->opt_expand_voxel_map && voxels <= (1ll << 28)) ? pool_try_alloc<int>(ctx, size_t(voxels)) : nullptr;   // (without it: the chain through the voxel map)
     k.voxel_cells = voxel_cells;
     if (voxel_cells) { ExpandK kf = k; kf.voxel_cells = nullptr; fill_voxel_cells<<<grid_blocks(voxels, kBlock), kBlock, 0, st>>>(kf, entries, voxel_cells, int(voxels)); HG_DBG(ctx); }
     int* counts = ctx->dscratch + 160;             // one list length per listed pass
-    const int max_listed = 48;
-    if (list) (void)hipMemsetAsync(counts, 0, max_listed * sizeof(int), st);
+    const int max_listed = std::min(std::max(ctx->opt_expand_max_listed, 0), 48);     // (48 unless a test lowers it: the switch back in mid-growth)
+    if (list) (void)hipMemsetAsync(counts, 0, 48 * sizeof(int), st);
     int listed = 0;
     for (int it = 0; it < iters; it++) {                                               // expansion_iter, expand.cu:184-197
         if (it > 0 && list && listed + 3 <= max_listed) {

@@ -80,8 +80,20 @@ int hagrid_kat_image_records(hagrid_ctx* ctx, const hagrid_grid* grid, const int
  *                        where look-ups that left their block start again), 0 = look-ups start at the map's top level
  *   "traverse.quad_head" 20 (default): in a learned tile order of a launch of one to five rounds the tiles that cost at least 2.0 times the median working tile -- if they
  *                        are more than a twelfth of the tiles -- start with four lanes per ray and are dispatched first; tenths of the median; 0 = never
- *   "ctx.fast_readback"  1 (default) = scalar read-backs through a publishing wavefront and a spinning host, 0 = hipMemcpyAsync + hipStreamSynchronize */
+ *   "ctx.fast_readback"  1 (default) = scalar read-backs through a publishing wavefront and a spinning host, 0 = hipMemcpyAsync + hipStreamSynchronize
+ * Selectors for branches that no input of a test's size reaches (tests/test_fallbacks_gpu.py); host side only, the defaults are the product's behaviour:
+ *   "distance.by_triangle" 0 (default); 1 = hagrid_distance_lattice sets the word "the sum of the task counts left 31 bits" behind its scan, so the splat takes
+ *                        triangles (each with all its runs of voxels) instead of tasks: what 2^30 tasks and more would do
+ *   "expand.listed"      1 (default); 0 = hagrid_expand_grid does not take its optional list of cells, as if the allocation had failed: every iteration is an
+ *                        all-cells pass
+ *   "expand.max_listed"  48 (default), 0 .. 48: the listed passes (three per iteration from the second iteration on) an expansion runs before it goes back to
+ *                        all-cells passes -- by default in iteration 18, where nothing grows any more; a small value puts the switch where cells still grow.
+ *                        Never above 48: the lists' lengths live in 48 words of the context's scratch
+ *   "scan.epoch"         the epoch of the look-back scans' status words (0 .. 2^30; they restart at 2^30 - 2).  Only forwards: a value below the current epoch
+ *                        is HAGRID_EINVAL, since words of a later epoch would look published again.  hagrid_kat_scan_epoch reads it back */
 int hagrid_kat_set_option(hagrid_ctx* ctx, const char* key, int value);
+/* The epoch the context's last look-back scan ran under (0: none since the status words were made or restarted). */
+int hagrid_kat_scan_epoch(hagrid_ctx* ctx, int32_t* epoch);
 
 /* What the context remembers about the ray buffer `rays` (traverse.hip, RayHints): out12 = { slot or -1, order valid, no order for a while (rays that keep changing), positions the order is rotated by (the
  * four-lanes-per-ray head), head share dropped by its trial, timed samples without / with the head, the share trial's choice (-1 measuring, 0 rule, 1 half), its samples (rule + 100 x half), cooldown, epoch, launches since the choice };

@@ -350,7 +350,15 @@ extern "C" int hagrid_kat_set_option(hagrid_ctx* ctx, const char* key, int value
         {"traverse.order_gate", &ctx->opt_order_gate, 0, 1}, {"traverse.share_trial", &ctx->opt_share_trial, 0, 1}, {"traverse.band_rows", &ctx->opt_band_rows, 0, 1 << 16}, {"traverse.mailbox", &ctx->opt_mailbox, -1, 1},
         {"merge.inplace", &ctx->opt_merge_inplace, 0, 1},           {"merge.inplace_iters", &ctx->opt_merge_inplace_iters, 0, 1 << 20}, {"merge.inplace_room", &ctx->opt_merge_inplace_room, 0, 0x7fffffff}, {"merge.inplace_div", &ctx->opt_merge_inplace_div, 0, 1 << 20},
         {"expand.voxel_map", &ctx->opt_expand_voxel_map, 0, 1},
+        {"expand.listed", &ctx->opt_expand_listed, 0, 1},          {"expand.max_listed", &ctx->opt_expand_max_listed, 0, 48},
+        {"distance.by_triangle", &ctx->opt_distance_by_triangle, 0, 1},
     };
+    if (!strcmp(key, "scan.epoch")) {
+        // only forwards: status words of an epoch that comes again would read as published
+        if (value < 0 || value > (1 << 30) || unsigned(value) < ctx->lb_epoch) HG_FAIL(ctx, HAGRID_EINVAL, "kat_set_option: scan.epoch is 0 .. 2^30 and never goes back");
+        ctx->lb_epoch = unsigned(value);
+        return HAGRID_OK;
+    }
     for (auto& t : table)
         if (!strcmp(key, t.name)) {
             if (value < t.lo || value > t.hi || (t.dst == &ctx->opt_variant && value == 3)) HG_FAIL(ctx, HAGRID_EINVAL, "kat_set_option: value out of range");
@@ -358,6 +366,12 @@ extern "C" int hagrid_kat_set_option(hagrid_ctx* ctx, const char* key, int value
             return HAGRID_OK;
         }
     return hagrid_set_option(ctx, key, value);              // the product's own options
+}
+
+extern "C" int hagrid_kat_scan_epoch(hagrid_ctx* ctx, int32_t* epoch) {
+    if (!ctx || !epoch) return HAGRID_EINVAL;
+    *epoch = int32_t(ctx->lb_epoch);
+    return HAGRID_OK;
 }
 
 extern "C" int hagrid_kat_order_state(hagrid_ctx* ctx, const void* rays, int32_t* out12, float* ms2 /* 4 floats */) {
