@@ -28,7 +28,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import Camera, GridPOD, HagridError, TraversalStats
-from .scene import BOX_QUERY_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, POINT_QUERY_DTYPE, SMALL_CELL_DTYPE
+from .scene import BOX_QUERY_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, NEAREST_ENTRY_DTYPE, POINT_QUERY_DTYPE, SMALL_CELL_DTYPE
 
 _current = None  # the most recently created MemManager (profile / setup_traversal take no manager)
 
@@ -400,6 +400,81 @@ def closest_points(grid: Grid, tris: int, points: int, results: int, n: int, cou
     mem = grid.mem or _current
     _check(mem, mem._L.hagrid_closest_points(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(points or 0), C.c_void_p(results or 0), int(n),
                                              C.c_void_p(counters or 0), 0), "closest_points")
+
+
+MAX_NEAREST = 8          # HAGRID_MAX_NEAREST
+
+
+def nearest_tris(grid: Grid, tris: int, points: int, n: int, k: int, entries: int = 0, records: int = 0, cursors: int = 0, query_labels: int = 0,
+                 tri_labels: int = 0, counters: int = 0):
+    """Extension (hagrid_nearest_tris): NEIGHBOUR queries -- for each of n points (POINT_QUERY_DTYPE: x, y, z, r) the k nearest triangles within r, nearest
+    first: entries[i * k .. i * k + k - 1] (NEAREST_ENTRY_DTYPE: d2, id; unused slots d2 = r * r, id -1) and / or records (k CLOSEST_DTYPE records per
+    query); one of the two may be 0.  1 <= k <= MAX_NEAREST.  cursors: 0, or one entry per query -- only what sorts after it in (d2, id) is listed; the
+    cursor of the next page is the last slot of a FULL list, a list that is not full is the last page.  query_labels (int32[n]) and tri_labels (int32[3 per
+    scene triangle]): both or neither; a triangle that carries the query's label (>= 0) is left out (MeshScene.vertex_labels with label = vertex index: a
+    vertex does not see its own triangles).  counters: 0, or a device int64[5] the batch totals are added to (queries, cells visited, triangles tested,
+    sub-blocks pruned, lists that came back full).  All arguments are device addresses (a torch tensor passes as t.data_ptr()); asynchronous on the
+    manager's stream.  scene.nearest_tris states the results in numpy, bit for bit.  Walks the construction format: not for a grid given up with
+    release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_nearest_tris(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(points or 0), int(n), int(k), C.c_void_p(cursors or 0),
+                                           C.c_void_p(query_labels or 0), C.c_void_p(tri_labels or 0), C.c_void_p(entries or 0), C.c_void_p(records or 0),
+                                           C.c_void_p(counters or 0), 0), "nearest_tris")
+
+
+def tris_within(grid: Grid, tris, points, k: int = MAX_NEAREST, query_labels=None, tri_labels=None, max_pages=None) -> dict:
+    """ALL the triangles within r of every point, nearest first, in CSR form: nearest_tris paged on torch tensors.  Page by page the queries whose last list
+    came back full are asked again behind their last entry; ONE scalar per page goes to the host (the fifth counter: how many lists were full).  tris,
+    points ((n, 4) float32: x, y, z, r), query_labels ((n,) int32) and tri_labels ((N, 3) int32): torch tensors on the device (tris and tri_labels may be
+    device addresses).  The manager must run on torch's current stream (mem.use_stream(torch.cuda.current_stream().cuda_stream)).  Returns "offsets" int64
+    (n + 1,), "ids" int32 and "d2" float32 (total,): the triangles of point i are offsets[i] .. offsets[i + 1], sorted by (d2, id) -- what scene.tris_within
+    states -- and "pages", how many launches it took, and "complete": False only when max_pages (None: no bound) ended the paging before every list had
+    ended; the lists are then prefixes.  Meant for radii that hold tens of triangles: every page walks the ball of the pages before it again, so a list of L
+    triangles costs L / k launches over O(L) triangles each, and r = inf lists the whole scene for every point, k at a time."""
+    import torch
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    k = int(k)
+    pts = points.reshape(-1, 4)
+    n = int(pts.shape[0])
+    dev = pts.device
+    active = torch.arange(n, dtype=torch.int64, device=dev)                 # the queries of this page
+    cur_pts, cur_lab, cursors = pts, query_labels, None
+    page_q, page_e = [], []
+    counters = torch.zeros(5, dtype=torch.int64, device=dev)
+    pages, complete = 0, True
+    while active.numel():
+        if max_pages is not None and pages >= int(max_pages):
+            complete = False
+            break
+        pages += 1
+        m = int(active.numel())
+        entries = torch.empty((m, k, 2), dtype=torch.int32, device=dev)
+        counters.zero_()
+        nearest_tris(grid, ptr(tris), cur_pts.data_ptr(), m, k, entries=entries.data_ptr(), cursors=ptr(cursors),
+                     query_labels=ptr(cur_lab) if query_labels is not None else 0, tri_labels=ptr(tri_labels) if query_labels is not None else 0,
+                     counters=counters.data_ptr())
+        page_q.append(active); page_e.append(entries)
+        if int(counters[4].item()) == 0:
+            break
+        full = entries[:, k - 1, 1] >= 0
+        active = active[full]
+        cur_pts = cur_pts[full].contiguous()
+        cursors = entries[full][:, k - 1, :].contiguous()
+        if query_labels is not None:
+            cur_lab = cur_lab[full].contiguous()
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if not page_q:
+        return {"offsets": offsets, "ids": torch.zeros(0, dtype=torch.int32, device=dev), "d2": torch.zeros(0, dtype=torch.float32, device=dev), "pages": 0,
+                "complete": complete}
+    # the entries of all pages, by query and -- pages being in list order -- by page inside a query: a stable sort by query
+    q = torch.cat([a[:, None].expand(-1, k).reshape(-1) for a in page_q])
+    e = torch.cat([x.reshape(-1, 2) for x in page_e])
+    used = e[:, 1] >= 0
+    q, e = q[used], e[used]
+    order = torch.sort(q, stable=True)[1]
+    e = e[order]
+    torch.cumsum(torch.bincount(q, minlength=n), 0, out=offsets[1:])
+    return {"offsets": offsets, "ids": e[:, 1].contiguous(), "d2": e[:, 0].contiguous().view(torch.float32), "pages": pages, "complete": complete}
 
 
 MAX_OVERLAP_IDS = 8      # HAGRID_MAX_OVERLAP_IDS
@@ -841,6 +916,6 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "traverse_grid_filtered", "skip_filters", "RAY_MASK_ALL",
-           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
            "overlap_tris", "self_intersections",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

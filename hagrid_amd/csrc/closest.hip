@@ -9,6 +9,11 @@
 // its own column, so there is nothing to synchronise, 64 lanes at one level read 64 consecutive words (no bank conflict), and no register
 // array is indexed at run time (no scratch).  8 KB of LDS per wavefront: 20 wavefronts per CU by LDS, which the registers allow as well
 // (DESIGN.md 4.6).  Queries are processed in buffer order: no binning, no traversal image, no hints -- each answer depends on its query alone.
+//
+// nearest_tris_kernel (hagrid_nearest_tris) is the same walk with the header's NearList as its accumulator: the k <= 8 nearest candidates of
+// every point, sorted, after a cursor, with label pairs skipped.  The list (8 ids, 8 distances) lives in registers; the 32-byte records are made again from
+// the winners' ids AFTER the walk, so q, feature and side cost no register at the walk's peak.  A kernel of its own: as a mode of closest_points_kernel the
+// list would take every nearest-surface launch from 5 wavefronts per SIMD to 4.
 #include "trav_common.h"
 #include "wave_prims.h"
 
@@ -41,6 +46,54 @@ __global__ void __launch_bounds__(64) closest_points_kernel(const DevGrid g, con
     if (counters) add_batch_counters(counters, lane, live ? 1 : 0, cnt.cells, cnt.tris, cnt.pruned);
 }
 
+struct NearestArgs {
+    const float4* __restrict__ points;
+    const float2* __restrict__ cursors;
+    const int* __restrict__ query_labels;
+    const int* __restrict__ tri_labels;
+    float2* __restrict__ entries;
+    float4* __restrict__ records;
+    unsigned long long* __restrict__ counters;
+    int n, k;
+};
+
+__global__ void __launch_bounds__(64) nearest_tris_kernel(const DevGrid g, const NearestArgs a) {
+    __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
+    const int lane = threadIdx.x;
+    const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
+    const bool live = id < a.n;
+    hc::Counts cnt;
+    cnt.cells = 0; cnt.tris = 0; cnt.pruned = 0;
+    int full = 0;
+    if (live) {
+        const float4 pr = nt_load4(a.points + id);
+        const vec3 p(pr.x, pr.y, pr.z);
+        LdsStack st;
+        st.w_ = &s_w[0][lane]; st.i_ = &s_i[0][lane];
+        hc::NearList<HAGRID_MAX_NEAREST> list;
+        float cur_d2 = -1.0f;
+        int cur_id = -1;
+        if (a.cursors) { const float2 c = a.cursors[id]; cur_d2 = c.x; cur_id = __float_as_int(c.y); }
+        list.setup(a.k, cur_d2, cur_id, a.query_labels ? a.query_labels[id] : -1, a.tri_labels);
+        hc::closest_query(g, st, p, pr.w, list, cnt);
+        full = list.full() ? 1 : 0;
+        const size_t base = size_t(id) * size_t(a.k);
+#pragma nounroll
+        for (int j = 0; j < a.k; j++) {
+            int sid; float sd2;
+            list.get(j, sid, sd2);
+            if (a.entries) nt_store2(a.entries + base + j, sd2, __int_as_float(sid));
+            if (a.records) {
+                hc::Best b;
+                hc::slot_record([&g](int t) { return g.tri(t); }, sid, sd2, p, b);
+                nt_store4(a.records + 2 * (base + j), b.q.x, b.q.y, b.q.z, b.d2);
+                nt_store4(a.records + 2 * (base + j) + 1, __int_as_float(b.id), __int_as_float(b.feature), float(b.side), 0.0f);
+            }
+        }
+    }
+    if (a.counters) add_batch_counters(a.counters, lane, live ? 1 : 0, cnt.cells, cnt.tris, cnt.pruned, full);
+}
+
 } // namespace
 
 extern "C" int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, void* results, int num_points,
@@ -61,6 +114,39 @@ extern "C" int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, c
     g.set(grid, tris);
     closest_points_kernel<<<grid_blocks(num_points, 64), 64, 0, ctx->stream>>>(g, static_cast<const float4*>(points), static_cast<float4*>(results), num_points,
                                                                                 static_cast<unsigned long long*>(counters));
+    HG_DBG(ctx);
+    HG_HIP(ctx, hipGetLastError());
+    return HAGRID_OK;
+}
+
+extern "C" int hagrid_nearest_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points, int k, const void* cursors,
+                                   const void* query_labels, const void* tri_labels, void* entries, void* records, void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (flags) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: unknown flag (flags must be 0)");
+    if (num_points < 0) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: negative num_points");
+    if (k < 1 || k > HAGRID_MAX_NEAREST) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: k must be 1 .. HAGRID_MAX_NEAREST");
+    if (!grid) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: null grid");
+    if (!grid->entries || (!grid->cells && !grid->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: the walk reads the construction format (grid released for traversal, or incomplete)");
+    if (!grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: incomplete grid");
+    if (grid->shift < 0 || grid->shift > 15 || grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: bad shift or dims");
+    if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: the counters must be 8-byte aligned");
+    if ((query_labels != nullptr) != (tri_labels != nullptr)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: query_labels and tri_labels are given together or not at all");
+    if (int64_t(num_points) * int64_t(k) > int64_t(INT32_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "nearest_tris: num_points * k beyond 2^31 - 1");
+    if (num_points == 0) return HAGRID_OK;
+    if (!tris || !points) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: null triangle or point buffer");
+    if (!entries && !records) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: entries and records are both null");
+    if (!aligned(tris, 16) || !aligned(points, 16) || !aligned(records, 16)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: triangles, points and records must be 16-byte aligned");
+    if (!aligned(entries, 8) || !aligned(cursors, 8)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: entries and cursors must be 8-byte aligned");
+    if (!aligned(query_labels, 4) || !aligned(tri_labels, 4)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: the labels must be 4-byte aligned");
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+    DevGrid g;
+    g.set(grid, tris);
+    NearestArgs a;
+    a.points = static_cast<const float4*>(points); a.cursors = static_cast<const float2*>(cursors);
+    a.query_labels = static_cast<const int*>(query_labels); a.tri_labels = static_cast<const int*>(tri_labels);
+    a.entries = static_cast<float2*>(entries); a.records = static_cast<float4*>(records); a.counters = static_cast<unsigned long long*>(counters);
+    a.n = num_points; a.k = k;
+    nearest_tris_kernel<<<grid_blocks(num_points, 64), 64, 0, ctx->stream>>>(g, a);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

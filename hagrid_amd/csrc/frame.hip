@@ -1,6 +1,6 @@
 // frame.hip -- a frame on the device: primary rays, bounce rays, shading, ambient occlusion (include/hagrid_amd.h "frames on the device").
 //
-// Three streaming kernels (the two ray generators are one, with a mode argument; so are the two ambient-occlusion steps, and the picture of hits and the layered picture of multi-hit lists), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
+// Two streaming kernels (the two ray generators are one, with a mode argument; so are the picture of hits, the layered picture of multi-hit lists and the two ambient-occlusion steps), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
 // host program calls); the kernels only move the records: a Ray is two float4 and a Hit one, loaded and stored as such (16-byte accesses,
 // what the traversal kernels read: rays[2 * i], rays[2 * i + 1]), a pixel is one 32-bit word.  Mode, miss rule and flags are kernel
 // arguments, not template parameters: one kernel each.  hagrid_render_frame strings them together with hagrid_traverse_grid_ex on the
@@ -57,28 +57,24 @@ __global__ void __launch_bounds__(kBlock) frame_rays_kernel(const RayGenArgs a) 
     store_ray(a.out, i, r);
 }
 
-// The two shading entry points share one kernel (the product library's kernel budget): `k` is launch-uniform.
-// k == 0: the pixel of hit i (hagrid_shade_hits); k > 0: the layered picture of the k Hit records of pixel i, read where they lie (the list of
-// pixel i starts at hits[i * k]: hagrid_shade_layers; mode is not used).
-__global__ void __launch_bounds__(kBlock) frame_shade_hits_kernel(const float4* __restrict__ hits, int n, int mode, float clip, int k, float opacity, uint32_t* __restrict__ bgra) {
+// The two shading entry points and the two ambient-occlusion steps share one kernel (the product library's kernel budget): `k` and
+// `samples` are launch-uniform.  k == 0: the pixel of hit i (hagrid_shade_hits); k > 0: the layered picture of the k Hit records of pixel i, read where
+// they lie (the list of pixel i starts at hits[i * k]: hagrid_shade_layers; mode is not used).  k < 0: ambient occlusion -- samples == 0:
+// counts[i] += hits[i].id >= 0 (`hits` are occlusion hits, bgra is not touched); samples > 0: the pixel of primary hit i and counts[i].
+__global__ void __launch_bounds__(kBlock) frame_shade_hits_kernel(const float4* __restrict__ hits, int n, int mode, float clip, int k, float opacity, int* __restrict__ counts, int samples,
+                                                                  uint32_t* __restrict__ bgra) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     if (k == 0) {
         const float4 hv = hits[i];
         bgra[i] = hf::shade_hit(Hit(__float_as_int(hv.x), hv.y, hv.z, hv.w), mode, clip);
-    } else {
+    } else if (k > 0) {
         bgra[i] = hf::shade_layers(reinterpret_cast<const Hit*>(hits) + size_t(i) * size_t(k), k, clip, opacity);
+    } else {
+        const int id = __float_as_int(hits[i].x);
+        if (samples == 0) counts[i] += id >= 0 ? 1 : 0;
+        else bgra[i] = hf::shade_occlusion(id, counts[i], samples);
     }
-}
-
-// The two ambient-occlusion steps share one kernel (the product library's kernel budget): `samples` is launch-uniform.
-// samples == 0: counts[i] += hits[i].id >= 0 (`hits` are occlusion hits, bgra is not touched); samples > 0: the pixel of primary hit i and counts[i].
-__global__ void __launch_bounds__(kBlock) frame_occlusion_kernel(const float4* __restrict__ hits, int* __restrict__ counts, int n, int samples, uint32_t* __restrict__ bgra) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const int id = __float_as_int(hits[i].x);
-    if (samples == 0) counts[i] += id >= 0 ? 1 : 0;
-    else bgra[i] = hf::shade_occlusion(id, counts[i], samples);
 }
 
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
@@ -149,7 +145,7 @@ extern "C" int hagrid_shade_hits(hagrid_ctx* ctx, const void* hits, int num_hits
     if (mode == HAGRID_SHADE_DEPTH && !(clip > 0.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_hits: the depth picture needs clip > 0");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_hits) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_hits, mode, clip, 0, 0.0f, static_cast<uint32_t*>(bgra));
+    frame_shade_hits_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_hits, mode, clip, 0, 0.0f, nullptr, 0, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -165,7 +161,7 @@ extern "C" int hagrid_shade_layers(hagrid_ctx* ctx, const void* hits, int num_ra
     if (!(opacity > 0.0f && opacity <= 1.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: opacity must be in (0, 1]");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_rays, 0, clip, k, opacity, static_cast<uint32_t*>(bgra));
+    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_rays, 0, clip, k, opacity, nullptr, 0, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -178,7 +174,7 @@ extern "C" int hagrid_accumulate_occlusion(hagrid_ctx* ctx, const void* occlusio
     if (num_rays <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "accumulate_occlusion: num_rays must be positive");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, counts, size_t(num_rays) * 4);
-    frame_occlusion_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(occlusion_hits), static_cast<int*>(counts), num_rays, 0, nullptr);
+    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(occlusion_hits), num_rays, 0, 0.0f, -1, 0.0f, static_cast<int*>(counts), 0, nullptr);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -191,7 +187,7 @@ extern "C" int hagrid_shade_occlusion(hagrid_ctx* ctx, const void* hits, const v
     if (num_rays <= 0 || samples <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "shade_occlusion: num_rays and samples must be positive");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
-    frame_occlusion_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), static_cast<int*>(const_cast<void*>(counts)), num_rays, samples, static_cast<uint32_t*>(bgra));
+    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_rays, 0, 0.0f, -1, 0.0f, static_cast<int*>(const_cast<void*>(counts)), samples, static_cast<uint32_t*>(bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

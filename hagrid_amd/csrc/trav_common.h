@@ -182,6 +182,11 @@ __device__ __forceinline__ void nt_store4(float4* p, float x, float y, float z, 
     f32x4 v; v.x = x; v.y = y; v.z = z; v.w = w;
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
 }
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void nt_store2(float2* p, float x, float y) {
+    f32x2 v; v.x = x; v.y = y;
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x2*>(p));
+}
 
 // ---- tile packets ---------------------------------------------------------------------------------------------------
 // A batch of camera rays arrives in image order (gen_rays, main.cpp:55-66: ray y * w + x), so 64 consecutive rays are

@@ -94,6 +94,12 @@ __device__ __forceinline__ void add_batch_counters(unsigned long long* counters,
         atomicAdd(counters + 3, sd);
     }
 }
+/// ... and a fifth total (nearest_tris: lists that came back full)
+__device__ __forceinline__ void add_batch_counters(unsigned long long* counters, int lane, int a, int b, int c, int d, int e) {
+    add_batch_counters(counters, lane, a, b, c, d);
+    const unsigned long long se = wave_sum_u64((unsigned)e);
+    if (lane == 0) atomicAdd(counters + 4, se);
+}
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) { int o = __shfl_xor(v, d, 64); v = o > v ? o : v; }

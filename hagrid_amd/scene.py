@@ -20,6 +20,8 @@ SMALL_CELL_DTYPE = np.dtype([("min", "<u2", 3), ("max", "<u2", 3), ("begin", "<i
 # nearest-surface queries (hagrid_closest_points): 16 bytes in, 32 bytes out per query
 POINT_QUERY_DTYPE = np.dtype([("p", "<f4", 3), ("r", "<f4")])
 CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("d2", "<f4"), ("id", "<i4"), ("feature", "<i4"), ("side", "<f4"), ("zero", "<i4")])
+# neighbour queries (hagrid_nearest_tris): 8 bytes per slot of a list, and per cursor
+NEAREST_ENTRY_DTYPE = np.dtype([("d2", "<f4"), ("id", "<i4")])
 # box-overlap queries (hagrid_overlap_boxes): 32 bytes per box, the layout of BBox with `first` in the pad slot after min
 BOX_QUERY_DTYPE = np.dtype([("min", "<f4", 3), ("first", "<i4"), ("max", "<f4", 3), ("pad", "<i4")])
 OVERLAP_ANY = 1
@@ -673,6 +675,94 @@ def closest_points(tris: np.ndarray, points: np.ndarray, chunk_pairs: int = 1 <<
             res["d2"] = np.where(p[:, 3] < np.float32(0.0), np.float32(-1.0), res["d2"])
             out[o:o + m] = res
     return out
+
+
+def _sorted_candidates(T, cols, p, k, cursors, query_labels, tri_labels):
+    """the candidates of hagrid_nearest_tris for a chunk of points p (m, 4) as three flat arrays (query, triangle, d2), grouped by query and sorted by
+    (d2, id) inside a query; k: None = all of them, else at least the k smallest of every query"""
+    r2 = p[:, 3] * p[:, 3]
+    valid, d2 = _point_tri((p[:, 0:1], p[:, 1:2], p[:, 2:3]), cols, False)
+    mask = valid & (d2 <= r2[:, None]) & (p[:, 3:4] >= np.float32(0.0))
+    if cursors is not None:
+        cd, ci = cursors["d2"][:, None], cursors["id"][:, None]
+        mask &= (d2 > cd) | ((d2 == cd) & (np.arange(T.shape[0], dtype=np.int64)[None, :] > ci))
+    if query_labels is not None:
+        ql = query_labels[:, None]
+        mask &= ~((ql >= 0) & ((tri_labels[None, :, 0] == ql) | (tri_labels[None, :, 1] == ql) | (tri_labels[None, :, 2] == ql)))
+    if k is not None and T.shape[0] > k:
+        kth = np.partition(np.where(mask, d2, np.float32(np.inf)), k - 1, axis=1)[:, k - 1]
+        mask &= d2 <= kth[:, None]
+    rows, ids = np.nonzero(mask)                                 # by query, ids ascending inside a query
+    d = d2[rows, ids]
+    order = np.lexsort((d, rows))                                # stable: a tie in d2 keeps the ids ascending
+    return rows[order], ids[order], d[order]
+
+
+def _nearest_args(tris, points, cursors, query_labels, tri_labels):
+    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    P = np.ascontiguousarray(points).view(np.float32).reshape(-1, 4)
+    C_ = None if cursors is None else np.ascontiguousarray(cursors).view(NEAREST_ENTRY_DTYPE).reshape(-1)
+    ql = None if query_labels is None else np.asarray(query_labels, dtype=np.int32).reshape(-1)
+    tl = None if tri_labels is None else np.asarray(tri_labels, dtype=np.int32).reshape(-1, 3)
+    return T, P, C_, ql, tl
+
+
+def nearest_tris(tris: np.ndarray, points: np.ndarray, k: int, cursors=None, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 21):
+    """The definition of hagrid_nearest_tris by brute force: points (n, 4) float32 x, y, z, r (or POINT_QUERY_DTYPE).  Triangle j is a candidate of query i
+    when it has a surface (stored normal != 0), d2 <= r * r (a NaN d2 never is), the pair is not skipped by the labels (query_labels (n,) int32, tri_labels
+    (N, 3) int32, both or neither: skipped when query_labels[i] >= 0 equals one of tri_labels[j]) and (d2, j) sorts strictly after cursors[i]
+    (NEAREST_ENTRY_DTYPE (n,), or None) in the order (d2 ascending, id ascending).  Returns (entries (n, k) NEAREST_ENTRY_DTYPE, records (n, k)
+    CLOSEST_DTYPE): the k smallest candidates in that order; unused slots id -1, d2 = r * r, q = p; r < 0: an inactive query, every slot id -1 and
+    d2 = -1.  Every point against every triangle, a chunk of points at a time."""
+    T, P, C_, ql, tl = _nearest_args(tris, points, cursors, query_labels, tri_labels)
+    n, N = P.shape[0], T.shape[0]
+    k = int(k)
+    entries = np.zeros((n, k), dtype=NEAREST_ENTRY_DTYPE)
+    records = np.zeros((n, k), dtype=CLOSEST_DTYPE)
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        r2 = P[:, 3] * P[:, 3]
+        entries["d2"] = np.where(P[:, 3] < np.float32(0.0), np.float32(-1.0), r2)[:, None]
+        entries["id"] = -1
+        for o in range(0, n if N else 0, m):
+            s = slice(o, o + m)
+            rows, ids, d = _sorted_candidates(T, cols, P[s], k, None if C_ is None else C_[s], None if ql is None else ql[s], tl)
+            start = np.searchsorted(rows, rows)                  # the first position of each entry's query
+            rank = np.arange(rows.size) - start
+            keep = rank < k
+            entries["id"][o + rows[keep], rank[keep]] = ids[keep]
+            entries["d2"][o + rows[keep], rank[keep]] = d[keep]
+        records["q"] = P[:, None, 0:3]; records["d2"] = entries["d2"]; records["id"] = entries["id"]
+        qi, sj = np.nonzero(entries["id"] >= 0)
+        if qi.size:
+            Tw = T[entries["id"][qi, sj]]; p = P[qi]
+            _, d2w, q, f, side = _point_tri((p[:, 0], p[:, 1], p[:, 2]), [Tw[:, i] for i in range(12)], True)
+            assert (d2w.astype(np.float32).view(np.uint32) == entries["d2"][qi, sj].view(np.uint32)).all()
+            records["q"][qi, sj] = np.stack(q, axis=1); records["feature"][qi, sj] = f; records["side"][qi, sj] = side.astype(np.float32)
+    return entries, records
+
+
+def tris_within(tris: np.ndarray, points: np.ndarray, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 21) -> dict:
+    """ALL the candidates of nearest_tris (no cursor) of every point, sorted by (d2, id), in CSR form: "offsets" int64 (n + 1,), "ids" int32 and "d2"
+    float32 (total,) -- what the pages of hagrid_nearest_tris concatenate to (api.tris_within).  For queries with a finite radius: r = inf lists every
+    triangle of the scene."""
+    T, P, _, ql, tl = _nearest_args(tris, points, None, query_labels, tri_labels)
+    n, N = P.shape[0], T.shape[0]
+    counts = np.zeros(n, dtype=np.int64)
+    all_ids, all_d = [np.zeros(0, np.int32)], [np.zeros(0, np.float32)]
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        for o in range(0, n if N else 0, m):
+            s = slice(o, o + m)
+            rows, ids, d = _sorted_candidates(T, cols, P[s], None, None, None if ql is None else ql[s], tl)
+            np.add.at(counts, o + rows, 1)
+            all_ids.append(ids.astype(np.int32)); all_d.append(d.astype(np.float32))
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return {"offsets": offsets, "ids": np.concatenate(all_ids), "d2": np.concatenate(all_d)}
 
 
 # ---- box-overlap queries: the numpy statement of include/hagrid/overlap.h (same operations, same order, same truth values) ----------------

@@ -50,12 +50,28 @@
 //
 // A cell reached through several leaves may be tested again; offering a triangle twice changes nothing.  The cell of p and the cell
 // tested last are recognised and skipped.  Three counts per query: cells visited, triangles tested, sub-blocks / top-level cells pruned.
+//
+// ---- the k nearest (hagrid_amd.h: hagrid_nearest_tris) --------------------------------------------------------------------------
+// trivial_query, brute_force, test_cell, visit_top and closest_query are templates over the ACCUMULATOR: what is offered every triangle
+// (offer), what a query starts from (init) and what the pruning compares with (the field d2).  Best keeps one answer; NearList<KMAX> keeps
+// the k <= KMAX smallest CANDIDATES in the order (d2 ascending, id ascending).  Triangle j is a candidate of a query when point_tri gives it
+// a surface, its d2 is not NaN, d2 <= r2, the pair is not skipped by the labels (the query's label is >= 0 and equals one of the triangle's
+// three) and (d2, j) sorts strictly AFTER the query's cursor.  A cursor of d2 = -1 excludes nothing (every candidate has d2 >= 0), a cursor
+// with a NaN d2 excludes everything; the cursor for the next page is the last slot of a FULL list.  Unused slots: d2 = r2, id -1.
+// The list's pruning field d2 is r2 until the list is full, then the d2 of its last entry -- the k-th best so far.  THE MARGIN holds with one
+// more sentence: a sub-block whose shrunk lower bound is beyond that value holds nothing that enters the list, because whatever enters
+// sorts before the last entry and so has d2 <= its d2; a tie with the last entry is never pruned, because equality does not satisfy `>`.
+// A triangle arrives once per cell that references it: one already in the list is dropped; one that fell off the end never comes back,
+// because the last entry only decreases; one of an earlier page is kept out by the cursor order.  Hence: the list for k is a prefix of
+// the list for k + 1, pages concatenated are all candidates sorted, and with k = 1, no cursor and no labels the entry is (d2, id) of Best.
+// There is no count of the ball's content: with pruning at the k-th best the walk never sees the rest.  A full list means "ask again".
 #ifndef HAGRID_CLOSEST_H
 #define HAGRID_CLOSEST_H
 
 #include "block_walk.h"
 #include "cell_walk.h"
 #include "grid.h"
+#include "multi_hit.h"
 #include "prims.h"
 #include "vec.h"
 
@@ -117,17 +133,93 @@ struct Best {
     }
 };
 
-/// is the query answered without looking at a triangle?  (inactive, NaN)
-HOST DEVICE inline bool trivial_query(const vec3& p, float r, Best& b) {
+/// The k <= KMAX nearest candidates of one query, sorted by (d2, id), in the style of HitList (multi_hit.h): every loop runs over compile-time
+/// indices, the capacity only appears in comparisons with them, nothing is indexed at run time -- the arrays live in registers on the device.
+template <int KMAX>
+struct NearList {
+    int id[KMAX];
+    float dd[KMAX];             ///< the entries' d2; an unused slot holds r2
+    int cap;                    ///< k: slots in use, 1 .. KMAX
+    float d2;                   ///< what the walk prunes with: r2 until the list is full, then the d2 of slot cap - 1
+    int last_id;                ///< the id of slot cap - 1: the list is full when last_id >= 0
+    float cur_d2; int cur_id;   ///< the cursor: only what sorts strictly after it is a candidate
+    int label;                  ///< the query's label (< 0: skips nothing)
+    const int* tri_labels;      ///< three labels per triangle, or null
+
+    /// before init: k, the cursor ((-1, -1): none) and the labels (null: none)
+    HOST DEVICE void setup(int k, float cursor_d2, int cursor_id, int query_label, const int* labels) {
+        cap = k; cur_d2 = cursor_d2; cur_id = cursor_id; label = query_label; tri_labels = labels;
+    }
+    HOST DEVICE void init(const vec3&, float r2) {
+        d2 = r2; last_id = -1;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) { id[j] = -1; dd[j] = r2; }
+    }
+    HOST DEVICE bool full() const { return last_id >= 0; }
+    /// (da, ia) sorts before (db, ib)
+    HOST DEVICE static bool before(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
+
+    HOST DEVICE void offer(const Tri& tri, int ref, const vec3& p) {
+        if (tri_labels && label >= 0) {
+            const int* l = tri_labels + 3 * size_t(ref);
+            if (l[0] == label || l[1] == label || l[2] == label) return;
+        }
+        Pair r;
+        if (!point_tri(tri, p, r)) return;
+        const float c = r.d2;
+        if (!(c <= d2)) return;                                                 // NaN, or beyond r2 (d2 is never above r2)
+        if (!(c > cur_d2 || (c == cur_d2 && ref > cur_id))) return;             // not after the cursor (a NaN cursor: nothing is)
+        if (last_id >= 0 && !before(c, ref, d2, last_id)) return;               // cannot change a full list
+        bool dup = false;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) dup = dup || id[j] == ref;
+        if (dup) return;
+        // the new entry sinks to its sorted place, pushing the rest one slot down; what falls off slot cap - 1 is dropped
+        int ci = ref; float cd = c;
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++) {
+            const bool take = j < cap && (id[j] < 0 || before(cd, ci, dd[j], id[j]));
+            const int oi = id[j]; const float od = dd[j];
+            id[j] = take ? ci : oi; dd[j] = take ? cd : od;
+            ci = take ? oi : ci; cd = take ? od : cd;
+        }
+        HAGRID_UNROLL
+        for (int j = 0; j < KMAX; j++)
+            if (j == cap - 1) { last_id = id[j]; d2 = dd[j]; }                  // an unused slot: -1 and r2, as before
+    }
+
+    /// slot j (a run-time value) without indexing at run time
+    HOST DEVICE void get(int j, int& out_id, float& out_d2) const {
+        out_id = -1; out_d2 = 0.0f;
+        HAGRID_UNROLL
+        for (int i = 0; i < KMAX; i++)
+            if (i == j) { out_id = id[i]; out_d2 = dd[i]; }
+    }
+};
+
+/// the 32-byte answer for slot (id, d2) of a list: q, feature and side made again by point_tri / tri_side, after the walk; an unused slot: q = p
+template <typename F>
+HOST DEVICE inline void slot_record(F tri_at, int id, float d2, const vec3& p, Best& b) {
+    b.init(p, d2);
+    if (id < 0) return;
+    const Tri tri = tri_at(id);
+    Pair r;
+    point_tri(tri, p, r);
+    b.id = id; b.d2 = r.d2; b.q = r.q; b.feature = r.feature; b.side = tri_side(tri, p, r.q);
+}
+
+/// is the query answered without looking at a triangle?  (inactive, NaN)  A: Best or NearList
+template <typename A>
+HOST DEVICE inline bool trivial_query(const vec3& p, float r, A& b) {
     const float r2 = r * r;
+    if (r < 0.0f) { b.init(p, -1.0f); return true; }
     b.init(p, r2);
-    if (r < 0.0f) { b.d2 = -1.0f; return true; }
     return !(p.x == p.x) || !(p.y == p.y) || !(p.z == p.z) || !(r2 == r2);
 }
 
 /// the definition: every triangle, in order.  tri_at(j) -> Tri
-template <typename F>
-HOST DEVICE inline void brute_force(F tri_at, int num_tris, const vec3& p, float r, Best& b) {
+template <typename F, typename A>
+HOST DEVICE inline void brute_force(F tri_at, int num_tris, const vec3& p, float r, A& b) {
     if (trivial_query(p, r, b)) return;
     for (int j = 0; j < num_tris; j++) b.offer(tri_at(j), j, p);
 }
@@ -154,8 +246,8 @@ HOST DEVICE inline float box_lower2(const GridConsts& c, const vec3& p, int lx, 
 }
 
 /// the list of one cell.  G: c (GridConsts), word(i), cell(i) -> CellRec, ref(i), tri(id)
-template <typename G>
-HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, Best& b, Counts& n) {
+template <typename G, typename A>
+HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, A& b, Counts& n) {
     const CellRec c = g.cell(index);
     n.cells++;
     if (c.begin >= 0) {
@@ -170,8 +262,8 @@ HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, 
 }
 
 /// one top-level cell: descend its sub-blocks (block_walk.h) while their boxes are not beyond the best so far
-template <typename G, typename S>
-HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& p, int tx, int ty, int tz, uint32_t first_cell, uint32_t& last_cell, Best& b, Counts& n) {
+template <typename G, typename S, typename A>
+HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& p, int tx, int ty, int tz, uint32_t first_cell, uint32_t& last_cell, A& b, Counts& n) {
     const GridConsts& c = g.c;
     auto prune = [&](int x, int y, int z, int s) {
         const bool far = beyond(box_lower2(c, p, x, y, z, x + (1 << s), y + (1 << s), z + (1 << s)), b.d2);
@@ -188,9 +280,9 @@ HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& p, int tx, int 
     else blocks::descend_top(g, st, top_w, tx, ty, tz, prune, leaf);
 }
 
-/// the answer for (p, r) over the grid g: equal, bit for bit, to brute_force over all triangles
-template <typename G, typename S>
-HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r, Best& b, Counts& n) {
+/// the answer for (p, r) over the grid g: equal, bit for bit, to brute_force over all triangles with the same accumulator (Best, NearList)
+template <typename G, typename S, typename A>
+HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r, A& b, Counts& n) {
     const GridConsts& c = g.c;
     n.cells = 0; n.tris = 0; n.pruned = 0;
     if (trivial_query(p, r, b)) return;

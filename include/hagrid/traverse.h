@@ -61,6 +61,16 @@ inline void closest_points(const Grid& grid, const Tri* tris, const void* points
     detail::check(detail::current_ctx(), hagrid_closest_points(detail::current_ctx(), &p, tris, points, results, num_points, counters, 0u));
 }
 
+/// Extension: neighbour queries (hagrid_amd.h: hagrid_nearest_tris; the list and the walk: closest.h).  The k <= HAGRID_MAX_NEAREST nearest triangles within r
+/// of every point, nearest first: entries (num_points * k records of 8 bytes {float d2, int id}) and / or records (num_points * k records of closest_points);
+/// cursors: nullptr or one entry per point (only what sorts after it is listed), the labels: both or neither, counters: nullptr or int64[5] -- all DEVICE
+/// pointers.  Asynchronous on the context's stream.
+inline void nearest_tris(const Grid& grid, const Tri* tris, const void* points, int num_points, int k, void* entries, void* records = nullptr, const void* cursors = nullptr,
+                         const int* query_labels = nullptr, const int* tri_labels = nullptr, void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_nearest_tris(detail::current_ctx(), &p, tris, points, num_points, k, cursors, query_labels, tri_labels, entries, records, counters, 0u));
+}
+
 /// Extension: box-overlap queries (hagrid_amd.h: hagrid_overlap_boxes, hagrid_overlap_lattice; the test, the list and the walk: overlap.h).  boxes:
 /// num_boxes records of 32 bytes (BBox with `first` in the pad slot after min), ids: num_boxes * k int32, counts: nullptr or num_boxes int32, counters:
 /// nullptr or int64[4] -- all DEVICE pointers.  any: stop at the first triangle that meets the box (k must be 1).  Asynchronous on the context's stream.

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_distance_lattice was ADDED, nothing else moved; 3 (still): hagrid_list_crossings was ADDED, nothing else moved; 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
+#define HAGRID_ABI_VERSION 3   /* 3 (still): hagrid_nearest_tris was ADDED, nothing else moved; 3 (still): hagrid_distance_lattice was ADDED, nothing else moved; 3 (still): hagrid_list_crossings was ADDED, nothing else moved; 3 (still): hagrid_count_crossings, hagrid_points_inside and hagrid_inside_lattice were ADDED, nothing else moved; 3 (still): hagrid_mesh and the scene entry points (hagrid_scene_create ... hagrid_scene_bad_indices) were ADDED, nothing else moved; 3 (still): hagrid_traverse_grid_multi and hagrid_shade_layers were ADDED, nothing else moved; 3 (still): the frame entry points (hagrid_gen_primary_rays ... hagrid_render_frame) were ADDED, nothing else moved; 3: code-path selectors left hagrid_set_option (test library); 2: hagrid_traversal_stats grew by long_list_refs (64 bytes), hagrid_grid_broadcast checks the communicator */
 #define HAGRID_MAX_LEVELS 32
 
 enum {
@@ -319,6 +319,37 @@ int hagrid_traverse_grid_filtered(hagrid_ctx* ctx, const hagrid_grid* grid, cons
  * hagrid_grid_release_for_traversal.  num_points = 0 is HAGRID_OK (null buffers are then fine). */
 int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, void* results,
                           int num_points, void* counters, uint32_t flags);
+
+/* Extension (no reference counterpart): NEIGHBOUR queries -- for every point of a batch the k NEAREST triangles within its radius, nearest first, paged
+ * (a particle of radius r against a mesh needs every triangle within r; the vertex-face proximity pairs of a cloth step; blending and voting over several
+ * neighbours).  points are the records of hagrid_closest_points (x, y, z, r; r2 = r * r, +inf allowed); d2 is point_tri's, the same bits.  Triangle j is a
+ * CANDIDATE of query i when it has a surface (stored normal != 0), its d2 is not NaN, d2 <= r2, the pair is not skipped by the labels, and (d2, j) sorts
+ * strictly AFTER the query's cursor in the order (d2 ascending, id ascending).  With m candidates and 1 <= k <= HAGRID_MAX_NEAREST:
+ *   entries  DEVICE, 8 bytes per slot {float32 d2; int32 id}, 8-byte aligned (NULL if records is given): the slots [i*k, i*k + k) hold the min(k, m)
+ *            smallest candidates in that order; unused slots d2 = r2, id -1.  An INACTIVE query (r < 0): k slots d2 = -1, id -1.  A NaN coordinate or a
+ *            NaN radius: id -1, d2 = r2 everywhere.
+ *   records  NULL, or DEVICE k x 32 bytes per query, 16-byte aligned: slot (i, j) holds the 32-byte record of hagrid_closest_points for that triangle
+ *            (q, d2, id, feature, side); an unused slot q = p, the slot's d2, id -1, feature = side = 0.
+ *   cursors  NULL (no cursor for anyone), or DEVICE 8 bytes per query in the entry layout, 8-byte aligned.  A cursor with d2 = -1 excludes nothing (every
+ *            candidate has d2 >= 0); a cursor with a NaN d2 excludes everything.  The cursor for page n + 1 is the LAST slot of page n.  A list that is
+ *            not full is the last page: its empty entry (id -1, d2 = r2) is NOT to be used as a cursor -- it would exclude nothing it should.
+ *   query_labels DEVICE int32[num_points], tri_labels DEVICE int32[3 per scene triangle], both given or both NULL, 4-byte aligned: pair (i, j) is SKIPPED
+ *            when query_labels[i] >= 0 equals one of triangle j's three labels.  With a mesh's vertices as queries, label = vertex index and the mesh's
+ *            index triples as triangle labels a vertex does not see the triangles it belongs to (the convention of hagrid_overlap_tris).
+ * Promises: the list for k is a prefix of the list for k + 1; the pages concatenated are the full sorted list of all candidates; the answer is that of the
+ * brute force over all triangles (hagrid_amd/scene.py: nearest_tris), and that of the unlabelled query over the scene with the skipped triangles deleted,
+ * ids unchanged; with k = 1, no cursor and no labels, entries are (d2, id) of hagrid_closest_points and records its whole 32-byte output, bit for bit.
+ * There is NO exact count of the ball's content and no "k + 1 says more": the walk prunes at the k-th best and never sees the rest.  A full list means
+ * "ask again".  counters: NULL, or DEVICE int64[5] (8-byte aligned) to which the batch totals are ADDED: queries, cells visited, triangles tested,
+ * sub-blocks pruned, lists that came back full -- the last one tells a paging caller with one scalar whether another page is needed.
+ * Asynchronous on the context's stream; walks the CONSTRUCTION format (include/hagrid/closest.h); the traversal image, ray binning and the
+ * hints kept for the nearest-hit path are neither used nor touched.  HAGRID_EINVAL: everything hagrid_closest_points refuses (a released grid, a bad
+ * shift), k < 1 or k > HAGRID_MAX_NEAREST, any flag, entries and records both NULL, one label array without the other, a misaligned buffer.
+ * HAGRID_ERANGE: num_points * k beyond 2^31 - 1.  num_points = 0 is HAGRID_OK (null buffers are then fine). */
+#define HAGRID_MAX_NEAREST 8
+int hagrid_nearest_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points, int k,
+                        const void* cursors, const void* query_labels, const void* tri_labels, void* entries, void* records,
+                        void* counters, uint32_t flags);
 
 /* Extension (no reference counterpart): BOX-OVERLAP queries -- for every axis-aligned box of a batch, which triangles meet it (contact candidates,
  * culling, sparse-volume allocation, surface voxelization).  Triangle j MEETS the box [lo, hi] exactly when intersect_tri_box<true, true>(v0, e1, e2, n,
