@@ -28,7 +28,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import Camera, GridPOD, HagridError, TraversalStats
-from .scene import BOX_QUERY_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, NEAREST_ENTRY_DTYPE, POINT_QUERY_DTYPE, SMALL_CELL_DTYPE
+from .scene import BOX_QUERY_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, NEAREST_ENTRY_DTYPE, POINT_QUERY_DTYPE, SEGMENT_DTYPE, SEGMENT_RECORD_DTYPE, SMALL_CELL_DTYPE
 
 _current = None  # the most recently created MemManager (profile / setup_traversal take no manager)
 
@@ -422,19 +422,12 @@ def nearest_tris(grid: Grid, tris: int, points: int, n: int, k: int, entries: in
                                            C.c_void_p(counters or 0), 0), "nearest_tris")
 
 
-def tris_within(grid: Grid, tris, points, k: int = MAX_NEAREST, query_labels=None, tri_labels=None, max_pages=None) -> dict:
-    """ALL the triangles within r of every point, nearest first, in CSR form: nearest_tris paged on torch tensors.  Page by page the queries whose last list
-    came back full are asked again behind their last entry; ONE scalar per page goes to the host (the fifth counter: how many lists were full).  tris,
-    points ((n, 4) float32: x, y, z, r), query_labels ((n,) int32) and tri_labels ((N, 3) int32): torch tensors on the device (tris and tri_labels may be
-    device addresses).  The manager must run on torch's current stream (mem.use_stream(torch.cuda.current_stream().cuda_stream)).  Returns "offsets" int64
-    (n + 1,), "ids" int32 and "d2" float32 (total,): the triangles of point i are offsets[i] .. offsets[i + 1], sorted by (d2, id) -- what scene.tris_within
-    states -- and "pages", how many launches it took, and "complete": False only when max_pages (None: no bound) ended the paging before every list had
-    ended; the lists are then prefixes.  Meant for radii that hold tens of triangles: every page walks the ball of the pages before it again, so a list of L
-    triangles costs L / k launches over O(L) triangles each, and r = inf lists the whole scene for every point, k at a time."""
+def _paged_csr(launch, width: int, grid: Grid, tris, queries, k: int, query_labels, tri_labels, max_pages) -> dict:
+    """tris_within and tris_near_segments: launch (nearest_tris or segment_tris) paged on torch tensors into CSR; width: float32 words per query"""
     import torch
     ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
     k = int(k)
-    pts = points.reshape(-1, 4)
+    pts = queries.reshape(-1, width)
     n = int(pts.shape[0])
     dev = pts.device
     active = torch.arange(n, dtype=torch.int64, device=dev)                 # the queries of this page
@@ -450,9 +443,9 @@ def tris_within(grid: Grid, tris, points, k: int = MAX_NEAREST, query_labels=Non
         m = int(active.numel())
         entries = torch.empty((m, k, 2), dtype=torch.int32, device=dev)
         counters.zero_()
-        nearest_tris(grid, ptr(tris), cur_pts.data_ptr(), m, k, entries=entries.data_ptr(), cursors=ptr(cursors),
-                     query_labels=ptr(cur_lab) if query_labels is not None else 0, tri_labels=ptr(tri_labels) if query_labels is not None else 0,
-                     counters=counters.data_ptr())
+        launch(grid, ptr(tris), cur_pts.data_ptr(), m, k, entries=entries.data_ptr(), cursors=ptr(cursors),
+               query_labels=ptr(cur_lab) if query_labels is not None else 0, tri_labels=ptr(tri_labels) if query_labels is not None else 0,
+               counters=counters.data_ptr())
         page_q.append(active); page_e.append(entries)
         if int(counters[4].item()) == 0:
             break
@@ -475,6 +468,42 @@ def tris_within(grid: Grid, tris, points, k: int = MAX_NEAREST, query_labels=Non
     e = e[order]
     torch.cumsum(torch.bincount(q, minlength=n), 0, out=offsets[1:])
     return {"offsets": offsets, "ids": e[:, 1].contiguous(), "d2": e[:, 0].contiguous().view(torch.float32), "pages": pages, "complete": complete}
+
+
+def tris_within(grid: Grid, tris, points, k: int = MAX_NEAREST, query_labels=None, tri_labels=None, max_pages=None) -> dict:
+    """ALL the triangles within r of every point, nearest first, in CSR form: nearest_tris paged on torch tensors.  Page by page the queries whose last list
+    came back full are asked again behind their last entry; ONE scalar per page goes to the host (the fifth counter: how many lists were full).  tris,
+    points ((n, 4) float32: x, y, z, r), query_labels ((n,) int32) and tri_labels ((N, 3) int32): torch tensors on the device (tris and tri_labels may be
+    device addresses).  The manager must run on torch's current stream (mem.use_stream(torch.cuda.current_stream().cuda_stream)).  Returns "offsets" int64
+    (n + 1,), "ids" int32 and "d2" float32 (total,): the triangles of point i are offsets[i] .. offsets[i + 1], sorted by (d2, id) -- what scene.tris_within
+    states -- and "pages", how many launches it took, and "complete": False only when max_pages (None: no bound) ended the paging before every list had
+    ended; the lists are then prefixes.  Meant for radii that hold tens of triangles: every page walks the ball of the pages before it again, so a list of L
+    triangles costs L / k launches over O(L) triangles each, and r = inf lists the whole scene for every point, k at a time."""
+    return _paged_csr(nearest_tris, 4, grid, tris, points, k, query_labels, tri_labels, max_pages)
+
+
+def segment_tris(grid: Grid, tris: int, segments: int, n: int, k: int, entries: int = 0, records: int = 0, cursors: int = 0, query_labels: int = 0,
+                 tri_labels: int = 0, counters: int = 0):
+    """Extension (hagrid_segment_tris): CAPSULE queries -- for each of n segments (SEGMENT_DTYPE: a, r, b, 0) the k triangles nearest to the SEGMENT
+    within r, nearest first: entries[i * k .. i * k + k - 1] (NEAREST_ENTRY_DTYPE: d2, id; unused slots d2 = r * r, id -1) and / or records (k
+    SEGMENT_RECORD_DTYPE records per query: q on the triangle, d2, id, feature 0 .. 4, side, s on the segment); one of the two may be 0.
+    1 <= k <= MAX_NEAREST; cursors and paging as nearest_tris.  query_labels (int32[2 n]: an edge's two vertex indices, -1 unused) and tri_labels
+    (int32[3 per scene triangle]): both or neither; a triangle that carries one of the query's labels (>= 0) is left out (MeshScene.edge_labels: an
+    edge does not see the triangles that share a vertex with it).  counters: 0, or a device int64[5] as nearest_tris.  All arguments are device
+    addresses (a torch tensor passes as t.data_ptr()); asynchronous on the manager's stream.  scene.segment_tris states the results in numpy, bit for
+    bit.  Walks the construction format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_segment_tris(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(segments or 0), int(n), int(k), C.c_void_p(cursors or 0),
+                                           C.c_void_p(query_labels or 0), C.c_void_p(tri_labels or 0), C.c_void_p(entries or 0), C.c_void_p(records or 0),
+                                           C.c_void_p(counters or 0), 0), "segment_tris")
+
+
+def tris_near_segments(grid: Grid, tris, segments, k: int = MAX_NEAREST, query_labels=None, tri_labels=None, max_pages=None) -> dict:
+    """ALL the triangles within r of every segment, nearest first, in CSR form: segment_tris paged on torch tensors, the analogue of tris_within
+    (the same keys, the same cost model, the same use of the fifth counter).  segments ((n, 8) float32: ax, ay, az, r, bx, by, bz, 0), query_labels
+    ((n, 2) int32) and tri_labels ((N, 3) int32): torch tensors on the device (tris and tri_labels may be device addresses).  What scene.tris_near_segments
+    states.  For finite radii."""
+    return _paged_csr(segment_tris, 8, grid, tris, segments, k, query_labels, tri_labels, max_pages)
 
 
 MAX_OVERLAP_IDS = 8      # HAGRID_MAX_OVERLAP_IDS
@@ -830,6 +859,21 @@ class MeshScene:
                 offset += nv
         return out
 
+    def edge_labels(self):
+        """The unique edges of the assembled triangles for segment_tris: (pairs, labels), two torch tensors (m, 2) on the device.  labels (int32) are the
+        edges' two vertex labels in the label space of vertex_labels(), smaller first, every edge once, sorted -- the query_labels of the mesh's own edges
+        as segments; with vertex_labels() as tri_labels an edge does not see the triangles that share a vertex with it.  pairs (int64) are the same
+        numbers as indices: the vertices of the instances in instance order, to gather the segments' ends with.  Made on the device (sort and unique on
+        the manager's stream)."""
+        import torch
+        with torch.cuda.stream(self.mem.torch_stream()):
+            L = self.vertex_labels()
+            e = torch.cat([L[:, [0, 1]], L[:, [1, 2]], L[:, [2, 0]]])
+            e = torch.sort(e, dim=1)[0]
+            e = torch.unique(e[e[:, 0] != e[:, 1]], dim=0).contiguous()
+            pairs = e.to(torch.int64)
+        return pairs, e
+
     def instance_masks(self, masks):
         """The triangle masks of traverse_grid_filtered for the assembled triangles: masks holds one 32-bit mask per INSTANCE; returns a torch int32 tensor
         (num_tris,) on the device in which every triangle carries its instance's mask (the bits of the uint32).  Fills on the manager's stream."""
@@ -916,6 +960,6 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "traverse_grid_filtered", "skip_filters", "RAY_MASK_ALL",
-           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "segment_tris", "tris_near_segments", "SEGMENT_DTYPE", "SEGMENT_RECORD_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
            "overlap_tris", "self_intersections",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

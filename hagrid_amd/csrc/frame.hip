@@ -1,9 +1,9 @@
 // frame.hip -- a frame on the device: primary rays, bounce rays, shading, ambient occlusion (include/hagrid_amd.h "frames on the device").
 //
-// Two streaming kernels (the two ray generators are one, with a mode argument; so are the picture of hits, the layered picture of multi-hit lists and the two ambient-occlusion steps), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
+// ONE streaming kernel with launch-uniform modes (the two ray generators, the picture of hits, the layered picture of multi-hit lists and the two ambient-occlusion steps: the product library's kernel budget), one ray or pixel per lane, 256 lanes per block.  The arithmetic is include/hagrid/frame.h (the same functions a
 // host program calls); the kernels only move the records: a Ray is two float4 and a Hit one, loaded and stored as such (16-byte accesses,
 // what the traversal kernels read: rays[2 * i], rays[2 * i + 1]), a pixel is one 32-bit word.  Mode, miss rule and flags are kernel
-// arguments, not template parameters: one kernel each.  hagrid_render_frame strings them together with hagrid_traverse_grid_ex on the
+// arguments, not template parameters.  hagrid_render_frame strings them together with hagrid_traverse_grid_ex on the
 // context's stream; nothing here waits for the device or copies to the host.
 #include "ctx.h"
 
@@ -24,20 +24,39 @@ __device__ inline void store_ray(float4* __restrict__ rays, int i, const Ray& r)
     rays[2 * size_t(i) + 1] = make_float4(r.dir.x, r.dir.y, r.dir.z, r.tmax);
 }
 
-// The two ray generators share one kernel (the product library's kernel budget): `hits` is launch-uniform.  hits == nullptr: the primary ray
-// of pixel first + i (hagrid_gen_primary_rays; cam, clip, w, h); else the bounce ray of hit i (hagrid_gen_bounce_rays; tris: 12 floats per triangle, the
-// normal in words 3, 7, 11 -- the only gather of this file).  The arithmetic is hf::primary_ray / hf::bounce_ray either way: the rays are the bits they were.
-struct RayGenArgs {
-    hf::Camera cam; float clip; int w, h;                                   // primary
-    const float* __restrict__ tris; const float4* __restrict__ rays; const float4* __restrict__ hits;      // bounce
+// Everything this file launches is one kernel (the product library's kernel budget): `shade`, `hits`, `k` and `samples` are
+// launch-uniform, every branch on them is taken by whole launches.
+// shade == 0, the two ray generators: hits == nullptr: the primary ray of pixel first + i (hagrid_gen_primary_rays; cam, clip, w, h); else the bounce ray
+// of hit i (hagrid_gen_bounce_rays; tris: 12 floats per triangle, the normal in words 3, 7, 11 -- the only gather of this file).  The arithmetic is
+// hf::primary_ray / hf::bounce_ray either way: the rays are the bits they were.
+// shade != 0, the two shading entry points and the two ambient-occlusion steps: k == 0: the pixel of hit i (hagrid_shade_hits); k > 0: the layered picture
+// of the k Hit records of pixel i, read where they lie (the list of pixel i starts at hits[i * k]: hagrid_shade_layers; mode is not used).  k < 0: ambient
+// occlusion -- samples == 0: counts[i] += hits[i].id >= 0 (`hits` are occlusion hits, bgra is not touched); samples > 0: the pixel of primary hit i and counts[i].
+struct FrameArgs {
+    hf::Camera cam; float clip; int w, h;                                   // primary (clip: shading as well)
+    const float* __restrict__ tris; const float4* __restrict__ rays; const float4* __restrict__ hits;      // bounce (hits: shading as well)
     unsigned long long seed; vec3 lo, hi; float tmax; unsigned flags;
     unsigned long long first; int n;
     float4* __restrict__ out;
+    int shade, mode, k, samples; float opacity; int* __restrict__ counts; uint32_t* __restrict__ bgra;      // shading
 };
 
-__global__ void __launch_bounds__(kBlock) frame_rays_kernel(const RayGenArgs a) {
+__global__ void __launch_bounds__(kBlock) frame_kernel(const FrameArgs a) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
+    if (a.shade) {
+        if (a.k == 0) {
+            const float4 hv = a.hits[i];
+            a.bgra[i] = hf::shade_hit(Hit(__float_as_int(hv.x), hv.y, hv.z, hv.w), a.mode, a.clip);
+        } else if (a.k > 0) {
+            a.bgra[i] = hf::shade_layers(reinterpret_cast<const Hit*>(a.hits) + size_t(i) * size_t(a.k), a.k, a.clip, a.opacity);
+        } else {
+            const int id = __float_as_int(a.hits[i].x);
+            if (a.samples == 0) a.counts[i] += id >= 0 ? 1 : 0;
+            else a.bgra[i] = hf::shade_occlusion(id, a.counts[i], a.samples);
+        }
+        return;
+    }
     Ray r;
     if (!a.hits) {
         r = hf::primary_ray(a.cam, a.clip, a.w, a.h, (long long)a.first + i);
@@ -57,24 +76,12 @@ __global__ void __launch_bounds__(kBlock) frame_rays_kernel(const RayGenArgs a) 
     store_ray(a.out, i, r);
 }
 
-// The two shading entry points and the two ambient-occlusion steps share one kernel (the product library's kernel budget): `k` and
-// `samples` are launch-uniform.  k == 0: the pixel of hit i (hagrid_shade_hits); k > 0: the layered picture of the k Hit records of pixel i, read where
-// they lie (the list of pixel i starts at hits[i * k]: hagrid_shade_layers; mode is not used).  k < 0: ambient occlusion -- samples == 0:
-// counts[i] += hits[i].id >= 0 (`hits` are occlusion hits, bgra is not touched); samples > 0: the pixel of primary hit i and counts[i].
-__global__ void __launch_bounds__(kBlock) frame_shade_hits_kernel(const float4* __restrict__ hits, int n, int mode, float clip, int k, float opacity, int* __restrict__ counts, int samples,
-                                                                  uint32_t* __restrict__ bgra) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    if (k == 0) {
-        const float4 hv = hits[i];
-        bgra[i] = hf::shade_hit(Hit(__float_as_int(hv.x), hv.y, hv.z, hv.w), mode, clip);
-    } else if (k > 0) {
-        bgra[i] = hf::shade_layers(reinterpret_cast<const Hit*>(hits) + size_t(i) * size_t(k), k, clip, opacity);
-    } else {
-        const int id = __float_as_int(hits[i].x);
-        if (samples == 0) counts[i] += id >= 0 ? 1 : 0;
-        else bgra[i] = hf::shade_occlusion(id, counts[i], samples);
-    }
+/// a shading launch: the arguments frame_kernel's shade modes read
+inline FrameArgs shade_args(const void* hits, int n, int mode, float clip, int k, float opacity, void* counts, int samples, void* bgra) {
+    FrameArgs a = {};
+    a.shade = 1; a.hits = static_cast<const float4*>(hits); a.n = n; a.mode = mode; a.clip = clip; a.k = k; a.opacity = opacity;
+    a.counts = static_cast<int*>(counts); a.samples = samples; a.bgra = static_cast<uint32_t*>(bgra);
+    return a;
 }
 
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
@@ -106,10 +113,10 @@ extern "C" int hagrid_gen_primary_rays(hagrid_ctx* ctx, const hagrid_camera* cam
     if (first < 0 || first + int64_t(count) > int64_t(width) * int64_t(height)) HG_FAIL(ctx, HAGRID_EINVAL, "gen_primary_rays: the pixel range [first, first + count) leaves the image");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, rays, size_t(count) * 32);
-    RayGenArgs a = {};
+    FrameArgs a = {};
     memcpy(&a.cam, cam, sizeof(a.cam));
     a.clip = clip; a.w = width; a.h = height; a.first = (unsigned long long)first; a.n = count; a.out = static_cast<float4*>(rays);
-    frame_rays_kernel<<<grid_blocks(count, kBlock), kBlock, 0, ctx->stream>>>(a);
+    frame_kernel<<<grid_blocks(count, kBlock), kBlock, 0, ctx->stream>>>(a);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -126,11 +133,11 @@ extern "C" int hagrid_gen_bounce_rays(hagrid_ctx* ctx, const void* tris, const v
     if (flags & ~HAGRID_BOUNCE_REDRAW_MISSES) HG_FAIL(ctx, HAGRID_EINVAL, "gen_bounce_rays: unknown flag");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, out_rays, size_t(num_rays) * 32);
-    RayGenArgs a = {};
+    FrameArgs a = {};
     a.tris = static_cast<const float*>(tris); a.rays = static_cast<const float4*>(rays); a.hits = static_cast<const float4*>(hits);
     a.seed = seed; a.lo = vec3(bbox_min[0], bbox_min[1], bbox_min[2]); a.hi = vec3(bbox_max[0], bbox_max[1], bbox_max[2]); a.tmax = tmax; a.flags = flags;
     a.first = first; a.n = num_rays; a.out = static_cast<float4*>(out_rays);
-    frame_rays_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(a);
+    frame_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(a);
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -145,7 +152,7 @@ extern "C" int hagrid_shade_hits(hagrid_ctx* ctx, const void* hits, int num_hits
     if (mode == HAGRID_SHADE_DEPTH && !(clip > 0.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_hits: the depth picture needs clip > 0");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_hits) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_hits, mode, clip, 0, 0.0f, nullptr, 0, static_cast<uint32_t*>(bgra));
+    frame_kernel<<<grid_blocks(num_hits, kBlock), kBlock, 0, ctx->stream>>>(shade_args(hits, num_hits, mode, clip, 0, 0.0f, nullptr, 0, bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -161,7 +168,7 @@ extern "C" int hagrid_shade_layers(hagrid_ctx* ctx, const void* hits, int num_ra
     if (!(opacity > 0.0f && opacity <= 1.0f)) HG_FAIL(ctx, HAGRID_EINVAL, "shade_layers: opacity must be in (0, 1]");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_rays, 0, clip, k, opacity, nullptr, 0, static_cast<uint32_t*>(bgra));
+    frame_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(shade_args(hits, num_rays, 0, clip, k, opacity, nullptr, 0, bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -174,7 +181,7 @@ extern "C" int hagrid_accumulate_occlusion(hagrid_ctx* ctx, const void* occlusio
     if (num_rays <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "accumulate_occlusion: num_rays must be positive");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, counts, size_t(num_rays) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(occlusion_hits), num_rays, 0, 0.0f, -1, 0.0f, static_cast<int*>(counts), 0, nullptr);
+    frame_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(shade_args(occlusion_hits, num_rays, 0, 0.0f, -1, 0.0f, counts, 0, nullptr));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
@@ -187,7 +194,7 @@ extern "C" int hagrid_shade_occlusion(hagrid_ctx* ctx, const void* hits, const v
     if (num_rays <= 0 || samples <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "shade_occlusion: num_rays and samples must be positive");
     HG_HIP(ctx, hipSetDevice(ctx->device));
     trav_image_source_touched(ctx, bgra, size_t(num_rays) * 4);
-    frame_shade_hits_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const float4*>(hits), num_rays, 0, 0.0f, -1, 0.0f, static_cast<int*>(const_cast<void*>(counts)), samples, static_cast<uint32_t*>(bgra));
+    frame_kernel<<<grid_blocks(num_rays, kBlock), kBlock, 0, ctx->stream>>>(shade_args(hits, num_rays, 0, 0.0f, -1, 0.0f, const_cast<void*>(counts), samples, bgra));
     HG_DBG(ctx);
     HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;

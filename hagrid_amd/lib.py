@@ -139,6 +139,7 @@ SIGNATURES = {
     "hagrid_traverse_grid_filtered": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.c_uint32]),
     "hagrid_closest_points": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _vp, C.c_uint32]),
     "hagrid_nearest_tris": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "hagrid_segment_tris": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_boxes": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_lattice": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_tris": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.c_uint32]),

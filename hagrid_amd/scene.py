@@ -22,6 +22,9 @@ POINT_QUERY_DTYPE = np.dtype([("p", "<f4", 3), ("r", "<f4")])
 CLOSEST_DTYPE = np.dtype([("q", "<f4", 3), ("d2", "<f4"), ("id", "<i4"), ("feature", "<i4"), ("side", "<f4"), ("zero", "<i4")])
 # neighbour queries (hagrid_nearest_tris): 8 bytes per slot of a list, and per cursor
 NEAREST_ENTRY_DTYPE = np.dtype([("d2", "<f4"), ("id", "<i4")])
+# capsule queries (hagrid_segment_tris): 32 bytes per segment; a record is CLOSEST_DTYPE with s in the word that is 0 there
+SEGMENT_DTYPE = np.dtype([("a", "<f4", 3), ("r", "<f4"), ("b", "<f4", 3), ("pad", "<f4")])
+SEGMENT_RECORD_DTYPE = np.dtype([("q", "<f4", 3), ("d2", "<f4"), ("id", "<i4"), ("feature", "<i4"), ("side", "<f4"), ("s", "<f4")])
 # box-overlap queries (hagrid_overlap_boxes): 32 bytes per box, the layout of BBox with `first` in the pad slot after min
 BOX_QUERY_DTYPE = np.dtype([("min", "<f4", 3), ("first", "<i4"), ("max", "<f4", 3), ("pad", "<i4")])
 OVERLAP_ANY = 1
@@ -681,14 +684,18 @@ def _sorted_candidates(T, cols, p, k, cursors, query_labels, tri_labels):
     """the candidates of hagrid_nearest_tris for a chunk of points p (m, 4) as three flat arrays (query, triangle, d2), grouped by query and sorted by
     (d2, id) inside a query; k: None = all of them, else at least the k smallest of every query"""
     r2 = p[:, 3] * p[:, 3]
-    valid, d2 = _point_tri((p[:, 0:1], p[:, 1:2], p[:, 2:3]), cols, False)
+    if p.shape[1] == 8:                                          # segments: seg_tri, and no walk for a coordinate that is not finite
+        valid, d2 = _seg_tri((p[:, 0:1], p[:, 1:2], p[:, 2:3]), (p[:, 4:5], p[:, 5:6], p[:, 6:7]), cols, False)
+        valid = valid & np.isfinite(p[:, [0, 1, 2, 4, 5, 6]]).all(axis=1)[:, None]
+    else:
+        valid, d2 = _point_tri((p[:, 0:1], p[:, 1:2], p[:, 2:3]), cols, False)
     mask = valid & (d2 <= r2[:, None]) & (p[:, 3:4] >= np.float32(0.0))
     if cursors is not None:
         cd, ci = cursors["d2"][:, None], cursors["id"][:, None]
         mask &= (d2 > cd) | ((d2 == cd) & (np.arange(T.shape[0], dtype=np.int64)[None, :] > ci))
     if query_labels is not None:
-        ql = query_labels[:, None]
-        mask &= ~((ql >= 0) & ((tri_labels[None, :, 0] == ql) | (tri_labels[None, :, 1] == ql) | (tri_labels[None, :, 2] == ql)))
+        for ql in (query_labels[:, None],) if query_labels.ndim == 1 else (query_labels[:, 0:1], query_labels[:, 1:2]):
+            mask &= ~((ql >= 0) & ((tri_labels[None, :, 0] == ql) | (tri_labels[None, :, 1] == ql) | (tri_labels[None, :, 2] == ql)))
     if k is not None and T.shape[0] > k:
         kth = np.partition(np.where(mask, d2, np.float32(np.inf)), k - 1, axis=1)[:, k - 1]
         mask &= d2 <= kth[:, None]
@@ -763,6 +770,250 @@ def tris_within(tris: np.ndarray, points: np.ndarray, query_labels=None, tri_lab
     offsets = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(counts, out=offsets[1:])
     return {"offsets": offsets, "ids": np.concatenate(all_ids), "d2": np.concatenate(all_d)}
+
+
+# ---- capsule queries: the numpy statement of include/hagrid/capsule.h (same operations, same order, same bits) ---------------------------
+
+def _clamp01(x):
+    zero, one = np.float32(0.0), np.float32(1.0)
+    x = np.where(x > zero, x, zero)
+    return np.where(x < one, x, one)
+
+
+def _seg_edge(a, d, A, e, u):
+    """seg_edge of capsule.h: (d2, q, s) of the segment a + d * s against the edge e + u * t"""
+    zero, one = np.float32(0.0), np.float32(1.0)
+    d2_0, q_0 = _segment_d2(a, e, u)                               # A == 0: the candidate IS segment_d2
+    w = _sub3(a, e)
+    E = _dot3(u, u); F = _dot3(u, w); C = _dot3(d, w)
+    B = _dot3(d, u)
+    den = A * E - B * B
+    s = np.where(den > zero, _clamp01((B * F - C * E) / den), zero)
+    t = (B * s + F) / E
+    s_lo = _clamp01(-C / A); s_hi = _clamp01((B - C) / A)
+    lo = ~(t >= zero); hi = ~lo & (t > one)
+    s = np.where(lo, s_lo, np.where(hi, s_hi, s)); t = np.where(lo, zero, np.where(hi, one, t))
+    flat = E == zero                                               # an edge of no length
+    s = np.where(flat, s_lo, s); t = np.where(flat, zero, t)
+    c = tuple(a[i] + d[i] * s for i in range(3))
+    q = tuple(e[i] + u[i] * t for i in range(3))
+    cq = _sub3(c, q)
+    d2 = _dot3(cq, cq)
+    point = A == zero
+    return np.where(point, d2_0, d2), tuple(np.where(point, q_0[i], q[i]) for i in range(3)), np.where(point, zero, s)
+
+
+def _seg_tri(a, b, T, want_q: bool):
+    """seg_tri (and tri_side) of capsule.h on broadcastable float32 arrays: a, b = (x, y, z), T = the 12 columns of the Tri records.
+    Returns valid, d2 and -- with want_q -- q (three arrays), feature, side, s."""
+    zero, one = np.float32(0.0), np.float32(1.0)
+    v0, e1, e2, n = (T[0], T[1], T[2]), (T[4], T[5], T[6]), (T[8], T[9], T[10]), (T[3], T[7], T[11])
+    valid, d2, q, f, _ = _point_tri(a, T, True)
+    _, db, qb, fb, _ = _point_tri(b, T, True)
+    shape = np.broadcast(d2, db).shape
+    less = db < d2
+    d2 = np.where(less, db, d2); q = tuple(np.where(less, qb[i], q[i]) for i in range(3)); f = np.where(less, fb, f)
+    s = np.where(less, one, np.zeros(shape, np.float32))
+    v1 = _sub3(v0, e1); v2 = (v0[0] + e2[0], v0[1] + e2[1], v0[2] + e2[2])
+    u1 = (-e1[0], -e1[1], -e1[2]); u2 = _sub3(v2, v1)
+    d = _sub3(b, a)
+    A = _dot3(d, d)
+    for k, (e, u) in ((1, (v0, u1)), (2, (v1, u2)), (3, (v0, e2))):
+        dk, qk, sk = _seg_edge(a, d, A, e, u)
+        less = dk < d2
+        d2 = np.where(less, dk, d2)
+        if want_q:
+            q = tuple(np.where(less, qk[i], q[i]) for i in range(3)); f = np.where(less, np.int32(k), f); s = np.where(less, sk, s)
+    ha = _dot3(_sub3(a, v0), n); hb = _dot3(_sub3(b, v0), n)
+    cross_ = ((ha > zero) & (hb < zero)) | ((ha < zero) & (hb > zero))
+    sx = ha / (ha - hb)
+    x = tuple(a[i] + d[i] * sx for i in range(3))
+    x0 = _sub3(x, v0); x1 = _sub3(x, v1)
+    s1 = _dot3(_cross3(e1, x0), n); s2 = _dot3(_cross3(x1, u2), n); s3 = _dot3(_cross3(e2, x0), n)
+    pierce = cross_ & (s1 >= zero) & (s2 >= zero) & (s3 >= zero) & (_dot3(n, n) > zero) & (zero < d2)
+    d2 = np.where(pierce, zero, d2)
+    if not want_q:
+        return valid, d2
+    q = tuple(np.where(pierce, x[i], q[i]) for i in range(3)); f = np.where(pierce, np.int32(4), f); s = np.where(pierce, sx, s)
+    c = tuple(a[i] + d[i] * s for i in range(3))
+    sd = _dot3(_sub3(c, q), n)
+    side = np.where(sd > zero, np.int32(1), np.where(sd < zero, np.int32(-1), np.int32(0)))
+    return valid, d2, q, f, side, s
+
+
+def _segments(segments) -> np.ndarray:
+    return np.ascontiguousarray(segments).view(np.float32).reshape(-1, 8)
+
+
+def segment_pairs(tris: np.ndarray, segments: np.ndarray) -> dict:
+    """Triangle i against segment i (segments: (n, 8) float32 ax, ay, az, r, bx, by, bz, 0, or SEGMENT_DTYPE): valid (the triangle has a surface), d2,
+    q (n, 3) on the triangle, feature (0 face, 1 .. 3 edge, 4 pierced), side, s -- the per-pair values of include/hagrid/capsule.h (seg_tri, tri_side),
+    bit for bit."""
+    T = np.ascontiguousarray(tris, dtype=np.float32); S = _segments(segments)
+    with np.errstate(all="ignore"):
+        valid, d2, q, f, side, s = _seg_tri((S[:, 0], S[:, 1], S[:, 2]), (S[:, 4], S[:, 5], S[:, 6]), [T[:, i] for i in range(12)], True)
+    return {"valid": valid, "d2": d2.astype(np.float32), "q": np.stack(q, axis=1).astype(np.float32), "feature": f.astype(np.int32),
+            "side": side.astype(np.int32), "s": s.astype(np.float32)}
+
+
+def _segment_args(tris, segments, cursors, query_labels, tri_labels):
+    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
+    C_ = None if cursors is None else np.ascontiguousarray(cursors).view(NEAREST_ENTRY_DTYPE).reshape(-1)
+    ql = None if query_labels is None else np.asarray(query_labels, dtype=np.int32).reshape(-1, 2)
+    tl = None if tri_labels is None else np.asarray(tri_labels, dtype=np.int32).reshape(-1, 3)
+    return T, _segments(segments), C_, ql, tl
+
+
+def segment_tris(tris: np.ndarray, segments: np.ndarray, k: int, cursors=None, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 20):
+    """The definition of hagrid_segment_tris by brute force: segments (n, 8) float32 ax, ay, az, r, bx, by, bz, 0 (or SEGMENT_DTYPE).  Triangle j is a
+    candidate of query i when it has a surface, seg_tri's d2 <= r * r (a NaN d2 never is), the pair is not skipped by the labels (query_labels (n, 2)
+    int32, tri_labels (N, 3) int32, both or neither: skipped when one of query_labels[i] >= 0 equals one of tri_labels[j]) and (d2, j) sorts strictly
+    after cursors[i] (NEAREST_ENTRY_DTYPE (n,), or None).  Returns (entries (n, k) NEAREST_ENTRY_DTYPE, records (n, k) SEGMENT_RECORD_DTYPE): the k
+    smallest candidates by (d2, id); unused slots id -1, d2 = r * r, q = a, s = 0; r < 0: an inactive query, every slot id -1 and d2 = -1; a NaN or
+    infinite coordinate: id -1, d2 = r * r.  Every segment against every triangle, a chunk of segments at a time."""
+    T, S, C_, ql, tl = _segment_args(tris, segments, cursors, query_labels, tri_labels)
+    n, N = S.shape[0], T.shape[0]
+    k = int(k)
+    entries = np.zeros((n, k), dtype=NEAREST_ENTRY_DTYPE)
+    records = np.zeros((n, k), dtype=SEGMENT_RECORD_DTYPE)
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        r2 = S[:, 3] * S[:, 3]
+        entries["d2"] = np.where(S[:, 3] < np.float32(0.0), np.float32(-1.0), r2)[:, None]
+        entries["id"] = -1
+        for o in range(0, n if N else 0, m):
+            sl = slice(o, o + m)
+            rows, ids, d = _sorted_candidates(T, cols, S[sl], k, None if C_ is None else C_[sl], None if ql is None else ql[sl], tl)
+            start = np.searchsorted(rows, rows)
+            rank = np.arange(rows.size) - start
+            keep = rank < k
+            entries["id"][o + rows[keep], rank[keep]] = ids[keep]
+            entries["d2"][o + rows[keep], rank[keep]] = d[keep]
+        records["q"] = S[:, None, 0:3]; records["d2"] = entries["d2"]; records["id"] = entries["id"]
+        qi, sj = np.nonzero(entries["id"] >= 0)
+        if qi.size:
+            Tw = T[entries["id"][qi, sj]]; p = S[qi]
+            _, d2w, q, f, side, s = _seg_tri((p[:, 0], p[:, 1], p[:, 2]), (p[:, 4], p[:, 5], p[:, 6]), [Tw[:, i] for i in range(12)], True)
+            assert (d2w.astype(np.float32).view(np.uint32) == entries["d2"][qi, sj].view(np.uint32)).all()
+            records["q"][qi, sj] = np.stack(q, axis=1); records["feature"][qi, sj] = f; records["side"][qi, sj] = side.astype(np.float32)
+            records["s"][qi, sj] = s
+    return entries, records
+
+
+def tris_near_segments(tris: np.ndarray, segments: np.ndarray, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 20) -> dict:
+    """ALL the candidates of segment_tris (no cursor) of every segment, sorted by (d2, id), in CSR form: "offsets" int64 (n + 1,), "ids" int32 and "d2"
+    float32 (total,) -- what the pages of hagrid_segment_tris concatenate to (api.tris_near_segments).  For queries with a finite radius."""
+    T, S, _, ql, tl = _segment_args(tris, segments, None, query_labels, tri_labels)
+    n, N = S.shape[0], T.shape[0]
+    counts = np.zeros(n, dtype=np.int64)
+    all_ids, all_d = [np.zeros(0, np.int32)], [np.zeros(0, np.float32)]
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        for o in range(0, n if N else 0, m):
+            sl = slice(o, o + m)
+            rows, ids, d = _sorted_candidates(T, cols, S[sl], None, None, None if ql is None else ql[sl], tl)
+            np.add.at(counts, o + rows, 1)
+            all_ids.append(ids.astype(np.int32)); all_d.append(d.astype(np.float32))
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return {"offsets": offsets, "ids": np.concatenate(all_ids), "d2": np.concatenate(all_d)}
+
+
+def mesh_edges(faces: np.ndarray) -> np.ndarray:
+    """the unique edges of an indexed mesh as (m, 2) int32 vertex pairs, smaller index first, sorted"""
+    F = np.asarray(faces, dtype=np.int64)
+    e = np.concatenate([F[:, [0, 1]], F[:, [1, 2]], F[:, [2, 0]]])
+    e = np.sort(e, axis=1)
+    return np.unique(e[e[:, 0] != e[:, 1]], axis=0).astype(np.int32)
+
+
+def make_segments(a, b, r) -> np.ndarray:
+    """(n, 8) float32 segment records from ends a, b (n, 3) and radii r (n,) or a scalar"""
+    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
+    s = np.zeros((a.shape[0], 8), dtype=np.float32)
+    s[:, 0:3] = a; s[:, 3] = r; s[:, 4:7] = b
+    return s
+
+
+def make_segments_short(tris: np.ndarray, bbox_min, bbox_max, count: int, seed: int, length: float = 0.005, r=np.inf) -> np.ndarray:
+    """the ordinary case: a near the surface (make_points_near_surface), b = a + a Gaussian of `length` box diagonals per axis"""
+    a = make_points_near_surface(tris, bbox_min, bbox_max, count, seed)
+    b = (a + make_gaussian3(seed ^ 0x73686F72, count) * (np.float32(length) * bbox_diagonal(bbox_min, bbox_max))).astype(np.float32)
+    return make_segments(a, b, r)
+
+
+def make_segments_diagonal(bbox_min, bbox_max, count: int, seed: int, r=np.inf) -> np.ndarray:
+    """long diagonals: from near one corner of the box to near the opposite one (each end within 5 % of the extents of its corner), the four body
+    diagonals in turn"""
+    lo = np.asarray(bbox_min, np.float32); hi = np.asarray(bbox_max, np.float32)
+    u = _uniform_rows(seed, count, 6) * np.float32(0.05)
+    corner = ((np.arange(count)[:, None] % 4) >> np.arange(3)[None, :]) & 1            # x, y flip with the diagonal; z runs low to high
+    corner[:, 2] = 0
+    ta = np.where(corner == 1, np.float32(1.0) - u[:, 0:3], u[:, 0:3]).astype(np.float32)
+    tb = np.where(corner == 1, u[:, 3:6], np.float32(1.0) - u[:, 3:6]).astype(np.float32)
+    return make_segments(lo + (hi - lo) * ta, lo + (hi - lo) * tb, r)
+
+
+def make_segments_axis(bbox_min, bbox_max, count: int, seed: int, r=np.inf) -> np.ndarray:
+    """axis-aligned: a uniform in the box, b = a moved along axis i % 3 by up to 30 % of that extent, either way"""
+    lo = np.asarray(bbox_min, np.float32); hi = np.asarray(bbox_max, np.float32)
+    a = make_points_uniform(lo, hi, count, seed, enlarge=0.0)
+    u = _uniform_rows(seed ^ 0x61786973, count, 1)[:, 0]
+    b = a.copy()
+    axis = np.arange(count) % 3
+    b[np.arange(count), axis] = a[np.arange(count), axis] + (u * np.float32(0.6) - np.float32(0.3)) * (hi - lo)[axis]
+    return make_segments(a, b, r)
+
+
+def make_segments_on_edges(tris: np.ndarray, count: int, seed: int, r=np.inf) -> np.ndarray:
+    """along triangle edges and on them: for a triangle uniform by index its edge v0 -> v1 (v1 = v0 - e1): a third of the segments the edge itself, a
+    third a part of it (a = v0 + u * t0, b = v0 + u * t1), a third the edge moved along the stored normal by 1e-3 of its length (parallel, off the edge)"""
+    u = _uniform_rows(seed, count, 3)
+    j = np.minimum((u[:, 0] * np.float32(tris.shape[0])).astype(np.int64), tris.shape[0] - 1)
+    t = tris[j]
+    v0 = t[:, 0:3]; e = (-t[:, 4:7]).astype(np.float32)
+    kind = np.arange(count) % 3
+    t0 = np.where(kind == 1, u[:, 1], np.float32(0.0))[:, None]; t1 = np.where(kind == 1, u[:, 2], np.float32(1.0))[:, None]
+    n = t[:, [3, 7, 11]]
+    nn = np.sqrt((n * n).sum(axis=1, dtype=np.float32))[:, None]
+    el = np.sqrt((e * e).sum(axis=1, dtype=np.float32))[:, None]
+    with np.errstate(all="ignore"):
+        off = np.where((kind == 2)[:, None] & (nn > 0), n / nn * (el * np.float32(1e-3)), np.float32(0.0)).astype(np.float32)
+    return make_segments(v0 + e * t0 + off, v0 + e * t1 + off, r)
+
+
+def make_segments_piercing(tris: np.ndarray, bbox_min, bbox_max, count: int, seed: int, r=np.inf) -> np.ndarray:
+    """through a face near its centroid: for a triangle uniform by index, from c + w * h to c - w * h with c the centroid, h = 0.5 % of the box
+    diagonal and w the unit normal tilted by a Gaussian of 0.2"""
+    u = _uniform_rows(seed, count, 1)
+    j = np.minimum((u[:, 0] * np.float32(tris.shape[0])).astype(np.int64), tris.shape[0] - 1)
+    t = tris[j]
+    c = (t[:, 0:3] + (t[:, 8:11] - t[:, 4:7]) * np.float32(1.0 / 3.0)).astype(np.float32)
+    n = t[:, [3, 7, 11]]
+    nn = np.sqrt((n * n).sum(axis=1, dtype=np.float32))[:, None]
+    with np.errstate(all="ignore"):
+        w = np.where(nn > 0, n / nn, np.float32([0.0, 0.0, 1.0])).astype(np.float32) + make_gaussian3(seed ^ 0x70696572, count) * np.float32(0.2)
+    h = np.float32(0.005) * bbox_diagonal(bbox_min, bbox_max)
+    return make_segments(c + w * h, c - w * h, r)
+
+
+def make_segments_outside(bbox_min, bbox_max, count: int, seed: int, r=np.inf) -> np.ndarray:
+    """one end outside the grid (even rows: a uniform in the box, b up to half a diagonal beyond one face) and both outside (odd rows: a and b beyond
+    faces of different axes, so some cross the box and some pass it)"""
+    lo = np.asarray(bbox_min, np.float32); hi = np.asarray(bbox_max, np.float32)
+    diag = bbox_diagonal(lo, hi)
+    a = make_points_uniform(lo, hi, count, seed, enlarge=0.0); b = make_points_uniform(lo, hi, count, seed ^ 0x6F757473, enlarge=0.0)
+    u = _uniform_rows(seed ^ 0x62657961, count, 2) * np.float32(0.5) * diag + np.float32(0.01) * diag
+    i = np.arange(count)
+    ax_b = i % 3; up_b = (i // 3) % 2 == 0
+    b[i, ax_b] = np.where(up_b, hi[ax_b] + u[:, 0], lo[ax_b] - u[:, 0])
+    both = i % 2 == 1
+    ax_a = (i + 1) % 3; up_a = (i // 2) % 2 == 0
+    a[i, ax_a] = np.where(both, np.where(up_a, hi[ax_a] + u[:, 1], lo[ax_a] - u[:, 1]), a[i, ax_a])
+    return make_segments(a, b, r)
 
 
 # ---- box-overlap queries: the numpy statement of include/hagrid/overlap.h (same operations, same order, same truth values) ----------------

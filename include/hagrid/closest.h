@@ -166,7 +166,10 @@ struct NearList {
         }
         Pair r;
         if (!point_tri(tri, p, r)) return;
-        const float c = r.d2;
+        insert(r.d2, ref);
+    }
+    /// the candidate (c, ref) of a pair that the labels do not skip: the rest of the candidate rule, and its place in the list (capsule.h offers seg_tri's d2 here)
+    HOST DEVICE void insert(const float c, int ref) {
         if (!(c <= d2)) return;                                                 // NaN, or beyond r2 (d2 is never above r2)
         if (!(c > cur_d2 || (c == cur_d2 && ref > cur_id))) return;             // not after the cursor (a NaN cursor: nothing is)
         if (last_id >= 0 && !before(c, ref, d2, last_id)) return;               // cannot change a full list

@@ -351,6 +351,36 @@ int hagrid_nearest_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tr
                         const void* cursors, const void* query_labels, const void* tri_labels, void* entries, void* records,
                         void* counters, uint32_t flags);
 
+/* Extension (no reference counterpart): CAPSULE queries -- for every SEGMENT of a batch the k nearest triangles within its radius, nearest first, paged
+ * (the edge-edge half of a cloth or rod step's proximity pairs; a character's or a robot link's capsule; "does this cable, or this line of sight, clear
+ * the mesh by r").  An additive extension: HAGRID_ABI_VERSION stays 3.  segments holds 32 bytes per query, 16-byte aligned:
+ *   float32 ax, ay, az, r;  bx, by, bz, 0.
+ * r2 = r * r (+inf allowed).  d2 is the squared distance between the segment a -> b and the triangle as seg_tri of include/hagrid/capsule.h computes it:
+ * float32 without contraction, operation for operation (hagrid_amd/scene.py: segment_pairs, segment_tris state the same in numpy -- the same bits), the
+ * smallest of: the two ends against the triangle (point_tri), the segment against the triangle's three edges, and 0 where the segment pierces the face.
+ * With a == b it is point_tri's d2, bit for bit.  r < 0 is an INACTIVE query (k slots d2 = -1, id -1); a NaN or infinite coordinate or a NaN radius gives
+ * id -1, d2 = r2 everywhere; neither walks.  entries, cursors, the candidate rule, the order (d2 ascending, id ascending), unused slots (d2 = r2, id -1),
+ * 1 <= k <= HAGRID_MAX_NEAREST and paging are exactly those of hagrid_nearest_tris.
+ *   query_labels DEVICE int32[2 per segment] (the edge's two vertex indices; -1: an unused slot), tri_labels DEVICE int32[3 per scene triangle], both
+ *            given or both NULL: pair (i, j) is SKIPPED when one of the query's labels >= 0 equals one of triangle j's three.  With a mesh's own edges
+ *            as queries and its index triples as triangle labels an edge does not see the triangles that share a vertex with it.
+ *   records  NULL, or DEVICE k x 32 bytes per query, 16-byte aligned: {float32 qx, qy, qz, d2}, {int32 id, int32 feature, float32 side, float32 s} --
+ *            the record of hagrid_closest_points with s in the word that is 0 there.  q is the closest point ON THE TRIANGLE, s in [0, 1] the parameter
+ *            of the closest point c = a + (b - a) * s ON THE SEGMENT, feature 0 face / 1, 2, 3 edge (as hagrid_closest_points) / 4 the segment pierces
+ *            the face (d2 = 0, q = the point of piercing), side = sign(dot(c - q, n)).  An unused slot: q = a, the slot's d2, id -1, feature = side = 0,
+ *            s = +0.  Made again from the winners' ids after the walk.
+ *   counters NULL, or DEVICE int64[5] as hagrid_nearest_tris: queries, cells visited, triangles tested, sub-blocks pruned, lists that came back full.
+ * Promises: the lists are those of the brute force over all triangles, bit for bit; the list for k is a prefix of the list for k + 1; the pages
+ * concatenated are all candidates, sorted; the labelled answer is the unlabelled answer over the scene without the skipped triangles, ids unchanged;
+ * with a == b, the first label of each pair set and the second -1, entries and records are hagrid_nearest_tris' for the points (a, r), bit for bit --
+ * hence at k = 1 without cursor or labels hagrid_closest_points' output.  There is no exact count of the capsule's content (as hagrid_nearest_tris).
+ * Asynchronous on the context's stream; walks the CONSTRUCTION format (include/hagrid/capsule.h); the traversal image, ray binning and the
+ * hints kept for the nearest-hit path are neither used nor touched.  HAGRID_EINVAL and HAGRID_ERANGE (num_segments * k beyond 2^31 - 1): everything
+ * hagrid_nearest_tris refuses.  num_segments = 0 is HAGRID_OK (null buffers are then fine). */
+int hagrid_segment_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* segments, int num_segments, int k,
+                        const void* cursors, const void* query_labels, const void* tri_labels, void* entries, void* records,
+                        void* counters, uint32_t flags);
+
 /* Extension (no reference counterpart): BOX-OVERLAP queries -- for every axis-aligned box of a batch, which triangles meet it (contact candidates,
  * culling, sparse-volume allocation, surface voxelization).  Triangle j MEETS the box [lo, hi] exactly when intersect_tri_box<true, true>(v0, e1, e2, n,
  * lo, hi) of include/hagrid/prims.h says so: the triangle's plane, the three box axes and the nine cross axes, float32 without contraction in the
