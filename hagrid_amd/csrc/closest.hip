@@ -46,18 +46,7 @@ __global__ void __launch_bounds__(64) closest_points_kernel(const DevGrid g, con
     if (counters) add_batch_counters(counters, lane, live ? 1 : 0, cnt.cells, cnt.tris, cnt.pruned);
 }
 
-struct NearestArgs {
-    const float4* __restrict__ points;
-    const float2* __restrict__ cursors;
-    const int* __restrict__ query_labels;
-    const int* __restrict__ tri_labels;
-    float2* __restrict__ entries;
-    float4* __restrict__ records;
-    unsigned long long* __restrict__ counters;
-    int n, k;
-};
-
-__global__ void __launch_bounds__(64) nearest_tris_kernel(const DevGrid g, const NearestArgs a) {
+__global__ void __launch_bounds__(64) nearest_tris_kernel(const DevGrid g, const ListArgs a) {
     __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
     const int lane = threadIdx.x;
     const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
@@ -66,7 +55,7 @@ __global__ void __launch_bounds__(64) nearest_tris_kernel(const DevGrid g, const
     cnt.cells = 0; cnt.tris = 0; cnt.pruned = 0;
     int full = 0;
     if (live) {
-        const float4 pr = nt_load4(a.points + id);
+        const float4 pr = nt_load4(a.queries + id);
         const vec3 p(pr.x, pr.y, pr.z);
         LdsStack st;
         st.w_ = &s_w[0][lane]; st.i_ = &s_i[0][lane];
@@ -101,10 +90,7 @@ extern "C" int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, c
     if (!ctx) return HAGRID_EINVAL;
     if (flags) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: unknown flag (flags must be 0)");
     if (num_points < 0) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: negative num_points");
-    if (!grid) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: null grid");
-    if (!grid->entries || (!grid->cells && !grid->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: the walk reads the construction format (grid released for traversal, or incomplete)");
-    if (!grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: incomplete grid");
-    if (grid->shift < 0 || grid->shift > 15 || grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: bad shift or dims");
+    HG_TRY(check_walk_grid(ctx, "closest_points", grid));
     if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: the counters must be 8-byte aligned");
     if (num_points == 0) return HAGRID_OK;
     if (!tris || !points || !results) HG_FAIL(ctx, HAGRID_EINVAL, "closest_points: null triangle, point or result buffer");
@@ -122,32 +108,5 @@ extern "C" int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, c
 extern "C" int hagrid_nearest_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points, int k, const void* cursors,
                                    const void* query_labels, const void* tri_labels, void* entries, void* records, void* counters, uint32_t flags) {
     if (!ctx) return HAGRID_EINVAL;
-    if (flags) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: unknown flag (flags must be 0)");
-    if (num_points < 0) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: negative num_points");
-    if (k < 1 || k > HAGRID_MAX_NEAREST) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: k must be 1 .. HAGRID_MAX_NEAREST");
-    if (!grid) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: null grid");
-    if (!grid->entries || (!grid->cells && !grid->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: the walk reads the construction format (grid released for traversal, or incomplete)");
-    if (!grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: incomplete grid");
-    if (grid->shift < 0 || grid->shift > 15 || grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: bad shift or dims");
-    if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: the counters must be 8-byte aligned");
-    if ((query_labels != nullptr) != (tri_labels != nullptr)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: query_labels and tri_labels are given together or not at all");
-    if (int64_t(num_points) * int64_t(k) > int64_t(INT32_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "nearest_tris: num_points * k beyond 2^31 - 1");
-    if (num_points == 0) return HAGRID_OK;
-    if (!tris || !points) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: null triangle or point buffer");
-    if (!entries && !records) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: entries and records are both null");
-    if (!aligned(tris, 16) || !aligned(points, 16) || !aligned(records, 16)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: triangles, points and records must be 16-byte aligned");
-    if (!aligned(entries, 8) || !aligned(cursors, 8)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: entries and cursors must be 8-byte aligned");
-    if (!aligned(query_labels, 4) || !aligned(tri_labels, 4)) HG_FAIL(ctx, HAGRID_EINVAL, "nearest_tris: the labels must be 4-byte aligned");
-    HG_HIP(ctx, hipSetDevice(ctx->device));
-    DevGrid g;
-    g.set(grid, tris);
-    NearestArgs a;
-    a.points = static_cast<const float4*>(points); a.cursors = static_cast<const float2*>(cursors);
-    a.query_labels = static_cast<const int*>(query_labels); a.tri_labels = static_cast<const int*>(tri_labels);
-    a.entries = static_cast<float2*>(entries); a.records = static_cast<float4*>(records); a.counters = static_cast<unsigned long long*>(counters);
-    a.n = num_points; a.k = k;
-    nearest_tris_kernel<<<grid_blocks(num_points, 64), 64, 0, ctx->stream>>>(g, a);
-    HG_DBG(ctx);
-    HG_HIP(ctx, hipGetLastError());
-    return HAGRID_OK;
+    return launch_lists(ctx, "nearest_tris", "point", nearest_tris_kernel, grid, tris, points, num_points, k, cursors, query_labels, tri_labels, entries, records, counters, flags);
 }

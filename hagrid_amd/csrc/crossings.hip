@@ -72,7 +72,7 @@ struct RowEmit {
     __device__ __forceinline__ void operator()(int first, int stride, int length, int state) const {
         int e = first;
         int left = length;
-        asm volatile("" : "+v"(e));         // addresses are made here, from the index: made ahead they would be carried through the whole walk, two registers each
+        HAGRID_MADE_HERE(e);         // addresses are made here, from the index: made ahead they would be carried through the whole walk, two registers each
         if (stride == 1 && pass == 0) {
             const unsigned b = hx::row_bits(0u, 0, valid, state);
             if (last) {
@@ -177,12 +177,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) cr
                 n_short = rec.id > sink.room() ? 1 : 0;
                 const unsigned long long none = EntrySink::word(tmax, 0xffffffffu);
                 int again = id;
-                asm volatile("" : "+v"(again));         // the range once more, from the ray's number: neither it nor its address is carried through the walk
+                HAGRID_MADE_HERE(again);         // the range once more, from the ray's number: neither it nor its address is carried through the walk
                 hx::slot_range(q.offsets, q.stride, q.capacity, again, first, room);
                 for (long long p = n_written; p < room; p++) __builtin_nontemporal_store(none, q.entries + first + p);
             }
             if (q.row) {            // (m = 1) the voxels behind the last crossing; a row that ends inside once more, as "abstains"
-                asm volatile("" : "+v"(sink.row.base));         // (as in RowEmit: nothing made from the base before the walk is carried through it)
+                HAGRID_MADE_HERE(sink.row.base);         // (as in RowEmit: nothing made from the base before the walk is carried through it)
                 sink.row.finish();
                 if (sink.row.state()) {
                     n_abstained = 1;

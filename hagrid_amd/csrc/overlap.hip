@@ -121,10 +121,7 @@ int launch(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid, const void
     if (flags & ~HAGRID_OVERLAP_ANY) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": unknown flag (HAGRID_OVERLAP_ANY is the only one)").c_str());
     if (a.k < 1 || a.k > HAGRID_MAX_OVERLAP_IDS) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": k must be 1 .. HAGRID_MAX_OVERLAP_IDS").c_str());
     if ((flags & HAGRID_OVERLAP_ANY) && a.k != 1) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": HAGRID_OVERLAP_ANY needs k = 1").c_str());
-    if (!grid) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": null grid").c_str());
-    if (!grid->entries || (!grid->cells && !grid->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the walk reads the construction format (grid released for traversal, or incomplete)").c_str());
-    if (!grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": incomplete grid").c_str());
-    if (grid->shift < 0 || grid->shift > 15 || grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": bad shift or dims").c_str());
+    HG_TRY(check_walk_grid(ctx, who, grid));
     if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the counters must be 8-byte aligned").c_str());
     if (!aligned(counts, 4)) HG_FAIL(ctx, HAGRID_EINVAL, (std::string(who) + ": the counts must be 4-byte aligned").c_str());
     if (a.n == 0) return HAGRID_OK;

@@ -188,6 +188,18 @@ __device__ __forceinline__ void nt_store2(float2* p, float x, float y) {
     __builtin_nontemporal_store(v, reinterpret_cast<f32x2*>(p));
 }
 
+// ---- list queries: the k nearest triangles of every query, paged (closest.hip: points, nearest_tris_kernel; capsule.hip: segments, segment_tris_kernel) ----
+struct ListArgs {
+    const float4* __restrict__ queries;     ///< a point: x, y, z, r; a segment: two float4, a, r; b, 0
+    const float2* __restrict__ cursors;
+    const int* __restrict__ query_labels;   ///< one per point, two per segment
+    const int* __restrict__ tri_labels;
+    float2* __restrict__ entries;
+    float4* __restrict__ records;
+    unsigned long long* __restrict__ counters;
+    int n, k;
+};
+
 // ---- tile packets ---------------------------------------------------------------------------------------------------
 // A batch of camera rays arrives in image order (gen_rays, main.cpp:55-66: ray y * w + x), so 64 consecutive rays are
 // a 64 x 1 pixel strip: the lanes of a wavefront fan out over 64 pixel columns and share few cells.  An 8 x 8 pixel
@@ -399,6 +411,45 @@ inline int check_lattice(hagrid_ctx* ctx, const char* who, const float* origin, 
         if (!(size[i] > 0.0f) || !(size[i] <= 3.4028234663852886e38f) || !(origin[i] >= -3.4028234663852886e38f && origin[i] <= 3.4028234663852886e38f))
             HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the voxel size must be positive and finite, the origin finite").c_str());
     *total = int(voxels);
+    return HAGRID_OK;
+}
+// the grid of a query that walks the construction format with block_walk.h: there, complete, its shift and dims in range
+inline int check_walk_grid(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid) {
+    const std::string w(who);
+    if (!grid) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null grid").c_str());
+    if (!grid->entries || (!grid->cells && !grid->small_cells)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the walk reads the construction format (grid released for traversal, or incomplete)").c_str());
+    if (!grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": incomplete grid").c_str());
+    if (grid->shift < 0 || grid->shift > 15 || grid->dims[0] <= 0 || grid->dims[1] <= 0 || grid->dims[2] <= 0) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": bad shift or dims").c_str());
+    return HAGRID_OK;
+}
+// what the two entry points of the list queries (ListArgs above) check and do; noun: what a query is called in the messages ("point", "segment")
+inline int launch_lists(hagrid_ctx* ctx, const char* who, const char* noun, void (*kernel)(DevGrid, ListArgs), const hagrid_grid* grid, const void* tris, const void* queries, int n,
+                        int k, const void* cursors, const void* query_labels, const void* tri_labels, void* entries, void* records, void* counters, uint32_t flags) {
+    const std::string w(who), q(noun);
+    if (flags) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": unknown flag (flags must be 0)").c_str());
+    if (n < 0) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": negative num_" + q + "s").c_str());
+    if (k < 1 || k > HAGRID_MAX_NEAREST) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": k must be 1 .. HAGRID_MAX_NEAREST").c_str());
+    HG_TRY(check_walk_grid(ctx, who, grid));
+    if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the counters must be 8-byte aligned").c_str());
+    if ((query_labels != nullptr) != (tri_labels != nullptr)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": query_labels and tri_labels are given together or not at all").c_str());
+    if (int64_t(n) * int64_t(k) > int64_t(INT32_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, (w + ": num_" + q + "s * k beyond 2^31 - 1").c_str());
+    if (n == 0) return HAGRID_OK;
+    if (!tris || !queries) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": null triangle or " + q + " buffer").c_str());
+    if (!entries && !records) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": entries and records are both null").c_str());
+    if (!aligned(tris, 16) || !aligned(queries, 16) || !aligned(records, 16)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": triangles, " + q + "s and records must be 16-byte aligned").c_str());
+    if (!aligned(entries, 8) || !aligned(cursors, 8)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": entries and cursors must be 8-byte aligned").c_str());
+    if (!aligned(query_labels, 4) || !aligned(tri_labels, 4)) HG_FAIL(ctx, HAGRID_EINVAL, (w + ": the labels must be 4-byte aligned").c_str());
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+    DevGrid g;
+    g.set(grid, tris);
+    ListArgs a;
+    a.queries = static_cast<const float4*>(queries); a.cursors = static_cast<const float2*>(cursors);
+    a.query_labels = static_cast<const int*>(query_labels); a.tri_labels = static_cast<const int*>(tri_labels);
+    a.entries = static_cast<float2*>(entries); a.records = static_cast<float4*>(records); a.counters = static_cast<unsigned long long*>(counters);
+    a.n = n; a.k = k;
+    kernel<<<grid_blocks(n, 64), 64, 0, ctx->stream>>>(g, a);
+    HG_DBG(ctx);
+    HG_HIP(ctx, hipGetLastError());
     return HAGRID_OK;
 }
 // bytes from p to the end of the device allocation that holds it (all bits set if the runtime does not know the pointer)

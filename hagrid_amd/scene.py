@@ -705,14 +705,71 @@ def _sorted_candidates(T, cols, p, k, cursors, query_labels, tri_labels):
     return rows[order], ids[order], d[order]
 
 
-def _nearest_args(tris, points, cursors, query_labels, tri_labels):
+def _list_args(tris, queries, width, cursors, query_labels, tri_labels):
+    """the arguments of a list query as arrays; width: 4 floats per query (a point, one label) or 8 (a segment, two labels)"""
     assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
     T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
-    P = np.ascontiguousarray(points).view(np.float32).reshape(-1, 4)
+    Q = np.ascontiguousarray(queries).view(np.float32).reshape(-1, width)
     C_ = None if cursors is None else np.ascontiguousarray(cursors).view(NEAREST_ENTRY_DTYPE).reshape(-1)
-    ql = None if query_labels is None else np.asarray(query_labels, dtype=np.int32).reshape(-1)
+    ql = None if query_labels is None else np.asarray(query_labels, dtype=np.int32).reshape((-1,) if width == 4 else (-1, 2))
     tl = None if tri_labels is None else np.asarray(tri_labels, dtype=np.int32).reshape(-1, 3)
-    return T, P, C_, ql, tl
+    return T, Q, C_, ql, tl
+
+
+def _k_lists(tris, queries, width, record_dtype, k, cursors, query_labels, tri_labels, chunk_pairs):
+    """nearest_tris (width 4, CLOSEST_DTYPE) and segment_tris (width 8, SEGMENT_RECORD_DTYPE): every query against every triangle, a chunk of queries at a
+    time; the k smallest candidates by rank; the records made again from the winners"""
+    T, Q, C_, ql, tl = _list_args(tris, queries, width, cursors, query_labels, tri_labels)
+    n, N = Q.shape[0], T.shape[0]
+    k = int(k)
+    entries = np.zeros((n, k), dtype=NEAREST_ENTRY_DTYPE)
+    records = np.zeros((n, k), dtype=record_dtype)
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        r2 = Q[:, 3] * Q[:, 3]
+        entries["d2"] = np.where(Q[:, 3] < np.float32(0.0), np.float32(-1.0), r2)[:, None]
+        entries["id"] = -1
+        for o in range(0, n if N else 0, m):
+            s = slice(o, o + m)
+            rows, ids, d = _sorted_candidates(T, cols, Q[s], k, None if C_ is None else C_[s], None if ql is None else ql[s], tl)
+            start = np.searchsorted(rows, rows)                  # the first position of each entry's query
+            rank = np.arange(rows.size) - start
+            keep = rank < k
+            entries["id"][o + rows[keep], rank[keep]] = ids[keep]
+            entries["d2"][o + rows[keep], rank[keep]] = d[keep]
+        records["q"] = Q[:, None, 0:3]; records["d2"] = entries["d2"]; records["id"] = entries["id"]
+        qi, sj = np.nonzero(entries["id"] >= 0)
+        if qi.size:
+            Tw = T[entries["id"][qi, sj]]; p = Q[qi]
+            Tc = [Tw[:, i] for i in range(12)]
+            if width == 8:
+                _, d2w, q, f, side, sw = _seg_tri((p[:, 0], p[:, 1], p[:, 2]), (p[:, 4], p[:, 5], p[:, 6]), Tc, True)
+                records["s"][qi, sj] = sw
+            else:
+                _, d2w, q, f, side = _point_tri((p[:, 0], p[:, 1], p[:, 2]), Tc, True)
+            assert (d2w.astype(np.float32).view(np.uint32) == entries["d2"][qi, sj].view(np.uint32)).all()
+            records["q"][qi, sj] = np.stack(q, axis=1); records["feature"][qi, sj] = f; records["side"][qi, sj] = side.astype(np.float32)
+    return entries, records
+
+
+def _all_lists(tris, queries, width, query_labels, tri_labels, chunk_pairs) -> dict:
+    """tris_within (width 4) and tris_near_segments (width 8): every candidate of every query, sorted, in CSR form"""
+    T, Q, _, ql, tl = _list_args(tris, queries, width, None, query_labels, tri_labels)
+    n, N = Q.shape[0], T.shape[0]
+    counts = np.zeros(n, dtype=np.int64)
+    all_ids, all_d = [np.zeros(0, np.int32)], [np.zeros(0, np.float32)]
+    cols = [T[None, :, i] for i in range(12)]
+    m = max(1, chunk_pairs // max(N, 1))
+    with np.errstate(all="ignore"):
+        for o in range(0, n if N else 0, m):
+            s = slice(o, o + m)
+            rows, ids, d = _sorted_candidates(T, cols, Q[s], None, None, None if ql is None else ql[s], tl)
+            np.add.at(counts, o + rows, 1)
+            all_ids.append(ids.astype(np.int32)); all_d.append(d.astype(np.float32))
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return {"offsets": offsets, "ids": np.concatenate(all_ids), "d2": np.concatenate(all_d)}
 
 
 def nearest_tris(tris: np.ndarray, points: np.ndarray, k: int, cursors=None, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 21):
@@ -722,54 +779,14 @@ def nearest_tris(tris: np.ndarray, points: np.ndarray, k: int, cursors=None, que
     (NEAREST_ENTRY_DTYPE (n,), or None) in the order (d2 ascending, id ascending).  Returns (entries (n, k) NEAREST_ENTRY_DTYPE, records (n, k)
     CLOSEST_DTYPE): the k smallest candidates in that order; unused slots id -1, d2 = r * r, q = p; r < 0: an inactive query, every slot id -1 and
     d2 = -1.  Every point against every triangle, a chunk of points at a time."""
-    T, P, C_, ql, tl = _nearest_args(tris, points, cursors, query_labels, tri_labels)
-    n, N = P.shape[0], T.shape[0]
-    k = int(k)
-    entries = np.zeros((n, k), dtype=NEAREST_ENTRY_DTYPE)
-    records = np.zeros((n, k), dtype=CLOSEST_DTYPE)
-    cols = [T[None, :, i] for i in range(12)]
-    m = max(1, chunk_pairs // max(N, 1))
-    with np.errstate(all="ignore"):
-        r2 = P[:, 3] * P[:, 3]
-        entries["d2"] = np.where(P[:, 3] < np.float32(0.0), np.float32(-1.0), r2)[:, None]
-        entries["id"] = -1
-        for o in range(0, n if N else 0, m):
-            s = slice(o, o + m)
-            rows, ids, d = _sorted_candidates(T, cols, P[s], k, None if C_ is None else C_[s], None if ql is None else ql[s], tl)
-            start = np.searchsorted(rows, rows)                  # the first position of each entry's query
-            rank = np.arange(rows.size) - start
-            keep = rank < k
-            entries["id"][o + rows[keep], rank[keep]] = ids[keep]
-            entries["d2"][o + rows[keep], rank[keep]] = d[keep]
-        records["q"] = P[:, None, 0:3]; records["d2"] = entries["d2"]; records["id"] = entries["id"]
-        qi, sj = np.nonzero(entries["id"] >= 0)
-        if qi.size:
-            Tw = T[entries["id"][qi, sj]]; p = P[qi]
-            _, d2w, q, f, side = _point_tri((p[:, 0], p[:, 1], p[:, 2]), [Tw[:, i] for i in range(12)], True)
-            assert (d2w.astype(np.float32).view(np.uint32) == entries["d2"][qi, sj].view(np.uint32)).all()
-            records["q"][qi, sj] = np.stack(q, axis=1); records["feature"][qi, sj] = f; records["side"][qi, sj] = side.astype(np.float32)
-    return entries, records
+    return _k_lists(tris, points, 4, CLOSEST_DTYPE, k, cursors, query_labels, tri_labels, chunk_pairs)
 
 
 def tris_within(tris: np.ndarray, points: np.ndarray, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 21) -> dict:
     """ALL the candidates of nearest_tris (no cursor) of every point, sorted by (d2, id), in CSR form: "offsets" int64 (n + 1,), "ids" int32 and "d2"
     float32 (total,) -- what the pages of hagrid_nearest_tris concatenate to (api.tris_within).  For queries with a finite radius: r = inf lists every
     triangle of the scene."""
-    T, P, _, ql, tl = _nearest_args(tris, points, None, query_labels, tri_labels)
-    n, N = P.shape[0], T.shape[0]
-    counts = np.zeros(n, dtype=np.int64)
-    all_ids, all_d = [np.zeros(0, np.int32)], [np.zeros(0, np.float32)]
-    cols = [T[None, :, i] for i in range(12)]
-    m = max(1, chunk_pairs // max(N, 1))
-    with np.errstate(all="ignore"):
-        for o in range(0, n if N else 0, m):
-            s = slice(o, o + m)
-            rows, ids, d = _sorted_candidates(T, cols, P[s], None, None, None if ql is None else ql[s], tl)
-            np.add.at(counts, o + rows, 1)
-            all_ids.append(ids.astype(np.int32)); all_d.append(d.astype(np.float32))
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(counts, out=offsets[1:])
-    return {"offsets": offsets, "ids": np.concatenate(all_ids), "d2": np.concatenate(all_d)}
+    return _all_lists(tris, points, 4, query_labels, tri_labels, chunk_pairs)
 
 
 # ---- capsule queries: the numpy statement of include/hagrid/capsule.h (same operations, same order, same bits) ---------------------------
@@ -856,15 +873,6 @@ def segment_pairs(tris: np.ndarray, segments: np.ndarray) -> dict:
             "side": side.astype(np.int32), "s": s.astype(np.float32)}
 
 
-def _segment_args(tris, segments, cursors, query_labels, tri_labels):
-    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
-    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)
-    C_ = None if cursors is None else np.ascontiguousarray(cursors).view(NEAREST_ENTRY_DTYPE).reshape(-1)
-    ql = None if query_labels is None else np.asarray(query_labels, dtype=np.int32).reshape(-1, 2)
-    tl = None if tri_labels is None else np.asarray(tri_labels, dtype=np.int32).reshape(-1, 3)
-    return T, _segments(segments), C_, ql, tl
-
-
 def segment_tris(tris: np.ndarray, segments: np.ndarray, k: int, cursors=None, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 20):
     """The definition of hagrid_segment_tris by brute force: segments (n, 8) float32 ax, ay, az, r, bx, by, bz, 0 (or SEGMENT_DTYPE).  Triangle j is a
     candidate of query i when it has a surface, seg_tri's d2 <= r * r (a NaN d2 never is), the pair is not skipped by the labels (query_labels (n, 2)
@@ -872,54 +880,13 @@ def segment_tris(tris: np.ndarray, segments: np.ndarray, k: int, cursors=None, q
     after cursors[i] (NEAREST_ENTRY_DTYPE (n,), or None).  Returns (entries (n, k) NEAREST_ENTRY_DTYPE, records (n, k) SEGMENT_RECORD_DTYPE): the k
     smallest candidates by (d2, id); unused slots id -1, d2 = r * r, q = a, s = 0; r < 0: an inactive query, every slot id -1 and d2 = -1; a NaN or
     infinite coordinate: id -1, d2 = r * r.  Every segment against every triangle, a chunk of segments at a time."""
-    T, S, C_, ql, tl = _segment_args(tris, segments, cursors, query_labels, tri_labels)
-    n, N = S.shape[0], T.shape[0]
-    k = int(k)
-    entries = np.zeros((n, k), dtype=NEAREST_ENTRY_DTYPE)
-    records = np.zeros((n, k), dtype=SEGMENT_RECORD_DTYPE)
-    cols = [T[None, :, i] for i in range(12)]
-    m = max(1, chunk_pairs // max(N, 1))
-    with np.errstate(all="ignore"):
-        r2 = S[:, 3] * S[:, 3]
-        entries["d2"] = np.where(S[:, 3] < np.float32(0.0), np.float32(-1.0), r2)[:, None]
-        entries["id"] = -1
-        for o in range(0, n if N else 0, m):
-            sl = slice(o, o + m)
-            rows, ids, d = _sorted_candidates(T, cols, S[sl], k, None if C_ is None else C_[sl], None if ql is None else ql[sl], tl)
-            start = np.searchsorted(rows, rows)
-            rank = np.arange(rows.size) - start
-            keep = rank < k
-            entries["id"][o + rows[keep], rank[keep]] = ids[keep]
-            entries["d2"][o + rows[keep], rank[keep]] = d[keep]
-        records["q"] = S[:, None, 0:3]; records["d2"] = entries["d2"]; records["id"] = entries["id"]
-        qi, sj = np.nonzero(entries["id"] >= 0)
-        if qi.size:
-            Tw = T[entries["id"][qi, sj]]; p = S[qi]
-            _, d2w, q, f, side, s = _seg_tri((p[:, 0], p[:, 1], p[:, 2]), (p[:, 4], p[:, 5], p[:, 6]), [Tw[:, i] for i in range(12)], True)
-            assert (d2w.astype(np.float32).view(np.uint32) == entries["d2"][qi, sj].view(np.uint32)).all()
-            records["q"][qi, sj] = np.stack(q, axis=1); records["feature"][qi, sj] = f; records["side"][qi, sj] = side.astype(np.float32)
-            records["s"][qi, sj] = s
-    return entries, records
+    return _k_lists(tris, segments, 8, SEGMENT_RECORD_DTYPE, k, cursors, query_labels, tri_labels, chunk_pairs)
 
 
 def tris_near_segments(tris: np.ndarray, segments: np.ndarray, query_labels=None, tri_labels=None, chunk_pairs: int = 1 << 20) -> dict:
     """ALL the candidates of segment_tris (no cursor) of every segment, sorted by (d2, id), in CSR form: "offsets" int64 (n + 1,), "ids" int32 and "d2"
     float32 (total,) -- what the pages of hagrid_segment_tris concatenate to (api.tris_near_segments).  For queries with a finite radius."""
-    T, S, _, ql, tl = _segment_args(tris, segments, None, query_labels, tri_labels)
-    n, N = S.shape[0], T.shape[0]
-    counts = np.zeros(n, dtype=np.int64)
-    all_ids, all_d = [np.zeros(0, np.int32)], [np.zeros(0, np.float32)]
-    cols = [T[None, :, i] for i in range(12)]
-    m = max(1, chunk_pairs // max(N, 1))
-    with np.errstate(all="ignore"):
-        for o in range(0, n if N else 0, m):
-            sl = slice(o, o + m)
-            rows, ids, d = _sorted_candidates(T, cols, S[sl], None, None, None if ql is None else ql[sl], tl)
-            np.add.at(counts, o + rows, 1)
-            all_ids.append(ids.astype(np.int32)); all_d.append(d.astype(np.float32))
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(counts, out=offsets[1:])
-    return {"offsets": offsets, "ids": np.concatenate(all_ids), "d2": np.concatenate(all_d)}
+    return _all_lists(tris, segments, 8, query_labels, tri_labels, chunk_pairs)
 
 
 def mesh_edges(faces: np.ndarray) -> np.ndarray:

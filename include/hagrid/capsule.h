@@ -49,12 +49,12 @@
 //
 // ---- the walk: segment_query --------------------------------------------------------------------------------------------------------
 // (a), (b), (c) of closest.h hold for a segment as they do for a point: a triangle's distance to the segment is at least the distance from the segment to
-// any box that contains the part of the triangle in question.  The walk tests the cells that hold a and b (each end clamped into the grid): a first best.
-// If the capsule (segment, sqrt(best)) stays inside the box of a's cell -- both ends at least that far from every face of it that has grid behind it -- it
-// is done (when b lies in another cell its distance to one of those faces is negative and the test fails by itself).  Otherwise it visits top-level cells
-// in Chebyshev rings around the BOX of top-level cells the two ends span: ring 0 is that box, ring k the shell k cells around it.  The lower bound of ring
-// k is the gap from the segment's bounding box to the nearest face of the cube of rings before it that still has grid behind it.  Inside a top-level cell
-// blocks::descend_top descends while a sub-block is not beyond the best so far.  The cells of a and b and the cell tested last are skipped.
+// any box that contains the part of the triangle in question.  From closest.h the walk takes test_cell, visit_top and face_room as they are,
+// with (a, b) as the query, block_beyond below as visit_top's lower bound and the cells of a and b as its home cells.  Its own: it tests the cells that hold
+// a and b (each end clamped into the grid) for a first best; the capsule (segment, sqrt(best)) stays inside the box of a's cell when BOTH ends have
+// face_room (when b lies in another cell its distance to one of those faces is negative and the test fails by itself); the rings lie around the BOX of
+// top-level cells the two ends span: ring 0 is that box, ring k the shell k cells around it, and the lower bound of ring k is the gap from the segment's
+// bounding box to the nearest face of the cube of rings before it that still has grid behind it.
 //
 // THE LOWER BOUND of segment to block is the larger of two, each sound on its own because both shapes are convex (any axis on which their projections lie
 // apart by g proves a distance of at least g):
@@ -93,20 +93,12 @@
 
 #include "closest.h"
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define HAGRID_NOUNROLL _Pragma("nounroll")
-/// what is made from x after this line is made HERE: nothing derived from x is computed ahead of a loop and carried through it in registers
-#define HAGRID_MADE_HERE(x) asm volatile("" : "+v"(x))
-#else
-#define HAGRID_NOUNROLL
-#define HAGRID_MADE_HERE(x)
-#endif
-
 namespace hagrid {
 namespace capsule {
 
 using closest::Pair; using closest::Counts; using closest::NearList; using closest::GridConsts; using closest::CellRec;
 using closest::point_tri; using closest::segment_d2; using closest::tri_side; using closest::shrink; using closest::beyond; using closest::face;
+using closest::test_cell; using closest::visit_top; using closest::face_room;
 
 struct SegPair { float d2; vec3 q; float s; int feature; };
 
@@ -270,59 +262,12 @@ HOST DEVICE inline bool far_ends(const GridConsts& c, const vec3& a, const vec3&
              detail::fabs1(b.x) <= lim && detail::fabs1(b.y) <= lim && detail::fabs1(b.z) <= lim);
 }
 
-/// the list of one cell
-template <typename G, typename A>
-HOST DEVICE inline CellRec test_cell(const G& g, const vec3& a, const vec3& b, uint32_t index, A& l, Counts& n) {
-    const CellRec c = g.cell(index);
-    n.cells++;
-    if (c.begin >= 0) {
-        for (int i = c.begin; i < c.end; i++) {
-            const int ref = g.ref(i);
-            if (ref < 0) break;
-            n.tris++;
-            l.offer(g.tri(ref), ref, a, b);
-        }
-    }
-    return c;
-}
-
-/// one top-level cell: descend its sub-blocks while they are not beyond the best so far
-template <typename G, typename S, typename A>
-HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& a, const vec3& b, bool sat, int tx, int ty, int tz, uint32_t cell_a, uint32_t cell_b,
-                                  uint32_t& last_cell, A& l, Counts& n) {
-    const GridConsts& c = g.c;
-    auto prune = [&](int x, int y, int z, int s) {
-        const bool far = block_beyond(c, a, b, sat, x, y, z, x + (1 << s), y + (1 << s), z + (1 << s), l.d2);
-        if (far) n.pruned++;
-        return far;
-    };
-    auto leaf = [&](uint32_t ci) {
-        if (ci != cell_a && ci != cell_b && ci != last_cell) { last_cell = ci; test_cell(g, a, b, ci, l, n); }
-        return false;
-    };
-    if (prune(tx << c.shift, ty << c.shift, tz << c.shift, c.shift)) return;       // before the word is read
-    const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
-    if (!(top_w & 3u)) leaf(top_w >> 2);
-    else blocks::descend_top(g, st, top_w, tx, ty, tz, prune, leaf);
-}
-
 /// the voxel of p along one axis, p clamped into the grid
 HOST DEVICE inline int voxel1(float p, float lo, float inv, int dim) {
     float f = (p - lo) * inv;
     f = f > 0.0f ? f : 0.0f;
     f = f < float(dim - 1) ? f : float(dim - 1);
     return int(f);
-}
-
-/// smallest distance from p to the faces of cell c0's box that have grid behind them; big: there is none
-HOST DEVICE inline float face_room(const GridConsts& c, const CellRec& c0, const vec3& p, float m) {
-    if (c0.lx > 0)        m = min(m, p.x - face(c0.lx, c.cell_size.x, c.lo.x));
-    if (c0.hx < c.dims.x) m = min(m, face(c0.hx, c.cell_size.x, c.lo.x) - p.x);
-    if (c0.ly > 0)        m = min(m, p.y - face(c0.ly, c.cell_size.y, c.lo.y));
-    if (c0.hy < c.dims.y) m = min(m, face(c0.hy, c.cell_size.y, c.lo.y) - p.y);
-    if (c0.lz > 0)        m = min(m, p.z - face(c0.lz, c.cell_size.z, c.lo.z));
-    if (c0.hz < c.dims.z) m = min(m, face(c0.hz, c.cell_size.z, c.lo.z) - p.z);
-    return m;
 }
 
 /// the answer for (a, b, r) over the grid g: equal, bit for bit, to brute_force over all triangles with the same accumulator.  use_axes = false leaves (ii)
@@ -338,8 +283,8 @@ HOST DEVICE inline void segment_query(const G& g, S& st, const vec3& a, const ve
     const int bx = voxel1(b.x, c.lo.x, c.inv.x, c.dims.x), by = voxel1(b.y, c.lo.y, c.inv.y, c.dims.y), bz = voxel1(b.z, c.lo.z, c.inv.z, c.dims.z);
     const uint32_t cell_a = walk::descend(g, g.word(uint32_t((ax >> c.shift) + c.top.x * ((ay >> c.shift) + c.top.y * (az >> c.shift)))), ax, ay, az) >> 2;
     const uint32_t cell_b = walk::descend(g, g.word(uint32_t((bx >> c.shift) + c.top.x * ((by >> c.shift) + c.top.y * (bz >> c.shift)))), bx, by, bz) >> 2;
-    const CellRec c0 = test_cell(g, a, b, cell_a, l, n);
-    if (cell_b != cell_a) test_cell(g, a, b, cell_b, l, n);
+    const CellRec c0 = test_cell(g, cell_a, l, n, a, b);
+    if (cell_b != cell_a) test_cell(g, cell_b, l, n, a, b);
 
     // does the capsule (segment, sqrt(best)) stay inside the box of a's cell?  faces on the grid boundary have nothing behind them
     const float big = 3.4028234663852886e38f;
@@ -352,6 +297,8 @@ HOST DEVICE inline void segment_query(const G& g, S& st, const vec3& a, const ve
 
     // rings of top-level cells around the box of top-level cells the ends span
     const bool sat = use_axes && !far_ends(c, a, b);
+    auto far_block = [&](int lx, int ly, int lz, int hx, int hy, int hz) { return block_beyond(c, a, b, sat, lx, ly, lz, hx, hy, hz, l.d2); };
+    auto home = [cell_a, cell_b](uint32_t ci) { return ci == cell_a || ci == cell_b; };       // by value: by reference the kernel is allocated differently
     uint32_t last_cell = cell_a;
     for (int k = 0;; k++) {
         // the cube of rings 0 .. k, from the ends once more: only its six corners are carried through the ring, not the box and the ring's ranges beside them
@@ -382,7 +329,7 @@ HOST DEVICE inline void segment_query(const G& g, S& st, const vec3& a, const ve
                 const bool shell = zface || y == y0 || y == y1;             // the whole row belongs to the ring, else its two ends
                 for (int x = shell ? max(x0, 0) : x0; x <= (shell ? min(x1, c.top.x - 1) : x1); x += shell ? 1 : x1 - x0) {
                     if (x < 0 || x >= c.top.x) continue;
-                    visit_top(g, st, a, b, sat, x, y, z, cell_a, cell_b, last_cell, l, n);
+                    visit_top(g, st, far_block, home, x, y, z, last_cell, l, n, a, b);
                 }
             }
         }

@@ -53,7 +53,8 @@
 //
 // ---- the k nearest (hagrid_amd.h: hagrid_nearest_tris) --------------------------------------------------------------------------
 // trivial_query, brute_force, test_cell, visit_top and closest_query are templates over the ACCUMULATOR: what is offered every triangle
-// (offer), what a query starts from (init) and what the pruning compares with (the field d2).  Best keeps one answer; NearList<KMAX> keeps
+// (offer), what a query starts from (init) and what the pruning compares with (the field d2).  test_cell and visit_top take the QUERY as a
+// trailing pack that they hand to offer unread (p here; a, b in capsule.h), and visit_top the lower bound as a callable: one of each for every query shape.  Best keeps one answer; NearList<KMAX> keeps
 // the k <= KMAX smallest CANDIDATES in the order (d2 ascending, id ascending).  Triangle j is a candidate of a query when point_tri gives it
 // a surface, its d2 is not NaN, d2 <= r2, the pair is not skipped by the labels (the query's label is >= 0 and equals one of the triangle's
 // three) and (d2, j) sorts strictly AFTER the query's cursor.  A cursor of d2 = -1 excludes nothing (every candidate has d2 >= 0), a cursor
@@ -248,9 +249,9 @@ HOST DEVICE inline float box_lower2(const GridConsts& c, const vec3& p, int lx, 
     return dx * dx + dy * dy + dz * dz;
 }
 
-/// the list of one cell.  G: c (GridConsts), word(i), cell(i) -> CellRec, ref(i), tri(id)
-template <typename G, typename A>
-HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, A& b, Counts& n) {
+/// the list of one cell.  G: c (GridConsts), word(i), cell(i) -> CellRec, ref(i), tri(id); q...: the query as b.offer takes it
+template <typename G, typename A, typename... Q>
+HOST DEVICE inline CellRec test_cell(const G& g, uint32_t index, A& b, Counts& n, const Q&... q) {
     const CellRec c = g.cell(index);
     n.cells++;
     if (c.begin >= 0) {
@@ -258,29 +259,42 @@ HOST DEVICE inline CellRec test_cell(const G& g, const vec3& p, uint32_t index, 
             const int ref = g.ref(i);
             if (ref < 0) break;
             n.tris++;
-            b.offer(g.tri(ref), ref, p);
+            b.offer(g.tri(ref), ref, q...);
         }
     }
     return c;
 }
 
-/// one top-level cell: descend its sub-blocks (block_walk.h) while their boxes are not beyond the best so far
-template <typename G, typename S, typename A>
-HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& p, int tx, int ty, int tz, uint32_t first_cell, uint32_t& last_cell, A& b, Counts& n) {
+/// one top-level cell: descend its sub-blocks (block_walk.h) while they are not beyond the best so far.  What differs between the queries comes as two
+/// callables that capture what the query function already holds: far_block(lx, ly, lz, hx, hy, hz) -- is the block with these integer corners certainly
+/// farther than b.d2? -- and home(cell): a cell tested before the rings, not to be tested again
+template <typename G, typename S, typename FB, typename H, typename A, typename... Q>
+HOST DEVICE inline void visit_top(const G& g, S& st, FB far_block, H home, int tx, int ty, int tz, uint32_t& last_cell, A& b, Counts& n, const Q&... q) {
     const GridConsts& c = g.c;
     auto prune = [&](int x, int y, int z, int s) {
-        const bool far = beyond(box_lower2(c, p, x, y, z, x + (1 << s), y + (1 << s), z + (1 << s)), b.d2);
+        const bool far = far_block(x, y, z, x + (1 << s), y + (1 << s), z + (1 << s));
         if (far) n.pruned++;
         return far;
     };
     auto leaf = [&](uint32_t ci) {
-        if (ci != first_cell && ci != last_cell) { last_cell = ci; test_cell(g, p, ci, b, n); }
+        if (!home(ci) && ci != last_cell) { last_cell = ci; test_cell(g, ci, b, n, q...); }
         return false;
     };
     if (prune(tx << c.shift, ty << c.shift, tz << c.shift, c.shift)) return;       // before the word is read
     const uint32_t top_w = g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz)));
     if (!(top_w & 3u)) leaf(top_w >> 2);
     else blocks::descend_top(g, st, top_w, tx, ty, tz, prune, leaf);
+}
+
+/// smallest distance from p to the faces of cell c0's box that have grid behind them, and m; m still big: there is none
+HOST DEVICE inline float face_room(const GridConsts& c, const CellRec c0, const vec3& p, float m) {    // c0 by value: by reference the kernels are allocated differently
+    if (c0.lx > 0)        m = min(m, p.x - face(c0.lx, c.cell_size.x, c.lo.x));
+    if (c0.hx < c.dims.x) m = min(m, face(c0.hx, c.cell_size.x, c.lo.x) - p.x);
+    if (c0.ly > 0)        m = min(m, p.y - face(c0.ly, c.cell_size.y, c.lo.y));
+    if (c0.hy < c.dims.y) m = min(m, face(c0.hy, c.cell_size.y, c.lo.y) - p.y);
+    if (c0.lz > 0)        m = min(m, p.z - face(c0.lz, c.cell_size.z, c.lo.z));
+    if (c0.hz < c.dims.z) m = min(m, face(c0.hz, c.cell_size.z, c.lo.z) - p.z);
+    return m;
 }
 
 /// the answer for (p, r) over the grid g: equal, bit for bit, to brute_force over all triangles with the same accumulator (Best, NearList)
@@ -301,26 +315,22 @@ HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r,
 
     // its cell
     const uint32_t first_cell = walk::descend(g, g.word(uint32_t(tx + c.top.x * (ty + c.top.y * tz))), vx, vy, vz) >> 2;
-    const CellRec c0 = test_cell(g, p, first_cell, b, n);
+    const CellRec c0 = test_cell(g, first_cell, b, n, p);
 
     // does the ball (p, sqrt(best)) stay inside the cell's box?  faces on the grid boundary have nothing behind them
     {
         const float big = 3.4028234663852886e38f;
-        float m = big;
-        if (c0.lx > 0)        m = min(m, p.x - face(c0.lx, c.cell_size.x, c.lo.x));
-        if (c0.hx < c.dims.x) m = min(m, face(c0.hx, c.cell_size.x, c.lo.x) - p.x);
-        if (c0.ly > 0)        m = min(m, p.y - face(c0.ly, c.cell_size.y, c.lo.y));
-        if (c0.hy < c.dims.y) m = min(m, face(c0.hy, c.cell_size.y, c.lo.y) - p.y);
-        if (c0.lz > 0)        m = min(m, p.z - face(c0.lz, c.cell_size.z, c.lo.z));
-        if (c0.hz < c.dims.z) m = min(m, face(c0.hz, c.cell_size.z, c.lo.z) - p.z);
+        const float m = face_room(c, c0, p, big);
         if (m == big) return;                           // the cell is the whole grid
         const float ms = shrink(m, c.eps);
         if (beyond(ms * ms, b.d2)) return;
     }
 
     // rings of top-level cells around (tx, ty, tz)
+    auto far_block = [&](int lx, int ly, int lz, int hx, int hy, int hz) { return beyond(box_lower2(c, p, lx, ly, lz, hx, hy, hz), b.d2); };
+    auto home = [first_cell](uint32_t ci) { return ci == first_cell; };
     uint32_t last_cell = first_cell;
-    visit_top(g, st, p, tx, ty, tz, first_cell, last_cell, b, n);
+    visit_top(g, st, far_block, home, tx, ty, tz, last_cell, b, n, p);
     for (int k = 1;; k++) {
         // lower bound of ring k: the nearest face of the cube of rings 0 .. k-1 that still has grid behind it
         const float big = 3.4028234663852886e38f;
@@ -345,7 +355,7 @@ HOST DEVICE inline void closest_query(const G& g, S& st, const vec3& p, float r,
                 const int step = shell ? 1 : 2 * k;
                 for (int x = xa; x <= xb; x += step) {
                     if (x < 0 || x >= c.top.x) continue;
-                    visit_top(g, st, p, x, y, z, first_cell, last_cell, b, n);
+                    visit_top(g, st, far_block, home, x, y, z, last_cell, b, n, p);
                 }
             }
         }

@@ -21,8 +21,16 @@
 
 #if defined(__clang__)
 #define HAGRID_UNROLL _Pragma("unroll")
+#define HAGRID_NOUNROLL _Pragma("nounroll")
 #else
 #define HAGRID_UNROLL
+#define HAGRID_NOUNROLL
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+/// what is made from x after this line is made HERE: nothing derived from x is computed ahead of a loop and carried through it in registers
+#define HAGRID_MADE_HERE(x) asm volatile("" : "+v"(x))
+#else
+#define HAGRID_MADE_HERE(x)
 #endif
 
 namespace hagrid {

@@ -28,14 +28,9 @@
 #ifndef HAGRID_TRI_TRI_H
 #define HAGRID_TRI_TRI_H
 
+#include "multi_hit.h"
 #include "prims.h"
 #include "vec.h"
-
-#if defined(__clang__)
-#define HAGRID_NOUNROLL _Pragma("nounroll")
-#else
-#define HAGRID_NOUNROLL
-#endif
 
 namespace hagrid {
 namespace tritri {

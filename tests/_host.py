@@ -1,8 +1,10 @@
 """What the helper modules of the queries over the construction format (_closest, _overlap, _crossings, _multi_hit) share: how a host program of tests/cpp
 is built, how arrays and the grid reach it as files (tests/cpp/host_support.h reads them), and the grids of the CPU oracle they walk."""
 import os
+import re
 import struct
 import subprocess
+import sys
 
 import numpy as np
 
@@ -56,6 +58,19 @@ def oracle_grid(tris: np.ndarray, compress: bool, subset_only: bool):
     if compress:
         G.compress()
     return G
+
+
+def kernel_rows(unit: str) -> dict:
+    """tools/kernel_resources.py for one translation unit: kernel name -> (VGPRs, spilled VGPRs, scratch bytes, wavefronts per SIMD)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), unit], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = {}
+    for line in r.stdout.splitlines():
+        m = re.match(r"vgpr\s+(\d+) spill\s+(\d+) scratch\s+(\d+) .* occ (\d+)\s+.*::(\w+_kernel)\(", line)
+        if m:
+            rows[m.group(5)] = tuple(int(m.group(i)) for i in (1, 2, 3, 4))
+    print(r.stdout)
+    return rows
 
 
 def bits(a) -> np.ndarray:

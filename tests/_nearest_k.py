@@ -33,40 +33,72 @@ def entries_of(d2, ids) -> np.ndarray:
     return e
 
 
-def _batch_files(d, n, k, tris, points, cursors, query_labels, tri_labels):
-    flags = struct.pack("<iiii", n, k, 0 if cursors is None else 1, 0 if query_labels is None else 1)
+def _batch_files(d, prefix, n, k, tris, queries, cursors, query_labels, tri_labels, extra=b""):
+    flags = struct.pack("<iiii", n, k, 0 if cursors is None else 1, 0 if query_labels is None else 1) + extra
     empty = np.zeros(0, np.int32)
-    files = [_host.put(d, "nk_tris", np.ascontiguousarray(tris, dtype=np.float32)), _host.put(d, "nk_points", np.ascontiguousarray(points, dtype=np.float32)),
-             _host.put(d, "nk_cursors", empty if cursors is None else np.ascontiguousarray(cursors).view(ENTRY)),
-             _host.put(d, "nk_qlabels", empty if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)),
-             _host.put(d, "nk_tlabels", empty if query_labels is None else np.ascontiguousarray(tri_labels, dtype=np.int32))]
+    files = [_host.put(d, prefix + "tris", np.ascontiguousarray(tris, dtype=np.float32)), _host.put(d, prefix + "queries", np.ascontiguousarray(queries, dtype=np.float32)),
+             _host.put(d, prefix + "cursors", empty if cursors is None else np.ascontiguousarray(cursors).view(ENTRY)),
+             _host.put(d, prefix + "qlabels", empty if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)),
+             _host.put(d, prefix + "tlabels", empty if query_labels is None else np.ascontiguousarray(tri_labels, dtype=np.int32))]
     return flags, files
 
 
-def host_brute(exe: str, directory, tris, points, k: int, cursors=None, query_labels=None, tri_labels=None):
-    """brute_force of include/hagrid/closest.h with the k-list: (entries (n, k), records (n, k))"""
+def host_brute(exe: str, directory, tris, points, k: int, cursors=None, query_labels=None, tri_labels=None, prefix="nk_", record=scene.CLOSEST_DTYPE, extra=b""):
+    """brute_force of include/hagrid/closest.h with the k-list: (entries (n, k), records (n, k)).  prefix, record, extra: the file names, the record and the
+    parameters behind the flags of another list program (_segments)"""
     d = str(directory); n = points.shape[0]
-    flags, files = _batch_files(d, n, k, tris, points, cursors, query_labels, tri_labels)
-    par = os.path.join(d, "nk_brute_params.bin")
+    flags, files = _batch_files(d, prefix, n, k, tris, points, cursors, query_labels, tri_labels, extra)
+    par = os.path.join(d, prefix + "brute_params.bin")
     with open(par, "wb") as f:
         f.write(flags)
-    out_e, out_r = os.path.join(d, "nk_brute_entries.bin"), os.path.join(d, "nk_brute_records.bin")
+    out_e, out_r = os.path.join(d, prefix + "brute_entries.bin"), os.path.join(d, prefix + "brute_records.bin")
     subprocess.run([exe, "brute", par, *files, out_e, out_r], check=True, timeout=1200)
-    return np.fromfile(out_e, dtype=ENTRY).reshape(n, k), np.fromfile(out_r, dtype=scene.CLOSEST_DTYPE).reshape(n, k)
+    return np.fromfile(out_e, dtype=ENTRY).reshape(n, k), np.fromfile(out_r, dtype=record).reshape(n, k)
 
 
-def host_walk(exe: str, directory, grid: dict, tris, points, k: int, cursors=None, query_labels=None, tri_labels=None):
+def host_walk(exe: str, directory, grid: dict, tris, points, k: int, cursors=None, query_labels=None, tri_labels=None, prefix="nk_", record=scene.CLOSEST_DTYPE, extra=b""):
     """closest_query of include/hagrid/closest.h with the k-list over grid arrays (what api.Grid.download returns): (entries (n, k), records (n, k), per-query
     counts (n, 4) int32: cells visited, triangles tested, pruned, list full)"""
     d = str(directory); n = points.shape[0]
-    flags, files = _batch_files(d, n, k, tris, points, cursors, query_labels, tri_labels)
-    par = os.path.join(d, "nk_walk_params.bin")
+    flags, files = _batch_files(d, prefix, n, k, tris, points, cursors, query_labels, tri_labels, extra)
+    par = os.path.join(d, prefix + "walk_params.bin")
     with open(par, "wb") as f:
         f.write(_host.grid_header(grid) + flags)
-    out_e, out_r, out_c = os.path.join(d, "nk_walk_entries.bin"), os.path.join(d, "nk_walk_records.bin"), os.path.join(d, "nk_walk_counts.bin")
-    subprocess.run([exe, "walk", par, *_host.grid_files(d, grid, "nk_"), *files, out_e, out_r, out_c], check=True, timeout=1200)
-    return (np.fromfile(out_e, dtype=ENTRY).reshape(n, k), np.fromfile(out_r, dtype=scene.CLOSEST_DTYPE).reshape(n, k),
-            np.fromfile(out_c, dtype=np.int32).reshape(n, 4))
+    out_e, out_r, out_c = (os.path.join(d, prefix + "walk_" + x + ".bin") for x in ("entries", "records", "counts"))
+    subprocess.run([exe, "walk", par, *_host.grid_files(d, grid, prefix), *files, out_e, out_r, out_c], check=True, timeout=1200)
+    return (np.fromfile(out_e, dtype=ENTRY).reshape(n, k), np.fromfile(out_r, dtype=record).reshape(n, k), np.fromfile(out_c, dtype=np.int32).reshape(n, 4))
+
+
+def run_lists(launch, record, mem, grid, d_tris, d_queries, n, k, cursors=None, query_labels=None, d_query_labels=0, d_tri_labels=0, counters=False, entries=True,
+              records=True):
+    """the lists of n queries on the device through launch (api.nearest_tris, api.segment_tris): (entries (n, k), records (n, k)[, the five counters]); outputs
+    are poisoned, every slot must be written, the guard behind them must stay untouched; cursors and query labels (unless given as a device address) are
+    uploaded"""
+    import _poison as P
+    d_e = P.alloc_out(mem, 8 * n * k) if entries else 0
+    d_r = P.alloc_out(mem, 32 * n * k) if records else 0
+    d_cur = mem.upload(np.ascontiguousarray(cursors)) if cursors is not None else 0
+    d_ql = mem.upload(np.ascontiguousarray(query_labels, dtype=np.int32)) if query_labels is not None else 0
+    d_cnt = 0
+    if counters:
+        d_cnt = mem.alloc(40); mem.zero(d_cnt, 40)
+    ql = d_ql or d_query_labels
+    launch(grid, d_tris, d_queries, n, k, entries=d_e, records=d_r, cursors=d_cur, query_labels=ql, tri_labels=d_tri_labels if ql else 0, counters=d_cnt)
+    mem.synchronize()
+    e = r = None
+    if entries:
+        e = P.fetch(mem, d_e, ENTRY, n * k).reshape(n, k).copy(); mem.free(d_e)
+        P.assert_all_written(e.reshape(-1).view(np.uint64))
+    if records:
+        r = P.fetch(mem, d_r, record, n * k).reshape(n, k).copy(); mem.free(d_r)
+        P.assert_all_written(r.reshape(-1))
+    for p in (d_cur, d_ql):
+        if p:
+            mem.free(p)
+    if counters:
+        cnt = mem.download(d_cnt, np.int64, 5); mem.free(d_cnt)
+        return e, r, cnt
+    return e, r
 
 
 def words(a) -> np.ndarray:

@@ -112,16 +112,6 @@ def build_host(directory, sanitize: bool = False) -> str:
     return _host.build_host("segments_host", directory, sanitize)
 
 
-def _batch_files(d, n, k, tris, segments, cursors, query_labels, tri_labels, box_only=False):
-    flags = struct.pack("<iiiii", n, k, 0 if cursors is None else 1, 0 if query_labels is None else 1, 1 if box_only else 0)
-    empty = np.zeros(0, np.int32)
-    files = [_host.put(d, "sg_tris", np.ascontiguousarray(tris, dtype=np.float32)), _host.put(d, "sg_segments", np.ascontiguousarray(segments, dtype=np.float32)),
-             _host.put(d, "sg_cursors", empty if cursors is None else np.ascontiguousarray(cursors).view(ENTRY)),
-             _host.put(d, "sg_qlabels", empty if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)),
-             _host.put(d, "sg_tlabels", empty if query_labels is None else np.ascontiguousarray(tri_labels, dtype=np.int32))]
-    return flags, files
-
-
 def host_pairs(exe: str, directory, tris, segments) -> dict:
     """triangle i against segment i through seg_tri / tri_side of include/hagrid/capsule.h"""
     d = str(directory); n = tris.shape[0]
@@ -138,27 +128,14 @@ def host_pairs(exe: str, directory, tris, segments) -> dict:
 
 def host_brute(exe: str, directory, tris, segments, k: int, cursors=None, query_labels=None, tri_labels=None):
     """brute_force of include/hagrid/capsule.h: (entries (n, k), records (n, k))"""
-    d = str(directory); n = segments.shape[0]
-    flags, files = _batch_files(d, n, k, tris, segments, cursors, query_labels, tri_labels)
-    par = os.path.join(d, "sg_brute_params.bin")
-    with open(par, "wb") as f:
-        f.write(flags)
-    out_e, out_r = os.path.join(d, "sg_brute_entries.bin"), os.path.join(d, "sg_brute_records.bin")
-    subprocess.run([exe, "brute", par, *files, out_e, out_r], check=True, timeout=1200)
-    return np.fromfile(out_e, dtype=ENTRY).reshape(n, k), np.fromfile(out_r, dtype=RECORD).reshape(n, k)
+    return NK.host_brute(exe, directory, tris, segments, k, cursors, query_labels, tri_labels, prefix="sg_", record=RECORD, extra=struct.pack("<i", 0))
 
 
 def host_walk(exe: str, directory, grid: dict, tris, segments, k: int, cursors=None, query_labels=None, tri_labels=None, box_only=False):
     """segment_query of include/hagrid/capsule.h over grid arrays (what api.Grid.download returns): (entries (n, k), records (n, k), per-query counts
     (n, 4) int32: cells visited, triangles tested, pruned, list full).  box_only: the lower bound without its separating axes"""
-    d = str(directory); n = segments.shape[0]
-    flags, files = _batch_files(d, n, k, tris, segments, cursors, query_labels, tri_labels, box_only)
-    par = os.path.join(d, "sg_walk_params.bin")
-    with open(par, "wb") as f:
-        f.write(_host.grid_header(grid) + flags)
-    out_e, out_r, out_c = os.path.join(d, "sg_walk_entries.bin"), os.path.join(d, "sg_walk_records.bin"), os.path.join(d, "sg_walk_counts.bin")
-    subprocess.run([exe, "walk", par, *_host.grid_files(d, grid, "sg_"), *files, out_e, out_r, out_c], check=True, timeout=1200)
-    return (np.fromfile(out_e, dtype=ENTRY).reshape(n, k), np.fromfile(out_r, dtype=RECORD).reshape(n, k), np.fromfile(out_c, dtype=np.int32).reshape(n, 4))
+    return NK.host_walk(exe, directory, grid, tris, segments, k, cursors, query_labels, tri_labels, prefix="sg_", record=RECORD,
+                        extra=struct.pack("<i", 1 if box_only else 0))
 
 
 def pack_lists(entries, pages) -> dict:

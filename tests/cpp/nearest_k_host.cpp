@@ -5,69 +5,33 @@
 //
 //   nearest_k_host brute PARAMS TRIS POINTS CURSORS QLABELS TLABELS ENTRIES RECORDS
 //   nearest_k_host walk  PARAMS GRID_ENTRIES CELLS REFS TRIS POINTS CURSORS QLABELS TLABELS ENTRIES RECORDS COUNTS
-// PARAMS: (walk: the grid header of host_support.h,) i32 n, i32 k, i32 cursors given, i32 labels given.  A point is 4 f32: x, y, z, r; a cursor and an
-// entry {f32 d2, i32 id}; QLABELS n i32, TLABELS 3 i32 per triangle (files that are not given are not read).  ENTRIES: n * k entries; RECORDS: n * k
-// result records of closest_host; COUNTS: n x 4 i32 (cells visited, triangles tested, pruned, 1 = the list came back full).
-#include <string>
-#include <vector>
+// The operations, PARAMS and the files: list_host.h.  A point is 4 f32: x, y, z, r; one label per point; RECORDS: the result records of closest_host.
+#include "list_host.h"
 
-#include "hagrid/common.h"
-#include "hagrid/prims.h"
-#include "hagrid/grid.h"
-#include "hagrid/closest.h"
-#include "host_support.h"
-
-using namespace hagrid;
-using namespace host_support;
-namespace hc = hagrid::closest;
+using namespace list_host;
 
 namespace {
 
-constexpr int KMAX = 8;
-struct Point { float x, y, z, r; };
-struct Entry { float d2; int32_t id; };
-struct Result { float qx, qy, qz, d2; int32_t id, feature; float side; int32_t zero; };
-static_assert(sizeof(Point) == 16 && sizeof(Entry) == 8 && sizeof(Result) == 32, "record layout");
-
-struct Batch {
-    int n, k;
-    std::vector<Point> pts;
-    std::vector<Entry> cursors;
-    std::vector<int32_t> qlabels, tlabels;
-    std::vector<Entry> entries;
-    std::vector<Result> records;
-
-    void load(Params& p, size_t num_tris, const char* points, const char* cursor_file, const char* ql_file, const char* tl_file) {
-        n = p.get<int32_t>(); k = p.get<int32_t>();
-        const bool has_cursors = p.get<int32_t>() != 0, has_labels = p.get<int32_t>() != 0;
-        if (k < 1 || k > KMAX) { fprintf(stderr, "k must be 1 .. %d\n", KMAX); exit(2); }
-        pts = read_file<Point>(points);
-        if (has_cursors) cursors = read_file<Entry>(cursor_file);
-        if (has_labels) { qlabels = read_file<int32_t>(ql_file); tlabels = read_file<int32_t>(tl_file); }
-        if (int(pts.size()) != n || (has_cursors && int(cursors.size()) != n) || (has_labels && (int(qlabels.size()) != n || tlabels.size() != 3 * num_tris))) {
-            fprintf(stderr, "the files do not hold n points, n cursors, n query labels or 3 labels per triangle\n"); exit(2);
-        }
-        entries.resize(size_t(n) * k); records.resize(size_t(n) * k);
-    }
-    vec3 point(int i) const { return vec3(pts[i].x, pts[i].y, pts[i].z); }
-    void setup(int i, hc::NearList<KMAX>& list) const {
-        list.setup(k, cursors.empty() ? -1.0f : cursors[i].d2, cursors.empty() ? -1 : cursors[i].id, qlabels.empty() ? -1 : qlabels[i],
-                   tlabels.empty() ? nullptr : tlabels.data());
+struct Points {
+    struct Query { float x, y, z, r; };
+    typedef hc::NearList<KMAX> List;
+    enum { kLabels = 1, kBoxOnly = 0 };
+    static vec3 p(const Query& q) { return vec3(q.x, q.y, q.z); }
+    static void setup(List& l, int k, float cursor_d2, int cursor_id, const int32_t* labels, const int32_t* tri_labels) {
+        l.setup(k, cursor_d2, cursor_id, labels ? labels[0] : -1, tri_labels);
     }
     template <typename F>
-    void store(int i, const hc::NearList<KMAX>& list, F tri_at) {
-        for (int j = 0; j < k; j++) {
-            int id; float d2;
-            list.get(j, id, d2);
-            Entry& e = entries[size_t(i) * k + j];
-            e.d2 = d2; e.id = id;
-            hc::Best b;
-            hc::slot_record(tri_at, id, d2, point(i), b);
-            Result& r = records[size_t(i) * k + j];
-            r.qx = b.q.x; r.qy = b.q.y; r.qz = b.q.z; r.d2 = b.d2; r.id = b.id; r.feature = b.feature; r.side = float(b.side); r.zero = 0;
-        }
+    static void brute(F tri_at, int num_tris, const Query& q, List& l) { hc::brute_force(tri_at, num_tris, p(q), q.r, l); }
+    template <typename G, typename S>
+    static void walk(const G& g, S& st, const Query& q, List& l, hc::Counts& c, bool) { hc::closest_query(g, st, p(q), q.r, l, c); }
+    template <typename F>
+    static void record(F tri_at, int id, float d2, const Query& q, Result& r) {
+        hc::Best b;
+        hc::slot_record(tri_at, id, d2, p(q), b);
+        r.qx = b.q.x; r.qy = b.q.y; r.qz = b.q.z; r.d2 = b.d2; r.id = b.id; r.feature = b.feature; r.side = float(b.side); r.last = 0.0f;
     }
 };
+static_assert(sizeof(Points::Query) == 16, "record layout");
 
 } // namespace
 
@@ -76,41 +40,7 @@ int main(int argc, char** argv) {
     const std::string op = argv[1];
     Params p;
     p.bytes = read_file<char>(argv[2]);
-    Batch b;
-    if (op == "brute" && argc == 10) {
-        const std::vector<Tri> tris = read_file<Tri>(argv[3]);
-        b.load(p, tris.size(), argv[4], argv[5], argv[6], argv[7]);
-        const Tri* t = tris.data();
-        for (int i = 0; i < b.n; i++) {
-            hc::NearList<KMAX> list;
-            b.setup(i, list);
-            hc::brute_force([t](int j) { return t[j]; }, int(tris.size()), b.point(i), b.pts[i].r, list);
-            b.store(i, list, [t](int j) { return t[j]; });
-        }
-        write_file(argv[8], b.entries);
-        write_file(argv[9], b.records);
-    } else if (op == "walk" && argc == 14) {
-        const GridHeader h = p.get_grid_header();
-        HostGrid<kEndUnbounded> g;
-        g.load(h, argv[3], argv[4], argv[5]);
-        g.tris = read_file<Tri>(argv[6]);
-        b.load(p, g.tris.size(), argv[7], argv[8], argv[9], argv[10]);
-        std::vector<int32_t> counts(size_t(b.n) * 4);
-        hc::ArrayStack<hc::kMaxLevels> st;
-        for (int i = 0; i < b.n; i++) {
-            hc::NearList<KMAX> list;
-            hc::Counts c;
-            b.setup(i, list);
-            hc::closest_query(g, st, b.point(i), b.pts[i].r, list, c);
-            b.store(i, list, [&g](int j) { return g.tri(j); });
-            counts[size_t(i) * 4] = c.cells; counts[size_t(i) * 4 + 1] = c.tris; counts[size_t(i) * 4 + 2] = c.pruned; counts[size_t(i) * 4 + 3] = list.full() ? 1 : 0;
-        }
-        write_file(argv[11], b.entries);
-        write_file(argv[12], b.records);
-        write_file(argv[13], counts);
-    } else {
-        fprintf(stderr, "nearest_k_host: unknown operation or wrong number of files: %s\n", op.c_str());
-        return 2;
-    }
-    return 0;
+    if (run<Points>(op, p, argc, argv) == 0) return 0;
+    fprintf(stderr, "nearest_k_host: unknown operation or wrong number of files: %s\n", op.c_str());
+    return 2;
 }

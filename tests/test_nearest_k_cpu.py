@@ -267,15 +267,8 @@ def test_deep_grids_at_every_stage(deep_hosts, name):
 def test_kernel_resources_and_budget(fixture):
     """tools/kernel_resources.py closest: no scratch and no spill for both kernels, 94 VGPRs for closest_points_kernel (the template costs the existing
     query nothing); tools/count_kernels.py: at most 120 kernels"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "closest"], capture_output=True, text=True, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rows = {}
-    for line in r.stdout.splitlines():
-        m = re.match(r"vgpr\s+(\d+) spill\s+(\d+) scratch\s+(\d+) .* occ (\d+)\s+.*::(\w+_kernel)\(", line)
-        if m:
-            rows[m.group(5)] = tuple(int(m.group(i)) for i in (1, 2, 3, 4))
-    print(r.stdout)
-    assert set(rows) == {"closest_points_kernel", "nearest_tris_kernel"}, r.stdout
+    rows = _host.kernel_rows("closest")
+    assert set(rows) == {"closest_points_kernel", "nearest_tris_kernel"}, rows
     for name, (vgpr, spill, scratch, occ) in rows.items():
         assert spill == 0 and scratch == 0, (name, rows[name])
     assert rows["closest_points_kernel"][0] == 94 and rows["closest_points_kernel"][3] == 5

@@ -54,32 +54,9 @@ def case(request, fixture):
     c.mem.close()
 
 
-def run_nearest(api, mem, grid, d_tris, d_points, n, k, cursors=None, query_labels=None, d_tri_labels=0, counters=False, entries=True, records=True):
-    """the lists of n queries: (entries (n, k), records (n, k)[, the five counters]); outputs are poisoned, every slot must be written, the guard behind
-    them must stay untouched; cursors and query labels are uploaded"""
-    d_e = P.alloc_out(mem, 8 * n * k) if entries else 0
-    d_r = P.alloc_out(mem, 32 * n * k) if records else 0
-    d_cur = mem.upload(np.ascontiguousarray(cursors)) if cursors is not None else 0
-    d_ql = mem.upload(np.ascontiguousarray(query_labels, dtype=np.int32)) if query_labels is not None else 0
-    d_cnt = 0
-    if counters:
-        d_cnt = mem.alloc(40); mem.zero(d_cnt, 40)
-    api.nearest_tris(grid, d_tris, d_points, n, k, entries=d_e, records=d_r, cursors=d_cur, query_labels=d_ql, tri_labels=d_tri_labels if d_ql else 0, counters=d_cnt)
-    mem.synchronize()
-    e = r = None
-    if entries:
-        e = P.fetch(mem, d_e, NK.ENTRY, n * k).reshape(n, k).copy(); mem.free(d_e)
-        P.assert_all_written(e.reshape(-1).view(np.uint64))
-    if records:
-        r = P.fetch(mem, d_r, scene.CLOSEST_DTYPE, n * k).reshape(n, k).copy(); mem.free(d_r)
-        P.assert_all_written(r.reshape(-1))
-    for p in (d_cur, d_ql):
-        if p:
-            mem.free(p)
-    if counters:
-        cnt = mem.download(d_cnt, np.int64, 5); mem.free(d_cnt)
-        return e, r, cnt
-    return e, r
+def run_nearest(api, mem, grid, d_tris, d_points, n, k, **kw):
+    """NK.run_lists with hagrid_nearest_tris: (entries (n, k), records (n, k)[, the five counters])"""
+    return NK.run_lists(api.nearest_tris, scene.CLOSEST_DTYPE, mem, grid, d_tris, d_points, n, k, **kw)
 
 
 def want_records(c, host, compress):

@@ -359,31 +359,19 @@ def test_the_separating_axes_prune(scenes, host, scene_name):
     assert box[:, 1].mean() > tris.shape[0]
 
 
-def kernel_rows(unit):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), unit], capture_output=True, text=True, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rows = {}
-    for line in r.stdout.splitlines():
-        m = re.match(r"vgpr\s+(\d+) spill\s+(\d+) scratch\s+(\d+) .* occ (\d+)\s+.*::(\w+_kernel)\(", line)
-        if m:
-            rows[m.group(5)] = tuple(int(m.group(i)) for i in (1, 2, 3, 4))
-    print(r.stdout)
-    return rows
-
-
 def test_kernel_resources_and_budget(fixture):
     """tools/kernel_resources.py: capsule.hip holds segment_tris_kernel alone, at most 128 VGPRs, no spill, no scratch, at least 4 wavefronts per SIMD;
     closest.hip is as test_nearest_k_cpu reads it and as the parent commit built it: two kernels, closest_points_kernel at 94 VGPRs and 5 wavefronts,
     nearest_tris_kernel at 103 VGPRs; frame.hip, whose two kernels became one to pay for the new one, holds frame_kernel alone without scratch; at most
     120 kernels"""
-    rows = kernel_rows("capsule")
+    rows = _host.kernel_rows("capsule")
     assert set(rows) == {"segment_tris_kernel"}, rows
     vgpr, spill, scratch, occ = rows["segment_tris_kernel"]
     assert vgpr <= 128 and spill == 0 and scratch == 0 and occ >= 4, rows
-    rows = kernel_rows("closest")
+    rows = _host.kernel_rows("closest")
     assert set(rows) == {"closest_points_kernel", "nearest_tris_kernel"}, rows
     assert rows["closest_points_kernel"] == (94, 0, 0, 5) and rows["nearest_tris_kernel"] == (103, 0, 0, 4), rows
-    rows = kernel_rows("frame")
+    rows = _host.kernel_rows("frame")
     assert set(rows) == {"frame_kernel"} and rows["frame_kernel"][1:3] == (0, 0), rows
     c = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "count_kernels.py")], capture_output=True, text=True, cwd=ROOT)
     m = re.search(r"(\d+) kernels", c.stdout)
