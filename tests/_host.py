@@ -1,5 +1,6 @@
 """What the helper modules of the queries over the construction format (_closest, _overlap, _crossings, _multi_hit) share: how a host program of tests/cpp
-is built, how arrays and the grid reach it as files (tests/cpp/host_support.h reads them), and the grids of the CPU oracle they walk."""
+is built, how arrays and the grid reach it as files (tests/cpp/host_support.h reads them), and the grids of the CPU oracle they walk.  What the GPU test files of the same queries share
+(the case on the device, the checks around a query's launches, the shim build, the kernel budget) is tests/_gpu_case.py."""
 import os
 import re
 import struct

@@ -1,18 +1,17 @@
 """Nearest-surface queries on the GPU (hagrid_amd/csrc/closest.hip): the device's answers against the fixture tests/golden/closest.npz (the whole 32-byte
 record of every query, bit for bit) on Cell and SmallCell grids built on the device, with a traversal image present and ray binning on, before and after a
 nearest-hit launch whose hints must not move; the counters against the host walk's totals; a larger live case against the host walk; torch tensors on
-torch's stream; a MeshScene whose vertices are rewritten; edges and every argument error."""
+torch's stream; a MeshScene whose vertices are rewritten; edges and every argument error.
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import numpy as np
 import pytest
 
 import _closest as K
+import _gpu_case as G
+import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -29,14 +28,7 @@ def host(tmp_path_factory):
 @pytest.fixture(scope="module", params=K.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, the queries uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.tris = K.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, K.make_tris(request.param))
     c.queries = K.fixture_queries(c.tris)
     c.want = K.fixture_results(fixture, c.name)
     c.n = c.queries.shape[0]
@@ -45,25 +37,23 @@ def case(request, fixture):
     c.mem.close()
 
 
-def run_closest(c, grid, d_points, n, counters=False, pad=4, d_tris=None):
-    """the answers of n queries as CLOSEST_DTYPE records (and the four counters); the buffer is `pad` records longer and those must stay untouched"""
+def run_closest(c, grid, d_points, n, counters=False, d_tris=None):
+    """the answers of n queries as CLOSEST_DTYPE records (and the four counters), out of a poisoned buffer whose guard must stay untouched"""
     mem = c.mem
-    d_res = mem.alloc(32 * (n + pad))
-    mem.one(d_res, 32 * (n + pad))
+    d_res = P.alloc_out(mem, 32 * n)
     d_cnt = 0
     if counters:
         d_cnt = mem.alloc(32)
         mem.zero(d_cnt, 32)
     c.api.closest_points(grid, d_tris or c.d_tris, d_points, d_res, n, d_cnt)
     mem.synchronize()
-    got = mem.download(d_res, c.api.CLOSEST_DTYPE, n + pad)
+    got = P.fetch(mem, d_res, c.api.CLOSEST_DTYPE, n).copy()
     mem.free(d_res)
-    assert (got[n:].view(np.uint32) == 0xFFFFFFFF).all(), "written beyond num_points records"
     if counters:
         cnt = mem.download(d_cnt, np.int64, 4)
         mem.free(d_cnt)
-        return got[:n], cnt
-    return got[:n]
+        return got, cnt
+    return got
 
 
 @pytest.mark.parametrize("compress", [False, True])
@@ -79,19 +69,11 @@ def test_device_results_equal_the_fixture(case, compress):
 def test_image_and_ray_binning_are_ignored(case, compress):
     c = case; mem = c.mem
     grid = c.grids[compress]
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
-    try:
+    with G.image_present(c, grid):
         K.assert_results_equal(run_closest(c, grid, c.d_points, c.n), c.want, f"{c.name} image present")
         mem.set_ray_binning(1)
         K.assert_results_equal(run_closest(c, grid, c.d_points, c.n), c.want, f"{c.name} binning set")
-    finally:
-        mem.set_ray_binning(0)
-    assert mem.image_bytes(grid) > 0, "the query dropped the traversal image"
-    mem.set_option("traverse.image", 0)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) == 0
+    G.drop_image(c, grid)
     K.assert_results_equal(run_closest(c, grid, c.d_points, c.n), c.want, f"{c.name} traverse.image=0")
     mem.set_option("traverse.image", 2)
 
@@ -102,24 +84,8 @@ def test_no_interference_with_the_nearest_hit_path(case):
     grid = c.grids[False]
     mem.set_option("traverse.image", 2)
     api.setup_traversal(grid)
-    rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 64, 64)
-    nr = rays.shape[0]
-    d_rays = mem.upload(rays)
-    d_hits = mem.alloc(16 * nr)
-
-    def nearest():
-        mem.one(d_hits, 16 * nr)
-        api.traverse_grid(grid, c.d_tris, d_rays, d_hits, nr)
-        mem.synchronize()
-        return mem.download(d_hits, api.HIT_DTYPE, nr)
-
-    before = nearest()
-    state = mem.order_state(d_rays)
-    got = run_closest(c, grid, c.d_points, c.n)
-    assert mem.order_state(d_rays) == state, "the hints of the nearest-hit path moved"
-    after = nearest()
-    mem.free(d_hits); mem.free(d_rays)
-    assert (before.view(np.uint32) == after.view(np.uint32)).all() and (before["id"] >= 0).any()
+    with G.nearest_hit_unmoved(c, grid):
+        got = run_closest(c, grid, c.d_points, c.n)
     K.assert_results_equal(got, c.want, f"{c.name} after a nearest-hit launch")
 
 
@@ -134,12 +100,9 @@ def test_counters_equal_the_host_walk(case, host, compress):
     assert cnt.tolist() == [c.n, int(counts[:, 0].sum()), int(counts[:, 1].sum()), int(counts[:, 2].sum())]
     assert cnt[2] > 0 and cnt[3] > 0
     # the totals are ADDED: a second launch doubles them
-    mem = c.mem
-    d_res = mem.alloc(32 * c.n); d_cnt = mem.upload(cnt)
-    c.api.closest_points(grid, c.d_tris, c.d_points, d_res, c.n, d_cnt)
-    mem.synchronize()
-    assert (mem.download(d_cnt, np.int64, 4) == 2 * cnt).all()
-    mem.free(d_res); mem.free(d_cnt)
+    d_res = c.mem.alloc(32 * c.n)
+    G.assert_totals_added(lambda d_cnt: c.api.closest_points(grid, c.d_tris, c.d_points, d_res, c.n, d_cnt), c.mem, cnt)
+    c.mem.free(d_res)
 
 
 def test_edges(case):
@@ -158,14 +121,13 @@ def test_errors_leave_the_context_working(case):
     c = case; api, mem = c.api, c.mem
     grid = c.grids[False]
     L = mem._L
-    import ctypes as C
     d_res = mem.alloc(32 * c.n + 64)
     d_cnt = mem.alloc(64)
 
     def call(g, tris, points, results, n, counters=0, flags=0):
-        return L.hagrid_closest_points(mem._ctx, C.byref(g.pod) if g is not None else None, C.c_void_p(tris), C.c_void_p(points), C.c_void_p(results), n, C.c_void_p(counters), flags)
+        return L.hagrid_closest_points(mem._ctx, G.pod(g), G.vp(tris), G.vp(points), G.vp(results), n, G.vp(counters), flags)
 
-    EINVAL = -1
+    EINVAL = G.EINVAL
     assert call(grid, c.d_tris, c.d_points, d_res, c.n, d_cnt) == 0
     assert call(None, c.d_tris, c.d_points, d_res, c.n) == EINVAL
     assert call(grid, 0, c.d_points, d_res, c.n) == EINVAL and call(grid, c.d_tris, 0, d_res, c.n) == EINVAL and call(grid, c.d_tris, c.d_points, 0, c.n) == EINVAL
@@ -177,19 +139,15 @@ def test_errors_leave_the_context_working(case):
         assert call(grid, c.d_tris, c.d_points, d_res, c.n, 0, flags) == EINVAL
         assert b"flag" in L.hagrid_last_error(mem._ctx)
     assert call(grid, c.d_tris, c.d_points, d_res, -1) == EINVAL
-    assert L.hagrid_closest_points(None, C.byref(grid.pod), C.c_void_p(c.d_tris), C.c_void_p(c.d_points), C.c_void_p(d_res), c.n, None, 0) == EINVAL
+    assert L.hagrid_closest_points(None, G.pod(grid), G.vp(c.d_tris), G.vp(c.d_points), G.vp(d_res), c.n, None, 0) == EINVAL
     with pytest.raises(api.HagridError, match="aligned"):
         api.closest_points(grid, c.d_tris, c.d_points + 4, d_res, 8)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.closest_points(g2, c.d_tris, c.d_points, d_res, c.n)
-        assert call(g2, c.d_tris, c.d_points, d_res, 0) == EINVAL
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.closest_points(g2, c.d_tris, c.d_points, d_res, c.n)
+            assert call(g2, c.d_tris, c.d_points, d_res, 0) == EINVAL
     mem.free(d_res); mem.free(d_cnt)
     api.setup_traversal(grid)
     K.assert_results_equal(run_closest(c, grid, c.d_points, c.n), c.want, f"{c.name} after the refused calls")
@@ -232,9 +190,7 @@ def test_larger_live_case(tmp_path):
     q[49152:, 3] = np.float32(0.01) * diag
     q = np.ascontiguousarray(q[np.random.default_rng(5).permutation(q.shape[0])])
     n = q.shape[0]
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     d_pts = mem.upload(q)
     exe = K.build_host(tmp_path)
     for compress in (False, True):
@@ -261,7 +217,7 @@ def test_rebuild_after_vertices_were_rewritten():
     F[7] = (0, 1, V.shape[0] + 5)                                # a bad index: the degenerate triangle on vertex 0
     nt = F.shape[0]
     mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
+    c = G.Case(); c.api, c.mem = api, mem
     tV = torch.from_numpy(V).cuda(); tF = torch.from_numpy(F).cuda()
     torch.cuda.synchronize()
     ms = api.MeshScene(mem, [(tV.data_ptr(), V.shape[0], tF.data_ptr(), nt)])

@@ -3,11 +3,8 @@ tests/golden/crossing_lists.npz in CSR form with offsets from the device's own c
 binning on; the stride form; rooms that are short, long and malformed; batch tails; records null and given; the six counters against the host walk's;
 hostile rays and a larger live case against the host walk; api.crossing_lists from torch tensors; a C++ program through the shim; every argument error; the
 kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py); empty entries are compared exactly against (the bits of
-tmax, -1), slots that no ray owns against the poison."""
-import ctypes as C
-import os
-import re
-import subprocess
+tmax, -1), slots that no ray owns against the poison.
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import sys
 
 import numpy as np
@@ -15,6 +12,7 @@ import pytest
 
 import _crossing_lists as CL
 import _crossings as X
+import _gpu_case as G
 import _multi_hit as M
 import _poison as P
 from hagrid_amd import scene
@@ -22,10 +20,6 @@ from hagrid_amd import scene
 pytestmark = pytest.mark.gpu
 
 assert P.GUARD == 8 * CL.GUARD, "the guard behind the entries is CL.GUARD slots on the host and on the device"
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -42,14 +36,7 @@ def host(tmp_path_factory):
 @pytest.fixture(scope="module", params=X.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, the rays uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.tris = X.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, X.make_tris(request.param))
     c.rays = fixture[c.name + "_rays"]
     c.want_records = fixture[c.name + "_records"]
     c.lists = CL.fixture_lists(fixture, c.name)
@@ -117,21 +104,14 @@ def test_device_entries_equal_the_fixture(case, compress):
 
 
 def test_image_and_binning_are_ignored_and_survive(case):
-    c = case; mem = c.mem
+    c = case
     grid = c.grids[False]
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
     total = int(c.lists[0][-1])
     want = scene.crossing_slots(c.lists[0], total, c.lists, c.rays[:, 7])
-    try:
-        mem.set_ray_binning(1)
+    with G.image_present(c, grid, binning=True):
         got = run_lists(c, grid, c.d_rays, c.n, total, offsets=c.lists[0])
-    finally:
-        mem.set_ray_binning(0)
     CL.assert_slots(got, want, f"{c.name} image present, binning on")
     X.assert_records_equal(got["records"], c.want_records, c.name)
-    assert mem.image_bytes(grid) > 0, "the query dropped the traversal image"
 
 
 def test_stride_form(case):
@@ -202,11 +182,9 @@ def test_counters_equal_the_host_walk(case, host, compress):
     assert (got["t"] == w["t"]).all() and (got["key"] == w["key"]).all()
     X.assert_records_equal(got["records"], w["records"], f"{c.name} compress={compress} against the host walk over the device's grid")
     mem = c.mem
-    d_ent = mem.alloc(8 * cap + 8); d_off = mem.upload(offsets); d_tot = mem.upload(got["totals"])
-    c.api.list_crossings(grid, c.d_tris, c.d_rays, c.n, d_ent, cap, offsets=d_off, counters=d_tot)
-    mem.synchronize()
-    assert (mem.download(d_tot, np.int64, 6) == 2 * got["totals"]).all()
-    mem.free(d_ent); mem.free(d_off); mem.free(d_tot)
+    d_ent = mem.alloc(8 * cap + 8); d_off = mem.upload(offsets)
+    G.assert_totals_added(lambda d_tot: c.api.list_crossings(grid, c.d_tris, c.d_rays, c.n, d_ent, cap, offsets=d_off, counters=d_tot), mem, got["totals"])
+    mem.free(d_ent); mem.free(d_off)
 
 
 @pytest.mark.parametrize("scene_name", ["soup", "mesh"])
@@ -217,9 +195,7 @@ def test_hostile_rays(host, scene_name):
     from hagrid_amd import api
     exe, d = host
     tris = X.make_tris(scene_name)
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     rays, family = H.catalogue(tris, X.oracle_grid(tris, False, True), mesh=scene_name == "mesh")
     n = rays.shape[0]
     d_rays = mem.upload(rays)
@@ -251,9 +227,7 @@ def test_larger_live_case(tmp_path):
     rays = np.concatenate([scene.make_rays_primary(lo, hi, 128, 128), scene.make_rays_incoherent(lo, hi, 32768, 5), X.aimed_rays(tris, 16384, 6)]).astype(np.float32)
     rays[::7, 3] = np.float32(0.1); rays[::7, 7] = np.float32(0.9)
     rays = np.ascontiguousarray(rays[np.random.default_rng(5).permutation(n)])
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     d_rays = mem.upload(rays)
     exe = CL.build_host(tmp_path)
     grid = api.build_all(mem, c.d_tris, tris.shape[0], compress=True)
@@ -309,14 +283,8 @@ def test_crossing_lists_from_torch_tensors(fixture):
 
 
 def test_cpp_program_through_the_shim(tmp_path):
-    import torch
     import _subproc
-    hip_lib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = os.path.join(str(tmp_path), "crossing_lists_shim")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", X.INC, os.path.join(X.ROOT, "tests", "cpp", "crossing_lists_shim.cpp"),
-                    "-o", exe, "-L", os.path.join(X.ROOT, "hagrid_amd"), "-lhagrid_amd", "-L", hip_lib, "-lamdhip64",
-                    "-Wl,-rpath," + os.path.join(X.ROOT, "hagrid_amd"), "-Wl,-rpath," + hip_lib, "-Wl,--allow-shlib-undefined"], check=True)
-    r = _subproc.check([exe, "20000", "1000"], timeout=120)
+    r = _subproc.check([G.build_shim("crossing_lists", tmp_path), "20000", "1000"], timeout=120)
     sys.stdout.write(r.stdout)
     assert " 0 mismatches vs host brute force" in r.stdout and " 0 mismatches in the stride form" in r.stdout, r.stdout
 
@@ -329,14 +297,11 @@ def test_errors_leave_the_context_working(case):
     cap = 8 * n
     d_ent = mem.alloc(8 * cap + 64); d_rec = mem.alloc(16 * n + 64); d_tot = mem.alloc(64)
     d_off = mem.upload(np.arange(n + 1, dtype=np.int64) * 8)
-    EINVAL, ERANGE = -1, -4
-
-    def pod(g):
-        return C.byref(g.pod) if g is not None else None
+    EINVAL, ERANGE = G.EINVAL, G.ERANGE
+    vp = G.vp
 
     def call(g=grid, tris=c.d_tris, rays=c.d_rays, k=n, offsets=d_off, stride=0, entries=d_ent, capacity=cap, records=d_rec, counters=d_tot, flags=0, ctx=mem._ctx):
-        return L.hagrid_list_crossings(ctx, pod(g), C.c_void_p(tris), C.c_void_p(rays), k, C.c_void_p(offsets), stride, C.c_void_p(entries), capacity,
-                                       C.c_void_p(records), C.c_void_p(counters), flags)
+        return L.hagrid_list_crossings(ctx, G.pod(g), vp(tris), vp(rays), k, vp(offsets), stride, vp(entries), capacity, vp(records), vp(counters), flags)
 
     assert call() == 0 and call(offsets=0, stride=8) == 0 and call(records=0, counters=0) == 0
     # a null context, a null grid, null buffers
@@ -372,15 +337,11 @@ def test_errors_leave_the_context_working(case):
     finally:
         mem.set_option("traverse.id_is_steps", 0)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.list_crossings(g2, c.d_tris, c.d_rays, n, d_ent, cap, stride=8)
-        assert call(g=g2, k=0) == EINVAL
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.list_crossings(g2, c.d_tris, c.d_rays, n, d_ent, cap, stride=8)
+            assert call(g=g2, k=0) == EINVAL
     mem.free(d_ent); mem.free(d_rec); mem.free(d_tot); mem.free(d_off)
     total = int(c.lists[0][-1])
     got = run_lists(c, grid, c.d_rays, c.n, total, offsets=c.lists[0])
@@ -392,7 +353,4 @@ def test_kernel_budget():
     """the list mode is a mode of the one crossings kernel, not a kernel of its own"""
     from hagrid_amd import lib
     assert "hagrid_list_crossings" in lib.SIGNATURES
-    out = subprocess.run([sys.executable, os.path.join(X.ROOT, "tools", "count_kernels.py"), "-v"], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"(\d+) kernels in", out)
-    assert m and int(m.group(1)) <= 120, out[-300:]
-    assert out.count("crossings_kernel") == 1, "crossing queries are ONE kernel"
+    G.kernel_budget(G.kernel_listing(), one_each=("crossings_kernel",))         # crossing queries are ONE kernel

@@ -2,25 +2,20 @@
 grids built on the device, with a traversal image present and ray binning on, with counters null; the batch totals against the host walk's; batch tails;
 points with one and three directions under both vote rules, records null and stored; the lattice form; hostile rays against the brute force; a larger live
 case against the host walk; the signed-distance snippet from torch tensors on torch's stream; a C++ program through the shim; the crossing-count picture;
-every argument error; the kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py)."""
+every argument error; the kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py).
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import ctypes as C
-import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import _crossings as X
+import _gpu_case as G
 import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -37,14 +32,8 @@ def host(tmp_path_factory):
 @pytest.fixture(scope="module", params=X.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, the rays uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name, c.fixture = api, request.param, fixture
-    c.tris = X.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, X.make_tris(request.param))
+    c.fixture = fixture
     c.rays = fixture[c.name + "_rays"]
     c.want = fixture[c.name + "_records"]
     c.n = c.rays.shape[0]
@@ -110,18 +99,12 @@ def test_image_binning_and_null_counters(case, compress):
     """a traversal image and ray binning are ignored and survive; counters may be null (above) or given"""
     c = case; mem = c.mem
     grid = c.grids[compress]
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
-    try:
+    with G.image_present(c, grid):
         X.assert_records_equal(run_rays(c, grid, c.d_rays, c.n), c.want, f"{c.name} image present")
         mem.set_ray_binning(1)
         rec, tot = run_rays(c, grid, c.d_rays, c.n, counters=True)
         X.assert_records_equal(rec, c.want, f"{c.name} binning set, counters given")
         assert tot[0] == c.n
-    finally:
-        mem.set_ray_binning(0)
-    assert mem.image_bytes(grid) > 0, "the query dropped the traversal image"
 
 
 @pytest.mark.parametrize("compress", [False, True])
@@ -134,12 +117,9 @@ def test_batch_totals_equal_the_host_walk(case, host, compress):
     X.assert_records_equal(rec, w["records"], f"{c.name} compress={compress} against the host walk over the device's grid")
     assert tot.tolist() == w["totals"].tolist() and tot[1] > 0 and tot[2] > 0 and tot[3] > 0
     # the totals are ADDED: a second launch doubles them
-    mem = c.mem
-    d_rec = mem.alloc(16 * c.n); d_tot = mem.upload(tot)
-    c.api.count_crossings(grid, c.d_tris, c.d_rays, d_rec, c.n, d_tot)
-    mem.synchronize()
-    assert (mem.download(d_tot, np.int64, 4) == 2 * tot).all()
-    mem.free(d_rec); mem.free(d_tot)
+    d_rec = c.mem.alloc(16 * c.n)
+    G.assert_totals_added(lambda d_tot: c.api.count_crossings(grid, c.d_tris, c.d_rays, d_rec, c.n, d_tot), c.mem, tot)
+    c.mem.free(d_rec)
 
 
 def test_batch_tails(case):
@@ -157,13 +137,9 @@ def test_batch_tails(case):
 
 @pytest.fixture(scope="module")
 def solids(fixture):
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.fixture = api, fixture
-    c.tris = X.make_tris("solids")
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
+    c = G.upload_case(X.make_tris("solids"))
+    c.fixture = fixture
+    c.grids = {False: c.api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: c.api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
     c.pts = fixture["points"]
     c.d_pts = c.mem.upload(c.pts)
     yield c
@@ -235,9 +211,7 @@ def test_hostile_rays(host, scene_name):
     from hagrid_amd import api
     exe, d = host
     tris = X.make_tris(scene_name)
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     # (the oracle's grid: the same resolution; Cell and SmallCell grids have the same voxel planes, so one catalogue and one brute force serve both)
     rays, family = H.catalogue(tris, X.oracle_grid(tris, False, True), mesh=scene_name == "mesh")
     want = X.host_query(exe, d, tris, rays=rays)["records"]
@@ -265,9 +239,7 @@ def test_larger_live_case(tmp_path):
     rays = np.concatenate([scene.make_rays_primary(lo, hi, 128, 128), scene.make_rays_incoherent(lo, hi, 32768, 5), X.aimed_rays(tris, 16384, 6)]).astype(np.float32)
     rays[::7, 3] = np.float32(0.1); rays[::7, 7] = np.float32(0.9)
     rays = np.ascontiguousarray(rays[np.random.default_rng(5).permutation(n)])
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     d_rays = mem.upload(rays)
     exe = X.build_host(tmp_path)
     for compress in (False, True):
@@ -319,14 +291,8 @@ def test_signed_distance_from_torch_tensors():
 
 
 def test_cpp_program_through_the_shim(tmp_path):
-    import torch
     import _subproc
-    hip_lib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = os.path.join(str(tmp_path), "crossings_shim")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", X.INC, os.path.join(X.ROOT, "tests", "cpp", "crossings_shim.cpp"),
-                    "-o", exe, "-L", os.path.join(X.ROOT, "hagrid_amd"), "-lhagrid_amd", "-L", hip_lib, "-lamdhip64",
-                    "-Wl,-rpath," + os.path.join(X.ROOT, "hagrid_amd"), "-Wl,-rpath," + hip_lib, "-Wl,--allow-shlib-undefined"], check=True)
-    r = _subproc.check([exe, "20000", "1000"], timeout=120)
+    r = _subproc.check([G.build_shim("crossings", tmp_path), "20000", "1000"], timeout=120)
     sys.stdout.write(r.stdout)
     assert " 0 mismatches vs host brute force" in r.stdout and " 0 mismatches in the point form" in r.stdout and " 0 mismatches in the lattice form" in r.stdout, r.stdout
 
@@ -354,24 +320,20 @@ def test_errors_leave_the_context_working(case):
     n = 256
     d_rec = mem.alloc(16 * 3 * n + 64); d_in = mem.alloc(4 * n + 64); d_tot = mem.alloc(64)
     d_pts = mem.upload(np.zeros((n, 4), np.float32))
-    EINVAL, ERANGE = -1, -4
+    EINVAL, ERANGE = G.EINVAL, G.ERANGE
+    pod, vp = G.pod, G.vp
 
-    def pod(g):
-        return C.byref(g.pod) if g is not None else None
+    def floats(dirs):
+        return (C.c_float * len(dirs))(*dirs) if dirs is not None else None
 
     def rays(g, tris, r, rec, k, counters=0, flags=0):
-        return L.hagrid_count_crossings(mem._ctx, pod(g), C.c_void_p(tris), C.c_void_p(r), C.c_void_p(rec), k, C.c_void_p(counters), flags)
+        return L.hagrid_count_crossings(mem._ctx, pod(g), vp(tris), vp(r), vp(rec), k, vp(counters), flags)
 
     def points(g, tris, p, k, dirs, m, inside, rec=0, counters=0, flags=0):
-        d = (C.c_float * len(dirs))(*dirs) if dirs is not None else None
-        return L.hagrid_points_inside(mem._ctx, pod(g), C.c_void_p(tris), C.c_void_p(p), k, d, m, C.c_void_p(inside), C.c_void_p(rec), C.c_void_p(counters), flags)
+        return L.hagrid_points_inside(mem._ctx, pod(g), vp(tris), vp(p), k, floats(dirs), m, vp(inside), vp(rec), vp(counters), flags)
 
     def lattice(g, origin, size, k, inside, dirs=None, m=0, rec=0, counters=0, flags=0, tris=None):
-        o = (C.c_float * 3)(*origin) if origin is not None else None
-        s = (C.c_float * 3)(*size) if size is not None else None
-        q = (C.c_int * 3)(*k) if k is not None else None
-        d = (C.c_float * len(dirs))(*dirs) if dirs is not None else None
-        return L.hagrid_inside_lattice(mem._ctx, pod(g), C.c_void_p(c.d_tris if tris is None else tris), o, s, q, d, m, C.c_void_p(inside), C.c_void_p(rec), C.c_void_p(counters), flags)
+        return L.hagrid_inside_lattice(mem._ctx, pod(g), vp(c.d_tris if tris is None else tris), G.f3(origin), G.f3(size), G.i3(k), floats(dirs), m, vp(inside), vp(rec), vp(counters), flags)
 
     T, R = c.d_tris, c.d_rays
     assert rays(grid, T, R, d_rec, n, d_tot) == 0 and points(grid, T, d_pts, n, None, 0, d_in, d_rec, d_tot) == 0 and lattice(grid, (0, 0, 0), (1, 1, 1), (4, 4, 2), d_in, rec=d_rec) == 0
@@ -394,7 +356,7 @@ def test_errors_leave_the_context_working(case):
         assert points(grid, T, d_pts, n, None, 0, d_in, flags=flags) == EINVAL and lattice(grid, (0, 0, 0), (1, 1, 1), (2, 2, 2), d_in, flags=flags) == EINVAL
     # counts
     assert rays(grid, T, R, d_rec, -1) == EINVAL and points(grid, T, d_pts, -1, None, 0, d_in) == EINVAL
-    assert L.hagrid_count_crossings(None, pod(grid), C.c_void_p(T), C.c_void_p(R), C.c_void_p(d_rec), n, None, 0) == EINVAL
+    assert L.hagrid_count_crossings(None, pod(grid), vp(T), vp(R), vp(d_rec), n, None, 0) == EINVAL
     # directions
     one = (0.0, 0.0, 1.0)
     for m in (-1, 2, 4):
@@ -409,12 +371,7 @@ def test_errors_leave_the_context_working(case):
     assert points(grid, T, d_pts, 1 << 30, None, 0, d_in) == ERANGE and points(grid, T, d_pts, (1 << 31) - 1, one, 1, 0) == EINVAL
     assert lattice(grid, (0, 0, 0), (1, 1, 1), (1 << 10, 1 << 10, 1 << 10), d_in) == ERANGE
     # the lattice errors of hagrid_overlap_lattice
-    for k in ((0, 4, 4), (4, -1, 4), (4, 4, 0), (1 << 16, 1 << 16, 1), (1 << 11, 1 << 10, 1 << 10), (1 << 30, 1, 4)):
-        assert lattice(grid, (0, 0, 0), (1, 1, 1), k, d_in) == EINVAL, k
-    for size in ((0, 1, 1), (1, -1, 1), (1, 1, float("nan")), (float("inf"), 1, 1)):
-        assert lattice(grid, (0, 0, 0), size, (2, 2, 2), d_in) == EINVAL, size
-    assert lattice(grid, (float("nan"), 0, 0), (1, 1, 1), (2, 2, 2), d_in) == EINVAL and lattice(grid, (0, float("-inf"), 0), (1, 1, 1), (2, 2, 2), d_in) == EINVAL
-    assert lattice(grid, None, (1, 1, 1), (2, 2, 2), d_in) == EINVAL and lattice(grid, (0, 0, 0), None, (2, 2, 2), d_in) == EINVAL and lattice(grid, (0, 0, 0), (1, 1, 1), None, d_in) == EINVAL
+    G.assert_lattice_refused(lambda origin, size, k: lattice(grid, origin, size, k, d_in))
     with pytest.raises(api.HagridError, match="aligned"):
         api.count_crossings(grid, T, R + 4, d_rec, 8)
     with pytest.raises(api.HagridError, match="voxel"):
@@ -428,27 +385,19 @@ def test_errors_leave_the_context_working(case):
     finally:
         mem.set_option("traverse.id_is_steps", 0)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, T, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.count_crossings(g2, T, R, d_rec, n)
-        with pytest.raises(api.HagridError, match="released"):
-            api.points_inside(g2, T, d_pts, n, d_in)
-        with pytest.raises(api.HagridError, match="released"):
-            api.inside_lattice(g2, T, (0, 0, 0), (1, 1, 1), (2, 2, 2), d_in)
-        assert rays(g2, T, R, d_rec, 0) == EINVAL
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.count_crossings(g2, T, R, d_rec, n)
+            with pytest.raises(api.HagridError, match="released"):
+                api.points_inside(g2, T, d_pts, n, d_in)
+            with pytest.raises(api.HagridError, match="released"):
+                api.inside_lattice(g2, T, (0, 0, 0), (1, 1, 1), (2, 2, 2), d_in)
+            assert rays(g2, T, R, d_rec, 0) == EINVAL
     mem.free(d_rec); mem.free(d_in); mem.free(d_tot); mem.free(d_pts)
     api.setup_traversal(grid)
     X.assert_records_equal(run_rays(c, grid, c.d_rays, c.n), c.want, f"{c.name} after the refused calls")
 
 
 def test_kernel_budget():
-    out = subprocess.run([sys.executable, os.path.join(X.ROOT, "tools", "count_kernels.py"), "-v"], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"(\d+) kernels in", out)
-    assert m and int(m.group(1)) <= 120, out[-300:]
-    assert out.count("crossings_kernel") == 1, "crossing queries are ONE kernel"
-    assert out.count("bw_stream_kernel") == 1 and "bw_copy_kernel" not in out and "bw_triad_kernel" not in out
+    G.kernel_budget(G.kernel_listing(), one_each=("crossings_kernel", "bw_stream_kernel"), absent=("bw_copy_kernel", "bw_triad_kernel"))   # crossing queries are ONE kernel

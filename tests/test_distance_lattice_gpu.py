@@ -2,11 +2,9 @@
 Cell and SmallCell grids built on the device -- ids, d2 and records bit for bit, the records also against hagrid_closest_points on the device; a workspace
 pre-filled with zeros (the smallest key: a missing initialisation shows); task shapes (one triangle alone, every triangle's box the whole lattice, 20 000 triangles
 on 1 680 voxels); two launches with identical bits; the counters against numpy; each output null alone; every argument error; a C++ program through the shim;
-api.signed_distance_lattice against the analytic solids; the kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py)."""
+api.signed_distance_lattice against the analytic solids; the kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py).
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import ctypes as C
-import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,17 +12,13 @@ import pytest
 
 import _distance as D
 import _fill_lattice as FL
-import _host
+import _gpu_case as G
 import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
 
 SCENES = ("boxes", "soup", "mesh", "solids")
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -35,26 +29,15 @@ def fixture():
 @pytest.fixture(scope="module", params=SCENES)
 def case(request):
     """one scene of the fixture: Cell and SmallCell grids built on the device"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.tris = D.tris_of(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, D.tris_of(request.param))
     c.lattices = [lat for lat in FL.lattices(c.name, c.tris) if lat[0] in D.KEYS]
     yield c
     c.mem.close()
 
 
 def small_case(tris):
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.tris = api, np.ascontiguousarray(tris, dtype=np.float32)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grid = api.build_all(c.mem, c.d_tris, c.tris.shape[0])
+    c = G.upload_case(np.ascontiguousarray(tris, dtype=np.float32))
+    c.grid = c.api.build_all(c.mem, c.d_tris, c.tris.shape[0])
     return c
 
 
@@ -149,11 +132,9 @@ def test_each_output_may_be_null_alone_and_counters_are_added(case, fixture):
         assert_equal(got, want, f"{key}: ids={ids} d2={d2} records={records}")
     full = run_distance(c, c.grids[False], origin, size, n, band)["totals"]
     voxels = int(np.prod(n))
-    d_ws = mem.alloc(8 * voxels); d_ids = mem.alloc(4 * voxels); d_tot = mem.upload(full)
-    c.api.distance_lattice(c.grids[False], c.d_tris, origin, size, n, band, d_ws, ids=d_ids, counters=d_tot)
-    mem.synchronize()
-    assert (mem.download(d_tot, np.int64, 4) == 2 * full).all()
-    mem.free(d_ws); mem.free(d_ids); mem.free(d_tot)
+    d_ws = mem.alloc(8 * voxels); d_ids = mem.alloc(4 * voxels)
+    G.assert_totals_added(lambda d_tot: c.api.distance_lattice(c.grids[False], c.d_tris, origin, size, n, band, d_ws, ids=d_ids, counters=d_tot), mem, full)
+    mem.free(d_ws); mem.free(d_ids)
 
 
 def test_with_and_without_the_traversal_image(case, fixture):
@@ -293,14 +274,8 @@ def fixture_fill():
 
 
 def test_cpp_program_through_the_shim(tmp_path):
-    import torch
     import _subproc
-    hip_lib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = os.path.join(str(tmp_path), "distance_shim")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", _host.INC, os.path.join(_host.ROOT, "tests", "cpp", "distance_shim.cpp"),
-                    "-o", exe, "-L", os.path.join(_host.ROOT, "hagrid_amd"), "-lhagrid_amd", "-L", hip_lib, "-lamdhip64",
-                    "-Wl,-rpath," + os.path.join(_host.ROOT, "hagrid_amd"), "-Wl,-rpath," + hip_lib, "-Wl,--allow-shlib-undefined"], check=True)
-    r = _subproc.check([exe, "40"], timeout=120)
+    r = _subproc.check([G.build_shim("distance", tmp_path), "40"], timeout=120)
     sys.stdout.write(r.stdout)
     assert " 0 ids or d2 differ, 0 records differ" in r.stdout, r.stdout
 
@@ -314,23 +289,17 @@ def test_errors_leave_the_context_working(case, fixture):
     d_ws = mem.alloc(8 * voxels + 64); d_ids = mem.alloc(4 * voxels + 64); d_d2 = mem.alloc(4 * voxels + 64); d_rec = mem.alloc(32 * voxels + 64); d_tot = mem.alloc(64)
     mem.zero(d_tot, 64)
     band = float(D.band_of(size, 1.5))
-    EINVAL = -1
-    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v]) if v is not None else None
-    i3 = lambda v: (C.c_int * 3)(*[int(x) for x in v]) if v is not None else None
-
-    def pod(g):
-        return C.byref(g.pod) if g is not None else None
+    EINVAL = G.EINVAL
+    vp = G.vp
 
     def call(g=grid, tris=c.d_tris, o=origin, s=size, k=n, r=band, work=d_ws, ids=d_ids, d2=d_d2, records=d_rec, counters=d_tot, flags=0, ctx=mem._ctx):
-        return L.hagrid_distance_lattice(ctx, pod(g), C.c_void_p(tris), f3(o), f3(s), i3(k), C.c_float(r), C.c_void_p(work), C.c_void_p(ids), C.c_void_p(d2), C.c_void_p(records),
-                                         C.c_void_p(counters), flags)
+        return L.hagrid_distance_lattice(ctx, G.pod(g), vp(tris), G.f3(o), G.f3(s), G.i3(k), C.c_float(r), vp(work), vp(ids), vp(d2), vp(records), vp(counters), flags)
 
     assert call() == 0 and call(records=0, counters=0) == 0 and call(ids=0, d2=0) == 0 and call(r=0.0) == 0
     # a null context, a null grid, null buffers
     assert call(ctx=None) == EINVAL
     assert call(g=None) == EINVAL and b"grid" in L.hagrid_last_error(mem._ctx)
     assert call(tris=0) == EINVAL and b"null" in L.hagrid_last_error(mem._ctx)
-    assert call(o=None) == EINVAL and call(s=None) == EINVAL and call(k=None) == EINVAL
     # the band
     for r in (-1.0, -1e-30, np.nan, np.inf, -np.inf):
         assert call(r=r) == EINVAL and b"band" in L.hagrid_last_error(mem._ctx)
@@ -341,10 +310,9 @@ def test_errors_leave_the_context_working(case, fixture):
     assert call(ids=d_ids + 2) == EINVAL and call(d2=d_d2 + 1) == EINVAL and call(counters=d_tot + 4) == EINVAL and b"aligned" in L.hagrid_last_error(mem._ctx)
     assert call(tris=c.d_tris + 4) == EINVAL and call(records=d_rec + 8) == EINVAL and b"aligned" in L.hagrid_last_error(mem._ctx)
     assert call(ids=d_ids + 4, d2=d_d2 + 12, work=d_ws + 8, records=d_rec + 16) == 0
-    # the lattice
-    assert call(k=(0, 4, 4)) == EINVAL and call(k=(4, -1, 4)) == EINVAL and call(k=(4, 4, 0)) == EINVAL and b"voxel" in L.hagrid_last_error(mem._ctx)
-    assert call(k=(1 << 16, 1 << 16, 1)) == EINVAL and call(k=(1 << 11, 1 << 10, 1 << 10)) == EINVAL
-    assert call(s=(0.1, 0.0, 0.1)) == EINVAL and call(s=(0.1, np.inf, 0.1)) == EINVAL and call(s=(np.nan, 1, 1)) == EINVAL and call(o=(0, np.inf, 0)) == EINVAL
+    # the lattice, null arrays among its cases
+    G.assert_lattice_refused(lambda o, s, k: call(o=o, s=s, k=k))
+    assert call(k=(4, 4, 0)) == EINVAL and b"voxel" in L.hagrid_last_error(mem._ctx)
     # any flag
     for flags in (1, 2, 1 << 31):
         assert call(flags=flags) == EINVAL and b"flag" in L.hagrid_last_error(mem._ctx)
@@ -353,14 +321,10 @@ def test_errors_leave_the_context_working(case, fixture):
     with pytest.raises(api.HagridError, match="band"):
         api.distance_lattice(grid, c.d_tris, origin, size, n, -0.5, d_ws, ids=d_ids)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.distance_lattice(g2, c.d_tris, origin, size, n, band, d_ws, ids=d_ids)
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.distance_lattice(g2, c.d_tris, origin, size, n, band, d_ws, ids=d_ids)
     mem.free(d_ws); mem.free(d_ids); mem.free(d_d2); mem.free(d_rec); mem.free(d_tot)
     got = run_distance(c, grid, origin, size, n, band)
     assert_equal(got, D.fixture_records(fixture, key, 0), f"{key} after the refused calls")
@@ -370,7 +334,4 @@ def test_kernel_budget():
     """one kernel with three modes; the slot came from the two ray generators of frame.hip, now one kernel"""
     from hagrid_amd import lib
     assert "hagrid_distance_lattice" in lib.SIGNATURES
-    out = subprocess.run([sys.executable, os.path.join(_host.ROOT, "tools", "count_kernels.py"), "-v"], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"(\d+) kernels in", out)
-    assert m and int(m.group(1)) <= 120, out[-300:]
-    assert out.count("distance_kernel") == 1, "the distance lattice is ONE kernel"
+    G.kernel_budget(G.kernel_listing(), one_each=("distance_kernel",))         # the distance lattice is ONE kernel

@@ -2,11 +2,8 @@
 tests/golden/fill_lattice.npz on Cell and SmallCell grids built on the device, every axis mask and both vote rules, records and counters null and given, bit
 for bit; the counters against the host walk's; row counts around the wavefront; output and workspace at every alignment the packed stores meet; a traversal
 image present and ray binning on; one axis with a null workspace; api.solid_voxels and the snippets of INTEGRATION.md on torch's stream; a C++ program through
-the shim; every argument error; the kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py)."""
-import ctypes as C
-import os
-import re
-import subprocess
+the shim; every argument error; the kernel budget.  Every compared output comes from a poisoned, guarded buffer (tests/_poison.py).
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import sys
 
 import numpy as np
@@ -14,16 +11,13 @@ import pytest
 
 import _crossings as X
 import _fill_lattice as FL
+import _gpu_case as G
 import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
 
 WINDING = 1
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -40,14 +34,7 @@ def host(tmp_path_factory):
 @pytest.fixture(scope="module", params=FL.SCENES)
 def case(request):
     """one scene of the fixture: Cell and SmallCell grids built on the device"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.tris = FL.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, FL.make_tris(request.param))
     c.lattices = FL.lattices(c.name, c.tris)
     yield c
     c.mem.close()
@@ -144,22 +131,16 @@ def test_counters_equal_the_host_walk(case, host, compress):
         FL.assert_fill_equal(got, w, f"{key} compress={compress} against the host walk over the device's grid")
     mem = c.mem
     voxels = int(np.prod(n))
-    d_in = mem.alloc(4 * voxels); d_ws = mem.alloc(voxels); d_tot = mem.upload(got["totals"])
-    c.api.fill_lattice(grid, c.d_tris, origin, size, n, d_in, axes=6, workspace=d_ws, counters=d_tot, flags=WINDING)
-    mem.synchronize()
-    assert (mem.download(d_tot, np.int64, 5) == 2 * got["totals"]).all()
-    mem.free(d_in); mem.free(d_ws); mem.free(d_tot)
+    d_in = mem.alloc(4 * voxels); d_ws = mem.alloc(voxels)
+    G.assert_totals_added(lambda d_tot: c.api.fill_lattice(grid, c.d_tris, origin, size, n, d_in, axes=6, workspace=d_ws, counters=d_tot, flags=WINDING), mem, got["totals"])
+    mem.free(d_in); mem.free(d_ws)
 
 
 def test_row_counts_around_the_wavefront(host):
     """lattices with 1, 63, 64 and 65 rows along an axis, against the host's brute force: the tail of a wavefront writes nothing"""
-    from hagrid_amd import api
     exe, d = host
-    c = Case(); c.api = api
-    c.tris = FL.make_tris("boxes")
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    grid = api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)
+    c = G.upload_case(FL.make_tris("boxes"))
+    grid = c.api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)
     origin, size = np.float32([-0.3, -0.2, -0.1]), np.float32([0.21, 0.17, 0.19])
     for n in ((8, 8, 1), (9, 7, 1), (5, 13, 1), (1, 64, 3), (65, 1, 2), (1, 1, 130)):
         for mask, winding in ((7, True), (5, False)):
@@ -171,19 +152,12 @@ def test_row_counts_around_the_wavefront(host):
 
 
 def test_image_and_binning_are_ignored_and_survive(case, fixture):
-    c = case; mem = c.mem
+    c = case
     grid = c.grids[False]
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
     key, origin, size, n = c.lattices[0]
-    try:
-        mem.set_ray_binning(1)
+    with G.image_present(c, grid, binning=True):
         got = run_fill(c, grid, origin, size, n, 7, True)
-    finally:
-        mem.set_ray_binning(0)
     FL.assert_fill_equal(got, FL.fixture_case(fixture, key, 7, True), f"{key} image present, binning on")
-    assert mem.image_bytes(grid) > 0, "the query dropped the traversal image"
 
 
 def test_neighbours_give_the_bits_they_gave(case):
@@ -241,14 +215,8 @@ def test_solid_voxels_from_torch_tensors(fixture):
 
 
 def test_cpp_program_through_the_shim(tmp_path):
-    import torch
     import _subproc
-    hip_lib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = os.path.join(str(tmp_path), "fill_lattice_shim")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", X.INC, os.path.join(X.ROOT, "tests", "cpp", "fill_lattice_shim.cpp"),
-                    "-o", exe, "-L", os.path.join(X.ROOT, "hagrid_amd"), "-lhagrid_amd", "-L", hip_lib, "-lamdhip64",
-                    "-Wl,-rpath," + os.path.join(X.ROOT, "hagrid_amd"), "-Wl,-rpath," + hip_lib, "-Wl,--allow-shlib-undefined"], check=True)
-    r = _subproc.check([exe, "40"], timeout=120)
+    r = _subproc.check([G.build_shim("fill_lattice", tmp_path), "40"], timeout=120)
     sys.stdout.write(r.stdout)
     assert " 0 mismatches vs host fill_row, 0 records differ, 0 mismatches vs the boxes" in r.stdout, r.stdout
 
@@ -261,22 +229,17 @@ def test_errors_leave_the_context_working(case, fixture):
     voxels = int(np.prod(n))
     rows = sum(FL.row_counts(n))
     d_in = mem.alloc(4 * voxels + 64); d_ws = mem.alloc(voxels + 64); d_rec = mem.alloc(16 * rows + 64); d_tot = mem.alloc(64)
-    EINVAL = -1
-    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v]) if v is not None else None
-    i3 = lambda v: (C.c_int * 3)(*[int(x) for x in v]) if v is not None else None
-
-    def pod(g):
-        return C.byref(g.pod) if g is not None else None
+    EINVAL = G.EINVAL
+    vp = G.vp
 
     def call(g=grid, tris=c.d_tris, o=origin, s=size, k=n, axes=7, inside=d_in, work=d_ws, records=d_rec, counters=d_tot, flags=0, ctx=mem._ctx):
-        return L.hagrid_fill_lattice(ctx, pod(g), C.c_void_p(tris), f3(o), f3(s), i3(k), axes, C.c_void_p(inside), C.c_void_p(work), C.c_void_p(records), C.c_void_p(counters), flags)
+        return L.hagrid_fill_lattice(ctx, G.pod(g), vp(tris), G.f3(o), G.f3(s), G.i3(k), axes, vp(inside), vp(work), vp(records), vp(counters), flags)
 
     assert call() == 0 and call(flags=WINDING) == 0 and call(records=0, counters=0) == 0 and call(axes=4, work=0) == 0 and call(axes=0) == 0
     # a null context, a null grid, null buffers
     assert call(ctx=None) == EINVAL
     assert call(g=None) == EINVAL and b"grid" in L.hagrid_last_error(mem._ctx)
     assert call(tris=0) == EINVAL and call(inside=0) == EINVAL and b"null" in L.hagrid_last_error(mem._ctx)
-    assert call(o=None) == EINVAL and call(s=None) == EINVAL and call(k=None) == EINVAL
     # the workspace is needed with more than one axis
     for axes in (0, 3, 5, 6, 7):
         assert call(axes=axes, work=0) == EINVAL and b"workspace" in L.hagrid_last_error(mem._ctx)
@@ -287,10 +250,9 @@ def test_errors_leave_the_context_working(case, fixture):
     assert call(inside=d_in + 2) == EINVAL and call(inside=d_in + 1) == EINVAL and b"aligned" in L.hagrid_last_error(mem._ctx)
     assert call(tris=c.d_tris + 4) == EINVAL and call(records=d_rec + 8) == EINVAL and call(counters=d_tot + 4) == EINVAL and b"aligned" in L.hagrid_last_error(mem._ctx)
     assert call(inside=d_in + 4, work=d_ws + 1) == 0, "inside needs 4 bytes, the workspace none"
-    # the lattice: a count of zero is not possible
-    assert call(k=(0, 4, 4)) == EINVAL and call(k=(4, -1, 4)) == EINVAL and call(k=(4, 4, 0)) == EINVAL and b"voxel" in L.hagrid_last_error(mem._ctx)
-    assert call(k=(1 << 16, 1 << 16, 1)) == EINVAL and call(k=(1 << 11, 1 << 10, 1 << 10)) == EINVAL
-    assert call(s=(0.1, 0.0, 0.1)) == EINVAL and call(s=(0.1, np.inf, 0.1)) == EINVAL and call(s=(np.nan, 1, 1)) == EINVAL and call(o=(0, np.inf, 0)) == EINVAL
+    # the lattice: a count of zero is not possible; null arrays
+    G.assert_lattice_refused(lambda o, s, k: call(o=o, s=s, k=k))
+    assert call(k=(4, 4, 0)) == EINVAL and b"voxel" in L.hagrid_last_error(mem._ctx)
     # an unknown flag
     for flags in (2, 4, 1 << 31):
         assert call(flags=flags) == EINVAL and b"flag" in L.hagrid_last_error(mem._ctx)
@@ -306,14 +268,10 @@ def test_errors_leave_the_context_working(case, fixture):
     finally:
         mem.set_option("traverse.id_is_steps", 0)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.fill_lattice(g2, c.d_tris, origin, size, n, d_in, workspace=d_ws)
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.fill_lattice(g2, c.d_tris, origin, size, n, d_in, workspace=d_ws)
     mem.free(d_in); mem.free(d_ws); mem.free(d_rec); mem.free(d_tot)
     got = run_fill(c, grid, origin, size, n, 7, True)
     FL.assert_fill_equal(got, FL.fixture_case(fixture, key, 7, True), f"{key} after the refused calls")
@@ -321,12 +279,8 @@ def test_errors_leave_the_context_working(case, fixture):
 
 def test_overflowed_centres_vote_outside():
     """a lattice whose centres overflow float32: the rows are not admissible, have no crossings and vote 0; nothing is read or written out of bounds"""
-    from hagrid_amd import api
-    c = Case(); c.api = api
-    c.tris = FL.make_tris("boxes")
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    grid = api.build_all(c.mem, c.d_tris, c.tris.shape[0])
+    c = G.upload_case(FL.make_tris("boxes"))
+    grid = c.api.build_all(c.mem, c.d_tris, c.tris.shape[0])
     n = (3, 2, 2)
     got = run_fill(c, grid, np.float32([3e38, 0.1, 0.1]), np.float32([3e38, 0.2, 0.2]), n, 7, True)
     want = scene.fill_lattice(c.tris, np.float32([3e38, 0.1, 0.1]), np.float32([3e38, 0.2, 0.2]), n, 7, True)
@@ -340,7 +294,4 @@ def test_kernel_budget():
     """the row form is a mode of the one crossings kernel, not a kernel of its own"""
     from hagrid_amd import lib
     assert "hagrid_fill_lattice" in lib.SIGNATURES
-    out = subprocess.run([sys.executable, os.path.join(X.ROOT, "tools", "count_kernels.py"), "-v"], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"(\d+) kernels in", out)
-    assert m and int(m.group(1)) <= 120, out[-300:]
-    assert out.count("crossings_kernel") == 1, "crossing queries are ONE kernel"
+    G.kernel_budget(G.kernel_listing(), one_each=("crossings_kernel",))         # crossing queries are ONE kernel

@@ -2,13 +2,15 @@
 brute force scene.filtered_hits (ids equal, t bit-equal, no ray excepted) and against the multi-hit fixture with the filter laid over it; the null
 combinations, and no filter at all against hagrid_traverse_grid_multi bit for bit; any-hit; rays that start on their triangle; edges; every refusal;
 MeshScene.instance_masks; one deep grid and a larger live case against the filtered host walk over the downloaded grid arrays.  Outputs are poisoned and
-guarded (tests/_poison.py)."""
+guarded (tests/_poison.py).
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import _filtered as F
+import _gpu_case as G
 import _multi_hit as M
 from _poison import alloc_out, fetch
 from hagrid_amd import scene
@@ -16,23 +18,13 @@ from hagrid_amd import scene
 pytestmark = pytest.mark.gpu
 
 
-class Case:
-    pass
-
-
 @pytest.fixture(scope="module", params=F.SCENES)
 def case(request):
     """one scene of the fixture: Cell and SmallCell grids built on the device; rays, filters and triangle masks uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.inp = F.inputs(c.name)
-    c.tris, c.rays, c.n = c.inp.tris, c.inp.rays, c.inp.n
-    c.mem = api.MemManager(keep=True)
-    c.mem.set_option("traverse.image", 0)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    inp = F.inputs(request.param)
+    c = G.open_case(request.param, inp.tris)
+    c.mem.set_option("traverse.image", 0)                         # (read by setup_traversal alone: building the grids does not look at it)
+    c.inp, c.rays, c.n = inp, inp.rays, inp.n
     c.d_rays = c.mem.upload(c.rays)
     c.d_filters = c.mem.upload(c.inp.filters)
     c.d_masks = c.mem.upload(c.inp.tri_masks)
@@ -247,13 +239,10 @@ def test_errors_leave_the_context_working(case):
     finally:
         mem.set_option("traverse.id_is_steps", 0)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.traverse_grid_filtered(g2, c.d_tris, c.d_rays, d_hits, c.n, 4, c.d_filters, c.d_masks)
-    g2.free()
+    with G.released_grid(c) as g2:                                # ("traverse.image" is 2 already)
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.traverse_grid_filtered(g2, c.d_tris, c.d_rays, d_hits, c.n, 4, c.d_filters, c.d_masks)
     # the level limit of make_args: a grid sixteen levels deep
     deep = D.make_tris("s16")
     d_deep = mem.upload(deep)
@@ -290,7 +279,7 @@ def test_instance_masks():
     transforms[:, [0, 1, 2], [0, 1, 2]] = 1.0
     transforms[1, :, 3] = (0.25, 0.0, 0.125); transforms[2, :, 3] = (0.0, 0.375, -0.25)
     mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
+    c = G.Case(); c.api, c.mem = api, mem
     tv = [torch.from_numpy(v).cuda() for v in verts]
     tt = torch.from_numpy(transforms.reshape(3, 12)).cuda()
     torch.cuda.synchronize()
@@ -336,9 +325,7 @@ def test_one_deep_grid(tmp_path):
     tris = D.make_tris(name)
     rays = D.make_rays(name, tris)
     n = rays.shape[0]
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     dev = D.DeviceStages(name, api, mem, c.d_tris, tris.shape[0])
     for st in D.stages_of(name):
         D.stage_grid(dev, st)
@@ -369,9 +356,7 @@ def test_larger_live_case(tmp_path):
     rays = np.ascontiguousarray(rays[np.random.default_rng(5).permutation(rays.shape[0])])      # both kinds of rays in every wavefront
     n = rays.shape[0]
     assert n == 16384
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     d_rays = mem.upload(rays)
     masks = F.tri_masks(tris.shape[0])
     d_m = mem.upload(masks)

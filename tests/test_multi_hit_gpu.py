@@ -1,21 +1,19 @@
 """Multi-hit traversal on the GPU (hagrid_amd/csrc/trav_multi.hip): the device's lists against the fixture tests/golden/multi_hit.npz
 (ids equal, t bit-equal, no ray excepted) for every k bucket, both cell formats, with and without a traversal image, with ray binning
 switched on; barycentrics against the oracle; a larger live case against the host walk and the per-triangle brute force; edges and
-error cases; no interference with the nearest-hit path; hagrid_shade_layers against scene.shade_layers."""
+error cases; no interference with the nearest-hit path; hagrid_shade_layers against scene.shade_layers.
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import _gpu_case as G
 import _multi_hit as M
 from _poison import alloc_out, assert_all_written, fetch
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -26,14 +24,7 @@ def fixture():
 @pytest.fixture(scope="module", params=M.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, the rays uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.tris = M.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, M.make_tris(request.param))
     c.rays, c.ids, c.t = fixture[c.name + "_rays"], fixture[c.name + "_ids"], fixture[c.name + "_t"]
     c.n = c.rays.shape[0]
     c.d_rays = c.mem.upload(c.rays)
@@ -41,17 +32,15 @@ def case(request, fixture):
     c.mem.close()
 
 
-def run_multi(c, grid, d_rays, n, k, flags=0, pad=4):
-    """the lists of n rays as an (n, k) HIT_DTYPE array; the buffer is `pad` records longer and those must stay untouched"""
+def run_multi(c, grid, d_rays, n, k, flags=0):
+    """the lists of n rays as an (n, k) HIT_DTYPE array out of a poisoned buffer whose guard must stay untouched"""
     mem = c.mem
-    d_hits = mem.alloc(16 * (n * k + pad))
-    mem.one(d_hits, 16 * (n * k + pad))
+    d_hits = alloc_out(mem, 16 * n * k)
     c.api.traverse_grid_multi(grid, c.d_tris, d_rays, d_hits, n, k, flags)
     mem.synchronize()
-    got = mem.download(d_hits, c.api.HIT_DTYPE, n * k + pad)
+    got = fetch(mem, d_hits, c.api.HIT_DTYPE, n * k).copy()
     mem.free(d_hits)
-    assert (got[n * k:].view(np.uint32) == 0xFFFFFFFF).all(), "written beyond num_rays * k records"
-    return got[:n * k].reshape(n, k)
+    return got.reshape(n, k)
 
 
 def assert_lists(got, ids, t, what):
@@ -75,20 +64,13 @@ def test_device_lists_equal_the_fixture(case, compress, k):
 def test_image_and_ray_binning_are_ignored(case, compress):
     c = case; mem = c.mem
     grid = c.grids[compress]
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
-    try:
+    with G.image_present(c, grid):
         for k in (1, 4, 8):
             assert_lists(run_multi(c, grid, c.d_rays, c.n, k), c.ids, c.t, f"{c.name} image present k={k}")
         mem.set_ray_binning(1)
         for k in (2, 8):
             assert_lists(run_multi(c, grid, c.d_rays, c.n, k), c.ids, c.t, f"{c.name} binning set k={k}")
-    finally:
-        mem.set_ray_binning(0)
-    mem.set_option("traverse.image", 0)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) == 0
+    G.drop_image(c, grid)
     assert_lists(run_multi(c, grid, c.d_rays, c.n, 8), c.ids, c.t, f"{c.name} traverse.image=0")
     mem.set_option("traverse.image", 2)
 
@@ -164,16 +146,12 @@ def test_errors_leave_the_context_working(case):
     finally:
         mem.set_option("traverse.id_is_steps", 0)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.traverse_grid_multi(g2, c.d_tris, c.d_rays, d_hits, c.n, 4)
-        api.traverse_grid(g2, c.d_tris, c.d_rays, d_hits, c.n)                         # ... and still serves the nearest hit
-        mem.synchronize()
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.traverse_grid_multi(g2, c.d_tris, c.d_rays, d_hits, c.n, 4)
+            api.traverse_grid(g2, c.d_tris, c.d_rays, d_hits, c.n)                     # ... and still serves the nearest hit
+            mem.synchronize()
     mem.free(d_hits)
     assert_lists(run_multi(c, grid, c.d_rays, c.n, 8), c.ids, c.t, f"{c.name} after the refused calls")
 
@@ -183,25 +161,12 @@ def test_no_interference_with_the_nearest_hit_path(case):
     grid = c.grids[False]
     mem.set_option("traverse.image", 2)
     api.setup_traversal(grid)
-    d_hits = mem.alloc(16 * c.n)
-
-    def nearest():
-        mem.one(d_hits, 16 * c.n)
-        api.traverse_grid(grid, c.d_tris, c.d_rays, d_hits, c.n)
-        mem.synchronize()
-        return mem.download(d_hits, api.HIT_DTYPE, c.n)
-
-    before = nearest()
-    state = mem.order_state(c.d_rays)
-    got = run_multi(c, grid, c.d_rays, c.n, 8)
-    assert mem.order_state(c.d_rays) == state, "the hints of the nearest-hit path moved"
-    after = nearest()
-    mem.free(d_hits)
-    assert (before.view(np.uint32) == after.view(np.uint32)).all()
+    with G.nearest_hit_unmoved(c, grid, c.d_rays, c.n) as nearest:
+        got = run_multi(c, grid, c.d_rays, c.n, 8)
     assert_lists(got, c.ids, c.t, c.name)
     # k = 1 is not promised to equal the nearest hit (a tie in t, the scaled tmax comparison), but a ray has a nearest hit exactly when its list
     # is not empty: the first triangle the nearest-hit walk accepts was tested against the ray's own window
-    assert ((before["id"] >= 0) == (got["id"][:, 0] >= 0)).all()
+    assert ((nearest.before["id"] >= 0) == (got["id"][:, 0] >= 0)).all()
 
 
 @pytest.mark.parametrize("k,opacity", [(1, 1.0), (4, 0.5), (8, 0.3), (8, 1.0)])
@@ -238,9 +203,7 @@ def test_larger_live_case(tmp_path):
     rays = np.ascontiguousarray(rays[np.random.default_rng(5).permutation(rays.shape[0])])      # both kinds of rays in every wavefront, and among the first 1024
     n = rays.shape[0]
     assert n == 65536
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     d_rays = mem.upload(rays)
     exe = M.build_host(tmp_path)
     for compress in (False, True):

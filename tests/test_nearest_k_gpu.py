@@ -2,25 +2,21 @@
 (entries bit for bit, records against the host walk's) on Cell and SmallCell grids built on the device, into poisoned and guarded buffers, with a traversal
 image present, ray binning on and no image; no interference with the nearest-hit path; k = 1 against hagrid_closest_points in the same test; paging, ties
 and labels with device cursors and labels; api.tris_within on torch tensors; counters against the host walk; batch shapes; the deep grids at every
-stage; a live case; every argument error."""
-import ctypes as C
-
+stage; a live case; every argument error.
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import numpy as np
 import pytest
 
 import _closest as K
 import _deep_grids as D
+import _gpu_case as G
 import _nearest_k as NK
 import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ERANGE = -1, -4
-
-
-class Case:
-    pass
+EINVAL, ERANGE = G.EINVAL, G.ERANGE
 
 
 @pytest.fixture(scope="module")
@@ -37,14 +33,7 @@ def host(tmp_path_factory):
 @pytest.fixture(scope="module", params=K.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, the queries uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name = api, request.param
-    c.tris = K.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, K.make_tris(request.param))
     c.queries = K.fixture_queries(c.tris)
     c.want, c.want_pages = NK.fixture_lists(fixture, c.name)
     c.n = c.queries.shape[0]
@@ -83,19 +72,11 @@ def test_device_lists_equal_the_fixture(case, host, compress):
     """k in {1, 2, 5, 8}, entries and records, with the image present, with ray binning set, and with traverse.image = 0"""
     c = case; mem = c.mem
     grid = c.grids[compress]
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
-    try:
+    with G.image_present(c, grid):
         check_all_k(c, host, compress, "image present")
         mem.set_ray_binning(1)
         check_all_k(c, host, compress, "binning set")
-    finally:
-        mem.set_ray_binning(0)
-    assert mem.image_bytes(grid) > 0, "the query dropped the traversal image"
-    mem.set_option("traverse.image", 0)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) == 0
+    G.drop_image(c, grid)
     check_all_k(c, host, compress, "traverse.image=0")
     mem.set_option("traverse.image", 2)
     # entries alone, records alone
@@ -111,24 +92,8 @@ def test_no_interference_with_the_nearest_hit_path(case):
     grid = c.grids[False]
     mem.set_option("traverse.image", 2)
     api.setup_traversal(grid)
-    rays = scene.make_rays_primary(grid.bbox_min, grid.bbox_max, 64, 64)
-    nr = rays.shape[0]
-    d_rays = mem.upload(rays)
-    d_hits = mem.alloc(16 * nr)
-
-    def nearest():
-        mem.one(d_hits, 16 * nr)
-        api.traverse_grid(grid, c.d_tris, d_rays, d_hits, nr)
-        mem.synchronize()
-        return mem.download(d_hits, api.HIT_DTYPE, nr)
-
-    before = nearest()
-    state = mem.order_state(d_rays)
-    e, _ = run_nearest(api, mem, grid, c.d_tris, c.d_points, c.n, 8)
-    assert mem.order_state(d_rays) == state, "the hints of the nearest-hit path moved"
-    after = nearest()
-    mem.free(d_hits); mem.free(d_rays)
-    assert (before.view(np.uint32) == after.view(np.uint32)).all() and (before["id"] >= 0).any()
+    with G.nearest_hit_unmoved(c, grid):
+        e, _ = run_nearest(api, mem, grid, c.d_tris, c.d_points, c.n, 8)
     NK.assert_lists_equal(e, c.want, f"{c.name} after a nearest-hit launch")
 
 
@@ -251,11 +216,9 @@ def test_counters_equal_the_host_walk(case, host, compress):
         assert cnt.tolist() == [c.n] + [int(counts[:, j].sum()) for j in range(4)]
         assert cnt[4] == (e["id"][:, k - 1] >= 0).sum() and 0 < cnt[4] < c.n and cnt[2] > 0 and cnt[3] > 0
     # the totals are ADDED: a second launch doubles them
-    d_e = mem.alloc(8 * c.n * 8); d_cnt = mem.upload(cnt)
-    api.nearest_tris(grid, c.d_tris, c.d_points, c.n, 8, entries=d_e, counters=d_cnt)
-    mem.synchronize()
-    assert (mem.download(d_cnt, np.int64, 5) == 2 * cnt).all()
-    mem.free(d_e); mem.free(d_cnt)
+    d_e = mem.alloc(8 * c.n * 8)
+    G.assert_totals_added(lambda d_cnt: api.nearest_tris(grid, c.d_tris, c.d_points, c.n, 8, entries=d_e, counters=d_cnt), mem, cnt)
+    mem.free(d_e)
 
 
 def test_batch_shapes(case):
@@ -314,8 +277,8 @@ def test_live_case(tmp_path):
     q[n // 2:, 0:3] = K.uniform_points(lo, hi, n // 2, 12)
     q[3 * n // 4:, 3] = np.float32(0.01) * diag
     q = np.ascontiguousarray(q[np.random.default_rng(5).permutation(n)])
-    mem = api.MemManager(keep=True)
-    d_tris = mem.upload(tris); d_pts = mem.upload(q)
+    c = G.upload_case(tris); mem, d_tris = c.mem, c.d_tris
+    d_pts = mem.upload(q)
     exe = NK.build_host(tmp_path)
     for compress in (False, True):
         grid = api.build_all(mem, d_tris, tris.shape[0], compress=compress)
@@ -342,10 +305,10 @@ def test_errors_leave_the_context_working(case):
     d_e = mem.alloc(8 * n * 8 + 64); d_r = mem.alloc(32 * n * 8 + 64); d_cnt = mem.alloc(64)
     d_cur = mem.alloc(8 * n + 64); d_ql = mem.alloc(4 * n + 64); d_tl = mem.alloc(12 * c.tris.shape[0] + 64)
     mem.zero(d_cur, 8 * n + 64); mem.zero(d_ql, 4 * n + 64); mem.zero(d_tl, 12 * c.tris.shape[0] + 64)
-    vp = C.c_void_p
+    vp = G.vp
 
     def call(g=grid, tris=c.d_tris, points=c.d_points, num=n, k=8, cursors=0, ql=0, tl=0, entries=d_e, records=d_r, counters=0, flags=0):
-        return L.hagrid_nearest_tris(mem._ctx, C.byref(g.pod) if g is not None else None, vp(tris), vp(points), num, k, vp(cursors), vp(ql), vp(tl), vp(entries), vp(records),
+        return L.hagrid_nearest_tris(mem._ctx, G.pod(g), vp(tris), vp(points), num, k, vp(cursors), vp(ql), vp(tl), vp(entries), vp(records),
                                      vp(counters), flags)
 
     assert call(counters=d_cnt, cursors=d_cur, ql=d_ql, tl=d_tl) == 0
@@ -363,7 +326,7 @@ def test_errors_leave_the_context_working(case):
     assert call(ql=d_ql + 2, tl=d_tl) == EINVAL and call(ql=d_ql, tl=d_tl + 2) == EINVAL and call(counters=d_cnt + 4) == EINVAL
     assert call(num=(1 << 31) // 8 + 1, k=8) == ERANGE and call(num=2 ** 31 - 1, k=2) == ERANGE
     assert call(num=0, tris=0, points=0, entries=0, records=0) == 0
-    assert L.hagrid_nearest_tris(None, C.byref(grid.pod), vp(c.d_tris), vp(c.d_points), n, 8, None, None, None, vp(d_e), None, None, 0) == EINVAL
+    assert L.hagrid_nearest_tris(None, G.pod(grid), vp(c.d_tris), vp(c.d_points), n, 8, None, None, None, vp(d_e), None, None, 0) == EINVAL
     with pytest.raises(api.HagridError, match="aligned"):
         api.nearest_tris(grid, c.d_tris, c.d_points + 4, 8, 8, entries=d_e)
     # a grid given up for traversal has no construction format left; a bad shift
@@ -372,14 +335,11 @@ def test_errors_leave_the_context_working(case):
     g2.pod.shift = 16
     assert call(g=g2) == EINVAL and b"shift" in L.hagrid_last_error(mem._ctx)
     g2.pod.shift = shift
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.nearest_tris(g2, c.d_tris, c.d_points, n, 8, entries=d_e)
-        assert call(g=g2, num=0) == EINVAL
-    g2.free()
+    with G.released_grid(c, g2) as released:
+        if released is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.nearest_tris(g2, c.d_tris, c.d_points, n, 8, entries=d_e)
+            assert call(g=g2, num=0) == EINVAL
     for p in (d_e, d_r, d_cnt, d_cur, d_ql, d_tl):
         mem.free(p)
     api.setup_traversal(grid)

@@ -1,23 +1,19 @@
 """Box-overlap queries on the GPU (hagrid_amd/csrc/overlap.hip): the device's ids and counts against the fixture tests/golden/overlap.npz on Cell and
 SmallCell grids built on the device, for k = 1, 2, 3, 5, 8, with a traversal image present and ray binning on, with counts null; the batch totals against
 the host walk's; batch tails; ANY; the lattice form; a larger live case against the host walk; the frame loop from torch tensors on torch's stream; a C++
-program through the shim; every argument error; the kernel budget."""
-import os
-import re
-import subprocess
+program through the shim; every argument error; the kernel budget.
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import sys
 
 import numpy as np
 import pytest
 
+import _gpu_case as G
 import _overlap as V
+import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -34,14 +30,8 @@ def host(tmp_path_factory):
 @pytest.fixture(scope="module", params=V.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, the boxes uploaded"""
-    from hagrid_amd import api
-    c = Case()
-    c.api, c.name, c.fixture = api, request.param, fixture
-    c.tris = V.make_tris(c.name)
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(c.tris)
-    c.grids = {False: api.build_all(c.mem, c.d_tris, c.tris.shape[0]), True: api.build_all(c.mem, c.d_tris, c.tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
+    c = G.open_case(request.param, V.make_tris(request.param))
+    c.fixture = fixture
     c.boxes = V.scene_boxes(fixture, c.name, c.tris)
     c.sizes = fixture[c.name + "_sizes"]
     c.n = c.boxes.shape[0]
@@ -56,13 +46,11 @@ def case(request, fixture):
     c.mem.close()
 
 
-def run_overlap(c, grid, d_boxes, n, k, flags=0, counts=True, counters=False, pad=3, d_tris=None, lattice=None):
-    """(ids (n, k), counts or None[, the four batch totals]); the buffers are `pad` records longer and those must stay untouched"""
+def run_overlap(c, grid, d_boxes, n, k, flags=0, counts=True, counters=False, d_tris=None, lattice=None):
+    """(ids (n, k), counts or None[, the four batch totals]); the outputs are poisoned first and guarded"""
     mem = c.mem
-    d_ids = mem.alloc(4 * k * (n + pad) + 16); mem.one(d_ids, 4 * k * (n + pad) + 16)
-    d_cnt = 0
-    if counts:
-        d_cnt = mem.alloc(4 * (n + pad)); mem.one(d_cnt, 4 * (n + pad))
+    d_ids = P.alloc_out(mem, 4 * k * n)
+    d_cnt = P.alloc_out(mem, 4 * n) if counts else 0
     d_tot = 0
     if counters:
         d_tot = mem.alloc(32); mem.zero(d_tot, 32)
@@ -71,15 +59,11 @@ def run_overlap(c, grid, d_boxes, n, k, flags=0, counts=True, counters=False, pa
     else:
         c.api.voxelize(grid, d_tris or c.d_tris, lattice[0], lattice[1], lattice[2], k, d_ids, d_cnt, d_tot, flags)
     mem.synchronize()
-    ids = mem.download(d_ids, np.int32, k * (n + pad))
+    out = [P.fetch(mem, d_ids, np.int32, k * n).reshape(n, k).copy(), None]
     mem.free(d_ids)
-    assert (ids[k * n:] == -1).all(), "ids written beyond num_boxes * k"
-    out = [ids[:k * n].reshape(n, k), None]
     if counts:
-        cnt = mem.download(d_cnt, np.int32, n + pad)
+        out[1] = P.fetch(mem, d_cnt, np.int32, n).copy()
         mem.free(d_cnt)
-        assert (cnt[n:] == -1).all(), "counts written beyond num_boxes"
-        out[1] = cnt[:n]
     if counters:
         out.append(mem.download(d_tot, np.int64, 4))
         mem.free(d_tot)
@@ -108,19 +92,13 @@ def test_image_binning_and_null_counts(case, compress):
     c = case; mem = c.mem
     grid = c.grids[compress]
     want_ids, want_counts = V.expected(c.fixture, c.name, 5)
-    mem.set_option("traverse.image", 2)
-    c.api.setup_traversal(grid)
-    assert mem.image_bytes(grid) > 0
-    try:
+    with G.image_present(c, grid):
         ids, counts = run_overlap(c, grid, c.d_boxes, c.n, 5)
         V.assert_answers_equal(ids, counts, want_ids, want_counts, f"{c.name} image present")
         mem.set_ray_binning(1)
         ids, counts = run_overlap(c, grid, c.d_boxes, c.n, 5, counts=False)
         assert counts is None
         V.assert_answers_equal(ids, None, want_ids, None, f"{c.name} binning set, counts null")
-    finally:
-        mem.set_ray_binning(0)
-    assert mem.image_bytes(grid) > 0, "the query dropped the traversal image"
 
 
 @pytest.mark.parametrize("compress", [False, True])
@@ -136,12 +114,9 @@ def test_batch_totals_equal_the_host_walk(case, host, compress):
         assert tot.tolist() == [c.n, int(totals[:, 0].astype(np.int64).sum()), int(totals[:, 1].astype(np.int64).sum()), int(totals[:, 2].astype(np.int64).sum())]
         assert tot[1] > 0 and tot[2] > 0 and tot[3] > 0
     # the totals are ADDED: a second launch doubles them
-    mem = c.mem
-    d_ids = mem.alloc(4 * c.n); d_tot = mem.upload(tot)
-    c.api.overlap_boxes(grid, c.d_tris, c.d_boxes, c.n, 1, d_ids, 0, d_tot, c.api.OVERLAP_ANY)
-    mem.synchronize()
-    assert (mem.download(d_tot, np.int64, 4) == 2 * tot).all()
-    mem.free(d_ids); mem.free(d_tot)
+    d_ids = c.mem.alloc(4 * c.n)
+    G.assert_totals_added(lambda d_tot: c.api.overlap_boxes(grid, c.d_tris, c.d_boxes, c.n, 1, d_ids, 0, d_tot, c.api.OVERLAP_ANY), c.mem, tot)
+    c.mem.free(d_ids)
 
 
 def test_batch_tails(case):
@@ -210,9 +185,7 @@ def test_larger_live_case(tmp_path):
         f = (i // 64) % 6
         b[i, (0, 1, 2, 4, 5, 6)[f]] = -np.inf if f < 3 else np.inf
     b = np.ascontiguousarray(b[np.random.default_rng(5).permutation(n)])
-    mem = api.MemManager(keep=True)
-    c = Case(); c.api, c.mem = api, mem
-    c.d_tris = mem.upload(tris)
+    c = G.upload_case(tris); mem = c.mem
     d_boxes = mem.upload(b)
     exe = V.build_host(tmp_path)
     for compress, k in ((False, 8), (True, 2)):
@@ -283,14 +256,8 @@ def test_frame_loop_from_torch_tensors():
 
 
 def test_cpp_program_through_the_shim(tmp_path):
-    import torch
     import _subproc
-    hip_lib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = os.path.join(str(tmp_path), "overlap_shim")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", V.INC, os.path.join(V.ROOT, "tests", "cpp", "overlap_shim.cpp"),
-                    "-o", exe, "-L", os.path.join(V.ROOT, "hagrid_amd"), "-lhagrid_amd", "-L", hip_lib, "-lamdhip64",
-                    "-Wl,-rpath," + os.path.join(V.ROOT, "hagrid_amd"), "-Wl,-rpath," + hip_lib, "-Wl,--allow-shlib-undefined"], check=True)
-    r = _subproc.check([exe, "20000", "1000"], timeout=120)
+    r = _subproc.check([G.build_shim("overlap", tmp_path), "20000", "1000"], timeout=120)
     sys.stdout.write(r.stdout)
     assert " 0 mismatches vs host brute force" in r.stdout and " 0 mismatches in the lattice form" in r.stdout, r.stdout
 
@@ -299,23 +266,18 @@ def test_errors_leave_the_context_working(case):
     c = case; api, mem = c.api, c.mem
     grid = c.grids[False]
     L = mem._L
-    import ctypes as C
     d_ids = mem.alloc(4 * 8 * c.n + 64)
     d_cnt = mem.alloc(4 * c.n + 64)
     d_tot = mem.alloc(64)
-    EINVAL = -1
+    EINVAL = G.EINVAL
     ANY = api.OVERLAP_ANY
+    vp = G.vp
 
     def call(g, tris, boxes, n, k, ids, counts=0, counters=0, flags=0):
-        return L.hagrid_overlap_boxes(mem._ctx, C.byref(g.pod) if g is not None else None, C.c_void_p(tris), C.c_void_p(boxes), n, k, C.c_void_p(ids), C.c_void_p(counts),
-                                      C.c_void_p(counters), flags)
+        return L.hagrid_overlap_boxes(mem._ctx, G.pod(g), vp(tris), vp(boxes), n, k, vp(ids), vp(counts), vp(counters), flags)
 
     def lattice(g, origin, size, n, k, ids, counts=0, counters=0, flags=0, tris=None):
-        o = (C.c_float * 3)(*origin) if origin is not None else None
-        s = (C.c_float * 3)(*size) if size is not None else None
-        m = (C.c_int * 3)(*n) if n is not None else None
-        return L.hagrid_overlap_lattice(mem._ctx, C.byref(g.pod) if g is not None else None, C.c_void_p(c.d_tris if tris is None else tris), o, s, m, k, C.c_void_p(ids),
-                                        C.c_void_p(counts), C.c_void_p(counters), flags)
+        return L.hagrid_overlap_lattice(mem._ctx, G.pod(g), vp(c.d_tris if tris is None else tris), G.f3(origin), G.f3(size), G.i3(n), k, vp(ids), vp(counts), vp(counters), flags)
 
     assert call(grid, c.d_tris, c.d_boxes, c.n, 8, d_ids, d_cnt, d_tot) == 0
     assert call(None, c.d_tris, c.d_boxes, c.n, 8, d_ids) == EINVAL and b"grid" in L.hagrid_last_error(mem._ctx)
@@ -341,16 +303,10 @@ def test_errors_leave_the_context_working(case):
         assert b"flag" in L.hagrid_last_error(mem._ctx)
         assert lattice(grid, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids, flags=flags) == EINVAL
     assert call(grid, c.d_tris, c.d_boxes, -1, 8, d_ids) == EINVAL
-    assert L.hagrid_overlap_boxes(None, C.byref(grid.pod), C.c_void_p(c.d_tris), C.c_void_p(c.d_boxes), c.n, 8, C.c_void_p(d_ids), None, None, 0) == EINVAL
+    assert L.hagrid_overlap_boxes(None, G.pod(grid), vp(c.d_tris), vp(c.d_boxes), c.n, 8, vp(d_ids), None, None, 0) == EINVAL
     # the lattice: n <= 0, too many voxels, a size that is not positive and finite, an origin that is not finite, null arrays
     assert lattice(grid, (0, 0, 0), (1, 1, 1), (4, 4, 2), 1, d_ids, d_cnt) == 0
-    for n in ((0, 4, 4), (4, -1, 4), (4, 4, 0), (1 << 16, 1 << 16, 1), (1 << 11, 1 << 10, 1 << 10), (1 << 30, 1, 4)):
-        assert lattice(grid, (0, 0, 0), (1, 1, 1), n, 1, d_ids) == EINVAL, n
-    for size in ((0, 1, 1), (1, -1, 1), (1, 1, float("nan")), (float("inf"), 1, 1)):
-        assert lattice(grid, (0, 0, 0), size, (2, 2, 2), 1, d_ids) == EINVAL, size
-    assert lattice(grid, (float("nan"), 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids) == EINVAL and lattice(grid, (0, float("-inf"), 0), (1, 1, 1), (2, 2, 2), 1, d_ids) == EINVAL
-    assert lattice(grid, None, (1, 1, 1), (2, 2, 2), 1, d_ids) == EINVAL and lattice(grid, (0, 0, 0), None, (2, 2, 2), 1, d_ids) == EINVAL
-    assert lattice(grid, (0, 0, 0), (1, 1, 1), None, 1, d_ids) == EINVAL
+    G.assert_lattice_refused(lambda origin, size, n: lattice(grid, origin, size, n, 1, d_ids))
     assert lattice(None, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids) == EINVAL and lattice(grid, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, 0) == EINVAL
     assert lattice(grid, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids, tris=0) == EINVAL and lattice(grid, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids + 2) == EINVAL
     with pytest.raises(api.HagridError, match="aligned"):
@@ -358,17 +314,13 @@ def test_errors_leave_the_context_working(case):
     with pytest.raises(api.HagridError, match="voxel"):
         api.voxelize(grid, c.d_tris, (0, 0, 0), (1, 1, 1), (0, 1, 1), 1, d_ids)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.overlap_boxes(g2, c.d_tris, c.d_boxes, c.n, 8, d_ids)
-        with pytest.raises(api.HagridError, match="released"):
-            api.voxelize(g2, c.d_tris, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids)
-        assert call(g2, c.d_tris, c.d_boxes, 0, 8, d_ids) == EINVAL
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.overlap_boxes(g2, c.d_tris, c.d_boxes, c.n, 8, d_ids)
+            with pytest.raises(api.HagridError, match="released"):
+                api.voxelize(g2, c.d_tris, (0, 0, 0), (1, 1, 1), (2, 2, 2), 1, d_ids)
+            assert call(g2, c.d_tris, c.d_boxes, 0, 8, d_ids) == EINVAL
     mem.free(d_ids); mem.free(d_cnt); mem.free(d_tot)
     api.setup_traversal(grid)
     ids, counts = run_overlap(c, grid, c.d_boxes, c.n, 8)
@@ -377,7 +329,4 @@ def test_errors_leave_the_context_working(case):
 
 
 def test_kernel_budget():
-    out = subprocess.run([sys.executable, os.path.join(V.ROOT, "tools", "count_kernels.py"), "-v"], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"(\d+) kernels in", out)
-    assert m and int(m.group(1)) <= 120, out[-300:]
-    assert out.count("overlap_boxes_kernel") == 1, "box-overlap queries are ONE kernel"
+    G.kernel_budget(G.kernel_listing(), one_each=("overlap_boxes_kernel",))         # box-overlap queries are ONE kernel

@@ -2,26 +2,20 @@
 fixture tests/golden/overlap_tris.npz -- the queries of two scenes and a lattice scene whose truth is exact arithmetic -- on Cell and SmallCell grids built
 on the device, for k = 1, 2, 3, 4, 5, 8, with counts, first and labels given and null; ANY; the batch totals against the host walk's; batch tails; the scene's
 own array as queries; the frame loop of two MeshScenes from torch tensors; a C++ program through the shim; every argument error; the kernel budget.  Every
-compared output buffer is poisoned and guarded (tests/_poison.py)."""
-import ctypes as C
-import os
-import re
-import subprocess
+compared output buffer is poisoned and guarded (tests/_poison.py).
+The case and what every query's file checks around its own launches come from tests/_gpu_case.py."""
 import sys
 
 import numpy as np
 import pytest
 
+import _gpu_case as G
 import _overlap as V
 import _overlap_tris as W
 import _poison as P
 from hagrid_amd import scene
 
 pytestmark = pytest.mark.gpu
-
-
-class Case:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -35,28 +29,23 @@ def host(tmp_path_factory):
     return W.build_host(d), d
 
 
-def make_case(api, name, tris, queries, first, qlab, tlab):
-    c = Case()
-    c.api, c.name, c.tris, c.queries, c.first, c.qlab, c.tlab = api, name, tris, queries, first, qlab, tlab
+def make_case(name, tris, queries, first, qlab, tlab):
+    c = G.open_case(name, tris)
+    c.queries, c.first, c.qlab, c.tlab = queries, first, qlab, tlab
     c.n = queries.shape[0]
-    c.mem = api.MemManager(keep=True)
-    c.d_tris = c.mem.upload(tris)
     c.d_queries = c.mem.upload(queries)
     c.d_first = c.mem.upload(first) if first is not None else 0
     c.d_qlab = c.mem.upload(qlab) if qlab is not None else 0
     c.d_tlab = c.mem.upload(tlab) if tlab is not None else 0
-    c.grids = {False: api.build_all(c.mem, c.d_tris, tris.shape[0]), True: api.build_all(c.mem, c.d_tris, tris.shape[0], compress=True)}
-    assert c.grids[True].small_cells and not c.grids[False].small_cells
     return c
 
 
 @pytest.fixture(scope="module", params=W.SCENES)
 def case(request, fixture):
     """one scene of the fixture: Cell and SmallCell grids built on the device, queries, firsts and labels uploaded"""
-    from hagrid_amd import api
     tris = W.make_tris(request.param)
     q, first, qlab = W.scene_queries(fixture, request.param, tris)
-    c = make_case(api, request.param, tris, q, first, qlab, W.scene_labels(request.param, tris.shape[0]))
+    c = make_case(request.param, tris, q, first, qlab, W.scene_labels(request.param, tris.shape[0]))
     c.fixture = fixture
     gb = scene.grid_box(tris)
     for g in c.grids.values():
@@ -67,10 +56,9 @@ def case(request, fixture):
 
 @pytest.fixture(scope="module")
 def lattice_case(fixture):
-    from hagrid_amd import api
     tris, queries, _, _ = W.lattice_scene()
     assert W.array_sum(tris) + W.array_sum(queries) == int(fixture["lattice_scene_sum"])
-    c = make_case(api, "lattice", tris, queries, None, None, None)
+    c = make_case("lattice", tris, queries, None, None, None)
     c.fixture = fixture
     yield c
     c.mem.close()
@@ -163,12 +151,10 @@ def test_batch_totals_equal_the_host_walk(case, host, compress):
         assert tot.tolist() == [c.n, int(totals[:, 0].astype(np.int64).sum()), int(totals[:, 1].astype(np.int64).sum()), int(totals[:, 2].astype(np.int64).sum())]
         assert tot[1] > 0 and tot[2] > 0 and tot[3] > 0
     # the totals are ADDED: a second launch doubles them
-    mem = c.mem
-    d_ids = mem.alloc(4 * c.n); d_tot = mem.upload(tot)
-    c.api.overlap_tris(grid, c.d_tris, c.d_queries, c.n, 1, d_ids, 0, d_tot, c.api.OVERLAP_ANY, first=c.d_first, query_labels=c.d_qlab, tri_labels=c.d_tlab)
-    mem.synchronize()
-    assert (mem.download(d_tot, np.int64, 4) == 2 * tot).all()
-    mem.free(d_ids); mem.free(d_tot)
+    d_ids = c.mem.alloc(4 * c.n)
+    G.assert_totals_added(lambda d_tot: c.api.overlap_tris(grid, c.d_tris, c.d_queries, c.n, 1, d_ids, 0, d_tot, c.api.OVERLAP_ANY, first=c.d_first, query_labels=c.d_qlab,
+                                                           tri_labels=c.d_tlab), c.mem, tot)
+    c.mem.free(d_ids)
 
 
 def test_batch_tails(case):
@@ -257,14 +243,8 @@ def test_frame_loop_from_torch_tensors():
 
 
 def test_cpp_program_through_the_shim(tmp_path):
-    import torch
     import _subproc
-    hip_lib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    exe = os.path.join(str(tmp_path), "overlap_tris_shim")
-    subprocess.run(["g++", "-std=c++11", "-O2", "-ffp-contract=off", "-DHOST=", "-DDEVICE=", "-I", W.INC, os.path.join(W.ROOT, "tests", "cpp", "overlap_tris_shim.cpp"),
-                    "-o", exe, "-L", os.path.join(W.ROOT, "hagrid_amd"), "-lhagrid_amd", "-L", hip_lib, "-lamdhip64",
-                    "-Wl,-rpath," + os.path.join(W.ROOT, "hagrid_amd"), "-Wl,-rpath," + hip_lib, "-Wl,--allow-shlib-undefined"], check=True)
-    r = _subproc.check([exe, "20000", "1000"], timeout=120)
+    r = _subproc.check([G.build_shim("overlap_tris", tmp_path), "20000", "1000"], timeout=120)
     sys.stdout.write(r.stdout)
     assert " 0 mismatches vs host brute force" in r.stdout, r.stdout
 
@@ -276,12 +256,12 @@ def test_errors_leave_the_context_working(case):
     d_ids = mem.alloc(4 * 8 * c.n + 64)
     d_cnt = mem.alloc(4 * c.n + 64)
     d_tot = mem.alloc(64)
-    EINVAL = -1
+    EINVAL = G.EINVAL
     ANY = api.OVERLAP_ANY
+    vp = G.vp
 
     def call(g, tris, queries, n, k, ids, counts=0, counters=0, flags=0, first=0, qlab=0, tlab=0):
-        return L.hagrid_overlap_tris(mem._ctx, C.byref(g.pod) if g is not None else None, C.c_void_p(tris), C.c_void_p(queries), n, C.c_void_p(first), C.c_void_p(qlab),
-                                     C.c_void_p(tlab), k, C.c_void_p(ids), C.c_void_p(counts), C.c_void_p(counters), flags)
+        return L.hagrid_overlap_tris(mem._ctx, G.pod(g), vp(tris), vp(queries), n, vp(first), vp(qlab), vp(tlab), k, vp(ids), vp(counts), vp(counters), flags)
 
     assert call(grid, c.d_tris, c.d_queries, c.n, 8, d_ids, d_cnt, d_tot, first=c.d_first, qlab=c.d_qlab, tlab=c.d_tlab) == 0
     assert call(None, c.d_tris, c.d_queries, c.n, 8, d_ids) == EINVAL and b"grid" in L.hagrid_last_error(mem._ctx)
@@ -307,7 +287,7 @@ def test_errors_leave_the_context_working(case):
         assert call(grid, c.d_tris, c.d_queries, c.n, 1, d_ids, flags=flags) == EINVAL and b"flag" in L.hagrid_last_error(mem._ctx)
     assert call(grid, c.d_tris, c.d_queries, -1, 8, d_ids) == EINVAL
     assert call(grid, 0, 0, 0, 8, 0) == 0, "num_queries = 0 is fine with null buffers"
-    assert L.hagrid_overlap_tris(None, C.byref(grid.pod), C.c_void_p(c.d_tris), C.c_void_p(c.d_queries), c.n, None, None, None, 8, C.c_void_p(d_ids), None, None, 0) == EINVAL
+    assert L.hagrid_overlap_tris(None, G.pod(grid), vp(c.d_tris), vp(c.d_queries), c.n, None, None, None, 8, vp(d_ids), None, None, 0) == EINVAL
     # 16 bytes only where 16-byte stores are used: any other k writes at any int32 boundary
     mem.one(d_ids, 4 * 8 * c.n + 64)
     assert call(grid, c.d_tris, c.d_queries, c.n, 3, d_ids + 4, first=c.d_first) == 0
@@ -318,14 +298,10 @@ def test_errors_leave_the_context_working(case):
     with pytest.raises(api.HagridError, match="together"):
         api.overlap_tris(grid, c.d_tris, c.d_queries, 8, 8, d_ids, tri_labels=c.d_tlab)
     # a grid given up for traversal has no construction format left
-    g2 = api.build_all(mem, c.d_tris, c.tris.shape[0])
-    mem.set_option("traverse.image", 2)
-    api.setup_traversal(g2)
-    if mem.image_bytes(g2) > 0:
-        api.release_for_traversal(g2)
-        with pytest.raises(api.HagridError, match="released"):
-            api.overlap_tris(g2, c.d_tris, c.d_queries, c.n, 8, d_ids)
-    g2.free()
+    with G.released_grid(c) as g2:
+        if g2 is not None:
+            with pytest.raises(api.HagridError, match="released"):
+                api.overlap_tris(g2, c.d_tris, c.d_queries, c.n, 8, d_ids)
     mem.free(d_ids); mem.free(d_cnt); mem.free(d_tot)
     # the context still works: the next box query equals its fixture, and so does the next contact query
     box_fixture = np.load(V.FIXTURE)
@@ -342,7 +318,4 @@ def test_errors_leave_the_context_working(case):
 
 
 def test_kernel_budget():
-    out = subprocess.run([sys.executable, os.path.join(W.ROOT, "tools", "count_kernels.py"), "-v"], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"(\d+) kernels in", out)
-    assert m and int(m.group(1)) <= 120, out[-300:]
-    assert out.count("overlap_boxes_kernel") == 1 and "overlap_tris_kernel" not in out, "contact queries are a mode of the ONE box-overlap kernel"
+    G.kernel_budget(G.kernel_listing(), one_each=("overlap_boxes_kernel",), absent=("overlap_tris_kernel",))     # contact queries are a mode of the ONE box-overlap kernel
