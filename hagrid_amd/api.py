@@ -105,6 +105,26 @@ class MemManager:
         _check(self, self._K.hagrid_kat_scan_epoch(self._ctx, C.byref(e)), "scan_epoch")
         return int(e.value)
 
+    MEM_STATE_KEYS = ("requests", "mallocs", "slots_in_use", "tracked", "bytes_in_use", "bytes_cached")
+
+    def mem_state(self) -> dict:
+        """tests: the allocation layer's books (csrc/kat/hagrid_amd_kat.h: hagrid_kat_mem_state; "mem.fail_request" / "mem.fail_malloc" inject failures)"""
+        out = (C.c_int64 * 6)()
+        _check(self, self._K.hagrid_kat_mem_state(self._ctx, out), "mem_state")
+        return dict(zip(self.MEM_STATE_KEYS, (int(v) for v in out)))
+
+    def mem_retry(self) -> dict:
+        """tests: the retry branch of hagrid_mem_alloc (csrc/kat/hagrid_amd_kat.h: hagrid_kat_mem_retry)"""
+        out = (C.c_int64 * 4)()
+        _check(self, self._K.hagrid_kat_mem_retry(self._ctx, out), "mem_retry")
+        return dict(zip(("retries", "bytes_given_back", "cached_behind", "usage_minus_in_use_behind"), (int(v) for v in out)))
+
+    def mem_pending(self) -> tuple:
+        """tests: ("mem.fail_request", "mem.fail_malloc", "mem.fail_scan") as they stand -- 0 once they have fired"""
+        a = C.c_int32(-1); b = C.c_int32(-1); c = C.c_int32(-1)
+        _check(self, self._K.hagrid_kat_mem_pending(self._ctx, C.byref(a), C.byref(b), C.byref(c)), "mem_pending")
+        return int(a.value), int(b.value), int(c.value)
+
     def forget_hints(self):
         """dev tools: the context forgets every ray buffer it has traversed (csrc/kat/hagrid_amd_kat.h: hagrid_kat_forget_hints)"""
         _check(self, self._K.hagrid_kat_forget_hints(self._ctx), "forget_hints")

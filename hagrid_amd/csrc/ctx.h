@@ -176,6 +176,17 @@ struct hagrid_ctx {
     size_t build_arena_hint = 0;          // bytes of temporaries the last build_grid of this context asked for (build.hip: one pool buffer for all of them)
     hagrid_build_counts counts = {};      // sizes of the last construction (hagrid_get_build_counts)
 
+    // Allocation requests (ctx.hip: mem_request, device_malloc).  A REQUEST is a call of hagrid_mem_alloc, a growth of the look-back status words or one of the
+    // context's own small device buffers (ray_order.hip); an ATTEMPT is one hipMalloc.  The two countdowns are settings of the test library
+    // ("mem.fail_request", "mem.fail_malloc"; the product's hagrid_set_option refuses them): the N-th request / attempt from now fails, then the setting is 0 again.
+    // "mem.fail_scan": the N-th look-back scan from now finds its status words gone and their growth refused -- the exits behind a scan in a LATE level or
+    // iteration of a pass, which a growth alone never reaches (the words only grow at a pass's first and largest scan).
+    long long mem_requests = 0, mem_mallocs = 0;
+    // the retry branch of hagrid_mem_alloc, for hagrid_kat_mem_retry: times taken, bytes given back (usage before - after, summed), and -- right behind the last
+    // one's release -- the bytes still cached (a walk over the slots) and usage minus the bytes of the slots in use
+    long long mem_retries = 0, mem_retry_bytes = 0, mem_retry_left = 0, mem_retry_slack = 0;
+    int opt_fail_request = 0, opt_fail_malloc = 0, opt_fail_scan = 0;
+
     std::string err;
 };
 
@@ -211,6 +222,15 @@ void debug_sync(hagrid_ctx* ctx, const char* file, int line);
 #else
 #define HG_DBG(ctx) do { } while (0)
 #endif
+
+// Counts one allocation request; false when this is the request "mem.fail_request" asked to fail.
+bool mem_request(hagrid_ctx* ctx);
+// ONE hipMalloc attempt for a device buffer -- the only place device buffers come from.  nullptr when it fails (the runtime's error state is cleared: a pass that
+// answers HAGRID_ENOMEM must not leave an out-of-memory error for the next pass's hipGetLastError) or when "mem.fail_malloc" names this attempt.  No message.
+void* device_malloc(hagrid_ctx* ctx, size_t bytes);
+// A request for a device buffer that is not a pool slot (the look-back status words, the context's row scores, tile-order and binning words): one request, one
+// attempt.  A failure leaves the message of hagrid_mem_alloc in the context unless the buffer is optional (the caller goes on without it).
+void* device_request(hagrid_ctx* ctx, size_t bytes, bool optional);
 
 // pool access for the passes (typed convenience over hagrid_mem_alloc)
 template <typename T>

@@ -107,8 +107,28 @@ static void release_slot_memory(hagrid_ctx* ctx, Slot& s) {
     s.size = 0;
 }
 
+bool hagrid_impl::mem_request(hagrid_ctx* ctx) {
+    ctx->mem_requests++;
+    return !(ctx->opt_fail_request > 0 && --ctx->opt_fail_request == 0);
+}
+
+void* hagrid_impl::device_malloc(hagrid_ctx* ctx, size_t bytes) {
+    ctx->mem_mallocs++;
+    if (ctx->opt_fail_malloc > 0 && --ctx->opt_fail_malloc == 0) return nullptr;
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return p;
+}
+
+void* hagrid_impl::device_request(hagrid_ctx* ctx, size_t bytes, bool optional) {
+    void* p = mem_request(ctx) ? device_malloc(ctx, bytes) : nullptr;
+    if (!p && !optional) fail(ctx, HAGRID_ENOMEM, __FILE__, __LINE__, "hipMalloc failed");
+    return p;
+}
+
 extern "C" void* hagrid_mem_alloc(hagrid_ctx* ctx, size_t bytes) {
     if (!ctx) return nullptr;
+    if (!mem_request(ctx)) { fail(ctx, HAGRID_ENOMEM, __FILE__, __LINE__, "hipMalloc failed"); return nullptr; }
     if (bytes == 0) bytes = 4;
     bytes = (bytes + 255) & ~size_t(255);
     int fit = -1, biggest = -1, empty = -1;
@@ -127,12 +147,20 @@ extern "C" void* hagrid_mem_alloc(hagrid_ctx* ctx, size_t bytes) {
         if (idx < 0) { idx = (int)ctx->slots.size(); ctx->slots.emplace_back(); }
         Slot& s = ctx->slots[idx];
         if (s.ptr) release_slot_memory(ctx, s);
-        void* p = nullptr;
         (void)hipSetDevice(ctx->device);
-        if (hipMalloc(&p, bytes) != hipSuccess) {
+        void* p = device_malloc(ctx, bytes);
+        if (!p) {
             // give back every cached buffer and retry once
+            const size_t held = ctx->usage;
             for (auto& t : ctx->slots) if (!t.in_use && t.ptr) release_slot_memory(ctx, t);
-            if (hipMalloc(&p, bytes) != hipSuccess) { fail(ctx, HAGRID_ENOMEM, __FILE__, __LINE__, "hipMalloc failed"); return nullptr; }
+            {   // (the books of the branch: a cold path)
+                size_t cached = 0, in_use = 0;
+                for (const auto& t : ctx->slots) { if (t.in_use) in_use += t.size; else if (t.ptr) cached += t.size; }
+                ctx->mem_retries++; ctx->mem_retry_bytes += (long long)(held - ctx->usage);
+                ctx->mem_retry_left = (long long)cached; ctx->mem_retry_slack = (long long)ctx->usage - (long long)in_use;
+            }
+            p = device_malloc(ctx, bytes);
+            if (!p) { fail(ctx, HAGRID_ENOMEM, __FILE__, __LINE__, "hipMalloc failed"); return nullptr; }
         }
         s.ptr = p; s.size = bytes;
         ctx->usage += bytes;
@@ -311,14 +339,18 @@ extern "C" int hagrid_bandwidth_probe(hagrid_ctx* ctx, size_t bytes, int iters, 
 
 unsigned long long* hagrid_impl::lookback_state(hagrid_ctx* ctx, int tiles, int words_per_tile, unsigned* epoch) {
     const size_t need = size_t(tiles > 0 ? tiles : 1) * size_t(words_per_tile);
-    if (need > ctx->lb_words || ctx->lb_epoch >= (1u << 30) - 2u) {
+    const bool refuse = ctx->opt_fail_scan > 0 && --ctx->opt_fail_scan == 0;      // (tests: as if the words had to grow for this scan and the device had no room)
+    if (need > ctx->lb_words || ctx->lb_epoch >= (1u << 30) - 2u || refuse) {
         // grow (or restart the epochs): the words must start out as "never published"
         (void)hipStreamSynchronize(ctx->stream);
-        if (need > ctx->lb_words) {
+        if (need > ctx->lb_words || refuse) {
             if (ctx->lb_state) (void)hipFree(ctx->lb_state);
             ctx->lb_state = nullptr; ctx->lb_words = 0;
             const size_t words = need + need / 2 + 1024;
-            if (hipMalloc((void**)&ctx->lb_state, words * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            // (the passes answer HAGRID_ENOMEM for a scan without status words: the message is left here, as hagrid_mem_alloc leaves it)
+            if (refuse) { (void)mem_request(ctx); fail(ctx, HAGRID_ENOMEM, __FILE__, __LINE__, "hipMalloc failed"); return nullptr; }
+            ctx->lb_state = static_cast<unsigned long long*>(device_request(ctx, words * sizeof(unsigned long long), false));
+            if (!ctx->lb_state) return nullptr;
             ctx->lb_words = words;
         }
         (void)hipMemsetAsync(ctx->lb_state, 0, ctx->lb_words * sizeof(unsigned long long), ctx->stream);

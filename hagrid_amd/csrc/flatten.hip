@@ -20,20 +20,19 @@ namespace {
 
 constexpr int kFlatLevels = 3;   // (1 << Entry::LOG_DIM_BITS) - 1, flatten.cu:6
 
-// collapse_entries + compute_depths for one level; children were finished by the previous launch
-__global__ void __launch_bounds__(kBlock) collapse_and_depth(uint32_t* __restrict__ entries, int* __restrict__ depths, int first, int num) {
+// collapse_entries + compute_depths for one level; children were finished by the previous launch.  The collapsed map is a WORKING COPY (`collapsed`, every
+// word of it written here, level by level): the caller's entries are only read, so a pass that fails behind these launches leaves the grid as it was.
+__global__ void __launch_bounds__(kBlock) collapse_and_depth(const uint32_t* __restrict__ entries, uint32_t* __restrict__ collapsed, int* __restrict__ depths, int first, int num) {
     const int id = blockIdx.x * kBlock + threadIdx.x;
     if (id >= num) return;
     uint32_t e = entries[first + id];
     int d = 0;
     if (e & 3u) {
-        const uint4* p = reinterpret_cast<const uint4*>(entries + (e >> 2));   // 8-entry blocks are 32 B aligned
+        const uint4* p = reinterpret_cast<const uint4*>(collapsed + (e >> 2));   // 8-entry blocks are 32 B aligned
         const uint4 a = p[0], b = p[1];
-        if (a.x == a.y && a.x == a.z && a.x == a.w && a.x == b.x && b.x == b.y && b.x == b.z && b.x == b.w) {
-            e = a.x;
-            entries[first + id] = e;
-        }
+        if (a.x == a.y && a.x == a.z && a.x == a.w && a.x == b.x && b.x == b.y && b.x == b.z && b.x == b.w) e = a.x;
     }
+    collapsed[first + id] = e;
     if (e & 3u) {
         const int4* q = reinterpret_cast<const int4*>(depths + (e >> 2));
         const int4 a = q[0], b = q[1];
@@ -95,21 +94,24 @@ extern "C" int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
     HG_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int shift = grid->shift, num_entries = grid->num_entries;
-    uint32_t* entries = static_cast<uint32_t*>(grid->entries);
+    const uint32_t* entries = static_cast<const uint32_t*>(grid->entries);
     auto first_of = [&](int i) { return i > 0 ? grid->offsets[i - 1] : 0; };
 
     int* depths = pool_alloc<int>(ctx, size_t(num_entries) + 8);
     int* start = pool_alloc<int>(ctx, size_t(num_entries) + 8);
+    uint32_t* collapsed = pool_alloc<uint32_t>(ctx, size_t(num_entries) + 8);      // the voxel map with its uniform subtrees collapsed (flatten.cu:115-124 does it in place)
     int max_level = 0;
     for (int i = 0; i <= shift; i++) max_level = std::max(max_level, grid->offsets[i] - first_of(i));
     int* partials = pool_alloc<int>(ctx, size_t(scan_num_tiles(max_level)) + 1);
-    auto release = [&]() { hagrid_mem_free(ctx, depths); hagrid_mem_free(ctx, start); hagrid_mem_free(ctx, partials); };
-    if (!depths || !start || !partials) { release(); return HAGRID_ENOMEM; }
+    auto release = [&]() { hagrid_mem_free(ctx, depths); hagrid_mem_free(ctx, start); hagrid_mem_free(ctx, partials); hagrid_mem_free(ctx, collapsed); };
+    if (!depths || !start || !partials || !collapsed) { release(); return HAGRID_ENOMEM; }
+    // (words no level covers -- none in a map of build_grid -- are taken over as they are)
+    if (grid->offsets[shift] != num_entries) (void)hipMemcpyAsync(collapsed, entries, size_t(num_entries) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);      // (errors surface at the final check)
 
     // collapse + depths, deepest level first (flatten.cu:115-124)
     for (int i = shift; i >= 0; i--) {
         const int first = first_of(i), num = grid->offsets[i] - first;
-        if (num > 0) collapse_and_depth<<<grid_blocks(num, kBlock), kBlock, 0, st>>>(entries, depths, first, num);
+        if (num > 0) collapse_and_depth<<<grid_blocks(num, kBlock), kBlock, 0, st>>>(entries, collapsed, depths, first, num);
     }
     // insertion position of every flattened block (flatten.cu:127-141): the scans of levels 0, 3, 6, ... chain
     // through a device carry initialised with the number of top-level entries
@@ -129,11 +131,11 @@ extern "C" int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
 
     uint32_t* out = pool_alloc<uint32_t>(ctx, size_t(total_entries));
     if (!out) { release(); return HAGRID_ENOMEM; }
-    copy_top<<<grid_blocks(top_entries, kBlock), kBlock, 0, st>>>(entries, start, depths, out, top_entries); HG_DBG(ctx);
+    copy_top<<<grid_blocks(top_entries, kBlock), kBlock, 0, st>>>(collapsed, start, depths, out, top_entries); HG_DBG(ctx);
     int new_offsets[HAGRID_MAX_LEVELS], num_new = 0;
     for (int i = 0, g = 0; i < shift; i += kFlatLevels, g++) {
         const int first = first_of(i), num = grid->offsets[i] - first;
-        if (num > 0) flatten_level<<<grid_blocks(num, kWaves), kBlock, 0, st>>>(entries, start, depths, out, first, num);
+        if (num > 0) flatten_level<<<grid_blocks(num, kWaves), kBlock, 0, st>>>(collapsed, start, depths, out, first, num);
         new_offsets[num_new++] = h[g];          // level_offsets[i]
     }
     new_offsets[num_new++] = total_entries;
@@ -141,7 +143,7 @@ extern "C" int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { release(); hagrid_mem_free(ctx, out); HG_FAIL(ctx, HAGRID_EHIP, hipGetErrorString(e)); }
     release();
-    hagrid_mem_free(ctx, entries);               // flatten.cu:168-170
+    hagrid_mem_free(ctx, grid->entries);         // flatten.cu:168-170
     ctx->counts.flatten_entries_in = num_entries; ctx->counts.flatten_entries_out = total_entries;
     grid->entries = out;
     grid->num_entries = total_entries;

@@ -90,8 +90,27 @@ int hagrid_kat_image_records(hagrid_ctx* ctx, const hagrid_grid* grid, const int
  *                        all-cells passes -- by default in iteration 18, where nothing grows any more; a small value puts the switch where cells still grow.
  *                        Never above 48: the lists' lengths live in 48 words of the context's scratch
  *   "scan.epoch"         the epoch of the look-back scans' status words (0 .. 2^30; they restart at 2^30 - 2).  Only forwards: a value below the current epoch
- *                        is HAGRID_EINVAL, since words of a later epoch would look published again.  hagrid_kat_scan_epoch reads it back */
+ *                        is HAGRID_EINVAL, since words of a later epoch would look published again.  hagrid_kat_scan_epoch reads it back
+ * Failure injection in the allocation layer (tests/test_alloc_failures_gpu.py); host side only, 0 (default) = off, the product's behaviour:
+ *   "mem.fail_request"   N > 0: the N-th allocation REQUEST from now -- a call of hagrid_mem_alloc, a growth of the look-back status words, one of the context's
+ *                        own small device buffers -- fails outright: null, the message of a failed hipMalloc, nothing allocated or released.  Clears itself
+ *                        when it has fired
+ *   "mem.fail_malloc"    N > 0: the N-th hipMalloc ATTEMPT from now counts as failed (nothing is allocated by it).  Inside hagrid_mem_alloc that is the branch
+ *                        "give back every cached buffer and retry once"; the retry is a real hipMalloc.  Clears itself when it has fired
+ *   "mem.fail_scan"      N > 0: the N-th look-back scan from now finds its status words released and their growth refused (counted as a request): what a growth
+ *                        that fails would leave, at a scan of ANY level or iteration -- the words of a pass otherwise grow at its first scan only, so the exits
+ *                        behind a late scan (merge.hip: the in-place iterations, the final compaction) would stay out of reach.  The next scan grows them again.
+ *                        Clears itself when it has fired; set to a large N, the difference read back afterwards counts the scans of a call */
 int hagrid_kat_set_option(hagrid_ctx* ctx, const char* key, int value);
+/* The allocation layer's books: out = { requests so far, hipMalloc attempts so far, slots in use, tracked pointers, bytes of the slots in use, bytes of cached
+ * free slots }. */
+int hagrid_kat_mem_state(hagrid_ctx* ctx, int64_t out[6]);
+/* The retry branch of hagrid_mem_alloc ("give back every cached buffer and retry once"): out = { times taken so far, bytes given back by it so far, and -- measured
+ * right behind the last one's release, before the second attempt -- the bytes still cached, usage minus the bytes of the slots in use }.  Both of the last are 0
+ * when the branch gave back every cached buffer. */
+int hagrid_kat_mem_retry(hagrid_ctx* ctx, int64_t out[4]);
+/* The three injection settings as they stand (requests / attempts / scans still to pass before the failure; 0: off, or fired).  Any pointer may be NULL. */
+int hagrid_kat_mem_pending(hagrid_ctx* ctx, int32_t* fail_request, int32_t* fail_malloc, int32_t* fail_scan);
 /* The epoch the context's last look-back scan ran under (0: none since the status words were made or restarted). */
 int hagrid_kat_scan_epoch(hagrid_ctx* ctx, int32_t* epoch);
 

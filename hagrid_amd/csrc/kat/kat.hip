@@ -352,6 +352,7 @@ extern "C" int hagrid_kat_set_option(hagrid_ctx* ctx, const char* key, int value
         {"expand.voxel_map", &ctx->opt_expand_voxel_map, 0, 1},
         {"expand.listed", &ctx->opt_expand_listed, 0, 1},          {"expand.max_listed", &ctx->opt_expand_max_listed, 0, 48},
         {"distance.by_triangle", &ctx->opt_distance_by_triangle, 0, 1},
+        {"mem.fail_request", &ctx->opt_fail_request, 0, 0x7fffffff}, {"mem.fail_malloc", &ctx->opt_fail_malloc, 0, 0x7fffffff}, {"mem.fail_scan", &ctx->opt_fail_scan, 0, 0x7fffffff},
     };
     if (!strcmp(key, "scan.epoch")) {
         // only forwards: status words of an epoch that comes again would read as published
@@ -366,6 +367,32 @@ extern "C" int hagrid_kat_set_option(hagrid_ctx* ctx, const char* key, int value
             return HAGRID_OK;
         }
     return hagrid_set_option(ctx, key, value);              // the product's own options
+}
+
+extern "C" int hagrid_kat_mem_state(hagrid_ctx* ctx, int64_t out[6]) {
+    if (!ctx || !out) return HAGRID_EINVAL;
+    int64_t in_use = 0, bytes_in_use = 0, bytes_cached = 0;
+    for (const auto& s : ctx->slots) {
+        if (s.in_use) { in_use++; bytes_in_use += int64_t(s.size); }
+        else if (s.ptr) bytes_cached += int64_t(s.size);
+    }
+    out[0] = ctx->mem_requests; out[1] = ctx->mem_mallocs; out[2] = in_use; out[3] = int64_t(ctx->tracker.size());
+    out[4] = bytes_in_use; out[5] = bytes_cached;
+    return HAGRID_OK;
+}
+
+extern "C" int hagrid_kat_mem_retry(hagrid_ctx* ctx, int64_t out[4]) {
+    if (!ctx || !out) return HAGRID_EINVAL;
+    out[0] = ctx->mem_retries; out[1] = ctx->mem_retry_bytes; out[2] = ctx->mem_retry_left; out[3] = ctx->mem_retry_slack;
+    return HAGRID_OK;
+}
+
+extern "C" int hagrid_kat_mem_pending(hagrid_ctx* ctx, int32_t* fail_request, int32_t* fail_malloc, int32_t* fail_scan) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (fail_request) *fail_request = ctx->opt_fail_request;
+    if (fail_malloc) *fail_malloc = ctx->opt_fail_malloc;
+    if (fail_scan) *fail_scan = ctx->opt_fail_scan;
+    return HAGRID_OK;
 }
 
 extern "C" int hagrid_kat_scan_epoch(hagrid_ctx* ctx, int32_t* epoch) {

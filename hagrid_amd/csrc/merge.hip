@@ -672,7 +672,10 @@ extern "C" int hagrid_merge_grid(hagrid_ctx* ctx, hagrid_grid* grid, float alpha
         hagrid_mem_free(ctx, tile_sums); hagrid_mem_free(ctx, partials); hagrid_mem_free(ctx, stamps_base);
     };
     if (!cells_b || !refs_b || !merge_counts || !nexts || !prevs || !cell_flags || !tile_sums || !partials || !stamps) {
+        // (nothing is queued yet, but the promise of the header is ONE state for every failure of this pass: the grid is gone)
         release(); hagrid_mem_free(ctx, cells_b); hagrid_mem_free(ctx, refs_b);
+        hagrid_mem_free(ctx, grid->cells); hagrid_mem_free(ctx, grid->ref_ids);
+        grid->cells = nullptr; grid->ref_ids = nullptr; grid->num_cells = 0; grid->num_refs = 0;
         return HAGRID_ENOMEM;
     }
 

@@ -369,7 +369,8 @@ void hagrid_trav::launch_detect(hagrid_ctx* ctx, const TraverseArgs& a, int num_
     const float tau = length(ext) / 64.0f;
     if (num_rays < origin_min_rays || !(tau > 0.0f) || !(tau < 3.0e18f)) return;
     if (!ctx->row_scores) {
-        if (hipMalloc((void**)&ctx->row_scores, (kRowCandidates + 8) * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); ctx->row_scores = nullptr; return; }
+        ctx->row_scores = static_cast<int*>(device_request(ctx, (kRowCandidates + 8) * sizeof(int), true));       // (optional: without it the first criterion stands alone)
+        if (!ctx->row_scores) return;
         (void)hipMemsetAsync(ctx->row_scores, 0, (kRowCandidates + 8) * sizeof(int), ctx->stream);
     }
     detect_ray_rows<<<1 + (kRowCandidates + 1 + 3) / 4, kDetectBlock, 0, ctx->stream>>>(a.rays, num_rays, row_len, ctx->row_scores, 1.0f / (tau * tau), 1); HG_DBG(ctx);
@@ -383,7 +384,8 @@ bool hagrid_trav::tile_order_buffers(hagrid_ctx* ctx, hagrid_ctx::RayHints& h, i
     // (growing waits for the stream: the old buffers may be in use)
     if (h.lpt_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.lpt_buf); h.lpt_buf = nullptr; h.lpt_cap = 0; }
     const int cap = tiles <= (1 << 14) ? (1 << 14) : kMaxOrderTiles;
-    if (hipMalloc((void**)&h.lpt_buf, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4)) != hipSuccess) { (void)hipGetLastError(); h.lpt_buf = nullptr; return false; }
+    h.lpt_buf = static_cast<int*>(device_request(ctx, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4), true));      // (optional: without it the launch keeps the default order)
+    if (!h.lpt_buf) return false;
     (void)hipMemsetAsync(h.lpt_buf, 0, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4), ctx->stream);
     h.lpt_cap = cap; h.lpt_valid = false;
     return true;
@@ -413,7 +415,8 @@ int bin_rays_bits(hagrid_ctx* ctx, TraverseArgs& a, int num_rays, PoolTemps& tmp
         int* row_len = ctx->dscratch + kScrRowLenBinned;
         int* flag = ctx->dscratch + kScrRowLenBinned + 1;
         if (!ctx->bin_diff) {
-            HG_HIP(ctx, hipMalloc((void**)&ctx->bin_diff, 64 * sizeof(int)));
+            ctx->bin_diff = static_cast<int*>(device_request(ctx, 64 * sizeof(int), false));
+            if (!ctx->bin_diff) return HAGRID_ENOMEM;
             HG_HIP(ctx, hipMemsetAsync(ctx->bin_diff, 0, 64 * sizeof(int), ctx->stream));
         }
         launch_detect(ctx, a, ctx->opt_image_width >= 0 ? num_rays : 0, row_len);

@@ -179,6 +179,9 @@ KAT_SIGNATURES = {
     "hagrid_kat_scan": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "hagrid_kat_set_option": (_i32, [_vp, C.c_char_p, _i32]),
     "hagrid_kat_scan_epoch": (_i32, [_vp, _vp]),
+    "hagrid_kat_mem_state": (_i32, [_vp, C.POINTER(_i64)]),
+    "hagrid_kat_mem_retry": (_i32, [_vp, C.POINTER(_i64)]),
+    "hagrid_kat_mem_pending": (_i32, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hagrid_kat_order_state": (_i32, [_vp, _vp, _vp, _vp]),
     "hagrid_kat_forget_hints": (_i32, [_vp]),
     "hagrid_kat_detect_ray_rows": (_i32, [_vp, _vp, _i32, C.c_float, _vp]),

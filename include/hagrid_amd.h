@@ -16,6 +16,14 @@
  *   - All work is enqueued on the context's HIP stream (default: the null stream, like the reference's
  *     <<<...>>> launches).  Build passes synchronise with the host where they need sizes; traversal is
  *     asynchronous.
+ *   - HAGRID_ENOMEM (a device allocation failed; the library shares the device with whoever else fills it, so this is an ordinary event
+ *     in a frame loop).  For EVERY entry point that can answer it: the context stays usable; hagrid_last_error names this failure;
+ *     nothing the call allocated stays in use (the pool's books are what they were, minus what the call is documented to release);
+ *     every pointer left in a descriptor is a live pool pointer that hagrid_mem_free accepts exactly once; no HIP error state is
+ *     left behind for the next call.  What the descriptor and the caller's buffers ARE afterwards is one of two states, named at
+ *     each entry point: "unchanged" (byte for byte what they were before the call, and still valid) or "released" (given back to
+ *     the pool and NULL in the descriptor).  Some allocations are OPTIONAL (a pass runs without the buffer, only slower): their
+ *     failure is not an error, the call answers HAGRID_OK with the same results.
  *   - One host thread per context.  Contexts are independent (the reference keeps per-TU __constant__
  *     state and therefore allows one grid per process: traverse.cu:7-12; here the traversal constants
  *     live in the context / the grid descriptor).
@@ -143,20 +151,27 @@ float hagrid_profile_end(hagrid_ctx* ctx);
  * scene-box extent is not finite, for a top-level grid, a level's references or cells, or the totals beyond 2^30 - 1 (true totals: a sum of 2^32 or
  * more is seen), and for 24 levels or more.  A scene whose box has no volume (a quad, a ground plane, coincident points) is built in a box widened
  * to 2^-10 of the scene's scale on its thin axes; that box is grid->bbox.  After a refusal *grid is as it was, the context stays usable and the pool's
- * usage is unchanged.  Grids of 16 to 23 levels (grid->shift > 15) are built, and hagrid_merge_grid, hagrid_flatten_grid and hagrid_expand_grid accept
+ * usage is unchanged.  HAGRID_ENOMEM, in whichever level of the construction: the same -- *grid is UNCHANGED byte for byte (it is written when the last
+ * kernel has run), every temporary and every output array already taken is back in the pool.  Optional: the one buffer the temporaries of a context's
+ * later constructions are carved from.  Grids of 16 to 23 levels (grid->shift > 15) are built, and hagrid_merge_grid, hagrid_flatten_grid and hagrid_expand_grid accept
  * them; hagrid_compress_grid returns 0, and every traversal, query and blob call -- hagrid_setup_traversal, hagrid_grid_release_for_traversal,
  * hagrid_grid_pack and hagrid_grid_save included -- answers HAGRID_EINVAL ("bad shift") before it launches or writes anything. */
 int hagrid_build_grid(hagrid_ctx* ctx, const void* tris, int num_tris, hagrid_grid* grid,
                       float top_density, float snd_density);
-/* merge_grid (merge.cu:331-377).  On an error the grid is gone: cells and ref_ids are released and NULL in the descriptor
- * (the voxel map may already name the new cells); entries stay the caller's to free. */
+/* merge_grid (merge.cu:331-377).  On HAGRID_ENOMEM and HAGRID_EHIP the grid is gone: cells and ref_ids are RELEASED and NULL in the
+ * descriptor, num_cells = num_refs = 0 (the voxel map may already name the new cells); entries stay the caller's to free.  That holds for
+ * every allocation of the pass -- the nine working buffers in front of the first kernel as well as the status words of a scan in a late
+ * iteration: one state, whenever it happens.  A refused argument (HAGRID_EINVAL) leaves the grid alone. */
 int hagrid_merge_grid(hagrid_ctx* ctx, hagrid_grid* grid, float alpha);
-/* flatten_grid (flatten.cu:109-175) */
+/* flatten_grid (flatten.cu:109-175).  HAGRID_ENOMEM: the grid is UNCHANGED -- the pass collapses the voxel map in a working copy and
+ * swaps grid->entries (releasing the old map) only when everything has run. */
 int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid);
-/* expand_grid (expand.cu:199-225) */
+/* expand_grid (expand.cu:199-225).  HAGRID_ENOMEM (the second cell buffer, the flags): the grid is UNCHANGED; nothing was launched.
+ * Optional: the list of cells of the later iterations, the voxel map resolved into one word per voxel. */
 int hagrid_expand_grid(hagrid_ctx* ctx, hagrid_grid* grid, const void* tris, int iters);
 /* compress_grid (compress.cu:38-63): returns 1 when compressed, 0 when the virtual resolution does not
- * fit 16 bits (grid untouched), negative on error. */
+ * fit 16 bits (grid untouched), negative on error.  HAGRID_ENOMEM: the grid is UNCHANGED (cells and ref_ids are released only when
+ * the small cells and their references stand). */
 int hagrid_compress_grid(hagrid_ctx* ctx, hagrid_grid* grid);
 
 /* ---- the grid as one buffer: multi-GPU broadcast and save / load (no reference counterpart) -------------- */
@@ -174,19 +189,26 @@ typedef struct hagrid_blob_header {
 } hagrid_blob_header;
 /* Size of the blob of `grid` with `num_tris` triangles (0 for an incomplete grid). */
 size_t hagrid_grid_blob_bytes(const hagrid_grid* grid, int num_tris);
-/* Copies grid + triangles into one new pool buffer (device-to-device); release it with hagrid_mem_free. */
+/* Copies grid + triangles into one new pool buffer (device-to-device); release it with hagrid_mem_free.  HAGRID_ENOMEM: *blob is NULL,
+ * *bytes is not written, grid and triangles are UNCHANGED (they are only read). */
 int hagrid_grid_pack(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, int num_tris, void** blob, size_t* bytes);
 /* Turns a blob held in a pool buffer of this context into a grid IN PLACE: the buffer is split into the four arrays, which from then
  * on are ordinary pool buffers (grid->entries, grid->cells | small_cells, grid->ref_ids, *tris: each released with hagrid_mem_free, in
- * any order, like the arrays of a built grid); `blob` itself must not be freed afterwards.  Nothing is copied. */
+ * any order, like the arrays of a built grid); `blob` itself must not be freed afterwards.  Nothing is copied and nothing is allocated: the
+ * call cannot answer HAGRID_ENOMEM. */
 int hagrid_grid_unpack(hagrid_ctx* ctx, void* blob, size_t bytes, hagrid_grid* grid, void** tris, int* num_tris);
-/* The blob as a file. */
+/* The blob as a file.  HAGRID_ENOMEM (save: the blob, or host memory for it; load: host memory, or the pool buffer the file goes into): save has
+ * written no file and leaves grid and triangles UNCHANGED; load leaves *grid, *tris and *num_tris UNCHANGED (they are written by the
+ * unpacking, last) and keeps no buffer. */
 int hagrid_grid_save(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, int num_tris, const char* path);
 int hagrid_grid_load(hagrid_ctx* ctx, const char* path, hagrid_grid* grid, void** tris, int* num_tris);
 /* One process per GPU: rank `root` passes its grid and triangles (they stay untouched), every other rank receives them (grid, *tris,
  * *num_tris are outputs there, arrays owned as after hagrid_grid_unpack).  `comm` is an ncclComm_t of RCCL spanning the ranks; two
  * ncclBroadcast calls on the context's stream: the 256-byte header, then the blob, straight from / into pool memory.  RCCL is
- * looked up in the running process (the copy PyTorch or the host program loaded, else /opt/rocm/lib/librccl.so).  Blocking. */
+ * looked up in the running process (the copy PyTorch or the host program loaded, else /opt/rocm/lib/librccl.so).  Blocking.
+ * HAGRID_ENOMEM for the blob (the root's pack, a receiver's buffer) is agreed among the ranks before the blob travels: every rank answers an
+ * error and keeps no buffer; the receivers' *grid, *tris and *num_tris are UNCHANGED.  The call's own 260 bytes are taken in front of the first
+ * collective: a rank that cannot get them answers HAGRID_ENOMEM at once, and the other ranks wait for it in the collective. */
 int hagrid_grid_broadcast(hagrid_ctx* ctx, void* comm, int rank, int root, hagrid_grid* grid, void** tris, int* num_tris);
 
 /* ---- traversal (traverse.h:11-14) ------------------------------------------------------------------- */
@@ -206,7 +228,11 @@ int hagrid_grid_broadcast(hagrid_ctx* ctx, void* comm, int rank, int root, hagri
  * hagrid_traverse_grid uses the image when it is called with the same grid (same arrays, same counts); the image is
  * dropped when a construction pass runs in this context or when one of the grid's arrays is freed or overwritten through
  * this API; without an image traversal reads the construction format.  Hits are identical either way.  Synchronous (size / fit
- * read-backs); 0.3 ms and 129 MB for the 1M-triangle scene of BASELINE.md. */
+ * read-backs); 0.3 ms and 129 MB for the 1M-triangle scene of BASELINE.md.
+ * HAGRID_ENOMEM: the grid is UNCHANGED (it is only read) and the context holds NO traversal image -- the image of an earlier call is dropped
+ * first, every buffer of the unfinished one is back in the pool -- so hagrid_traverse_grid still works and reads the construction format.  The
+ * call does not end "OK without an image" for lack of memory: that answer is kept for grids no layout describes.  Optional: the compact layout
+ * that is built next to a much bigger uniform one. */
 int hagrid_setup_traversal(hagrid_ctx* ctx, const hagrid_grid* grid);
 /* Extension: after hagrid_setup_traversal built the image of `grid` (no layout refers to the voxel map), the
  * caller may give the construction format up: entries and cells | small_cells are released to the pool and set to NULL in the
@@ -229,7 +255,10 @@ int hagrid_share_traversal(hagrid_ctx* dst, hagrid_ctx* src);
  * Rays are taken as they are.  A ray with a NaN or infinite org / dir component, a NaN tmin / tmax, or a dir with no component whose float32 reciprocal is finite
  * ((+-0, +-0, +-0), or every component below about 2.94e-39) is a MISS that takes no
  * cell step: id -1, t = the bits of its tmax, u = v = 0 (multi-hit: k such records), whatever else the batch holds; +-inf are valid tmin / tmax; the
- * sign of a zero dir component changes no result (include/hagrid/ray.h admit_ray). */
+ * sign of a zero dir component changes no result (include/hagrid/ray.h admit_ray).
+ * HAGRID_ENOMEM (only with hagrid_set_ray_binning: the permutation, the keys, the bin table, its partial sums, the words of the automatic mode,
+ * the status words of the scan): the traversal kernel was not launched, so `hits` is UNCHANGED -- not one byte written -- and so are grid, tris and
+ * rays; the binning buffers are back in the pool.  Optional (the launch keeps its default order): the row scores and the tile-order buffer of a ray buffer. */
 int hagrid_traverse_grid(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
                          const void* rays, void* hits, int num_rays);
 /* Variants of the same walk (no separate entry point in the reference).  flags:
@@ -244,7 +273,8 @@ int hagrid_traverse_grid(hagrid_ctx* ctx, const hagrid_grid* grid, const void* t
 int hagrid_traverse_grid_ex(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
                             const void* rays, void* hits, int num_rays, uint32_t flags);
 /* Same traversal, additionally: steps[i] (device int32, may be NULL) = the reference's per-ray step
- * count (traverse.cu:80,93), and *stats (host, may be NULL) = batch totals.  Synchronous. */
+ * count (traverse.cu:80,93), and *stats (host, may be NULL) = batch totals.  Synchronous.
+ * HAGRID_ENOMEM (the eight counters, taken only when stats is given): nothing was launched; hits and steps are UNCHANGED, *stats is all zeroes. */
 int hagrid_traverse_grid_stats(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris,
                                const void* rays, void* hits, int num_rays,
                                void* steps, hagrid_traversal_stats* stats);
@@ -517,7 +547,9 @@ int hagrid_fill_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tr
  * On the context's stream.  With the traversal image of this grid in the context (hagrid_setup_traversal) there is no host round trip; without it one word (the
  * largest id) is read back first.  One temporary of 4 bytes per triangle comes from the context's pool.
  * HAGRID_EINVAL: the lattice errors of hagrid_inside_lattice; a null, released or incomplete grid; a band that is negative, NaN or infinite; a null or
- * misaligned workspace; ids, d2 and records all NULL; misaligned buffers (triangles and records 16 bytes, ids and d2 4, counters 8); any flag. */
+ * misaligned workspace; ids, d2 and records all NULL; misaligned buffers (triangles and records 16 bytes, ids and d2 4, counters 8); any flag.
+ * HAGRID_ENOMEM (the temporary, the status words of the scan over it): ids, d2, records and counters are UNCHANGED -- the kernel that writes them
+ * was not launched; the workspace is the call's to scribble on, as always. */
 int hagrid_distance_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const float* origin, const float* size, const int* n,
                             float band, void* workspace, void* ids, void* d2, void* records, void* counters, uint32_t flags);
 
@@ -646,7 +678,8 @@ typedef struct hagrid_scene hagrid_scene;
  * HAGRID_EINVAL (and *out = NULL): a null `out`, null `meshes` with num_meshes > 0, negative counts, a mesh with a stride below 12 or not a
  * multiple of 4, a non-zero `reserved`, num_vertices == 0 with num_tris > 0, a null or misaligned vertex buffer of a mesh that has triangles, a
  * misaligned index buffer, indices == NULL with 3 * num_tris beyond 2^31 - 1, instance_mesh[i] outside 0 .. num_meshes-1, instance_mesh ==
- * NULL with num_instances != num_meshes.  HAGRID_ERANGE: more than 2^31 - 1 output triangles.  A scene without triangles is HAGRID_OK. */
+ * NULL with num_instances != num_meshes.  HAGRID_ERANGE: more than 2^31 - 1 output triangles.  A scene without triangles is HAGRID_OK.
+ * HAGRID_ENOMEM (the pool buffer of the tables): *out = NULL, nothing is kept.  hagrid_scene_assemble itself allocates nothing. */
 int hagrid_scene_create(hagrid_ctx* ctx, const hagrid_mesh* meshes, int num_meshes,
                         const int32_t* instance_mesh, int num_instances, hagrid_scene** out);
 void hagrid_scene_destroy(hagrid_ctx* ctx, hagrid_scene* scene);
