@@ -124,32 +124,56 @@ struct hagrid_ctx {
     // What the context remembers about a ray buffer it has traversed (traverse.hip): the row length found for it and the order of its tiles.  A few
     // buffers are remembered at once (a renderer that alternates between two or three ray buffers keeps the hints of each); the least recently used
     // slot is taken over by a new buffer.  Slot i owns the device word dscratch[kScrRowLen + i] and the pinned words mailbox[kMbxRowLen + i], [kMbxOrderStale + i], [kMbxHeadSuggest + i].
+    // The state is grouped by what owns it; a group that is reset as a whole (`trial`) is assigned `{}`, so a field added to it is reset with it.
     struct RayHints {
-        const void* key_rays = nullptr; int key_n = 0;       // the buffer the slot belongs to
-        const void* rowlen_rays = nullptr; int rowlen_n = 0, rowlen_age = 0, rowlen_known = -1, rowlen_seen = 0; bool rows_from_origins = false /* the row length came from neighbouring origins alone: an image order without coherent directions (bounce rays) */;   // rowlen_known: the row length as the host has seen it (-1: not yet)
-        hipEvent_t rowlen_evt = nullptr; bool rowlen_pending = false;
+        const void* key_rays = nullptr; int key_n = 0;  // the buffer the slot belongs to
+        unsigned long long used = 0;                    // clock of the last call that used the slot
+        // the row length found for the buffer
+        struct Rows {
+            const void* rowlen_rays = nullptr; int rowlen_n = 0, rowlen_age = 0;
+            int rowlen_known = -1, rowlen_seen = 0;     // rowlen_known: the row length as the host has seen it (-1: not yet)
+            bool rows_from_origins = false;             // the row length came from neighbouring origins alone: an image order without coherent directions (bounce rays)
+            hipEvent_t rowlen_evt = nullptr; bool rowlen_pending = false;
+        } rows;
         // tile order of the tail kernel: cost | order, lpt_cap ints each; the order is valid for launches over (lpt_rays, lpt_n)
-        int* lpt_buf = nullptr; int lpt_cap = 0; const void* lpt_rays = nullptr; int lpt_n = 0, lpt_blocks = 0, lpt_age = 0, lpt_period = 32, lpt_rot = 0 /* positions the stored order is rotated by: its last lpt_rot tiles are the longest */; bool rot_adopted = false /* the first suggestion of a sort was taken up by a sort of its own */;
-        // the head share measures itself: launches in the learned order are timed (an event pair around the kernel, polled by later calls) without it and with it --
-        // three samples each, the smaller ones compared -- and a share that does not pay is dropped for as long as the order lives
-        hipEvent_t trial_evt[2] = {nullptr, nullptr}; bool trial_pending = false, trial_with_head = false, head_disabled = false;
-        float t_base = 0.0f, t_head = 0.0f; int n_base = 0, n_head = 0, trial_opt = -1 /* the value of traverse.quad_head the trial belongs to */; unsigned head_serial = 0 /* ... and the traversal image (ctx->image_serial) */; bool lpt_valid = false;
         // The order is only as good as the rays it was learned on: the sort leaves a copy of one sample ray of the buffer behind the order
         // (lpt_buf + 2 * lpt_cap: 2 float4), the first wavefront of every launch compares them with the buffer's rays ON THE DEVICE, bit for bit, and when the
         // buffer holds other rays (refilled, recycled address, a camera that moved) reports the order's epoch in the pinned word mailbox[kMbxOrderStale + i],
         // which the host polls: that launch is the only one that follows the stale order, the order is learned again.  Orders that do not last (a camera that moves fast) are not learned for a while (cooldown).
-        int lpt_epoch = 1 /* never 0: the pinned report word starts as 0 and is reset to -1 */, relearn_streak = 0, cooldown = 0, cooldown_len = 64; unsigned long long relearn_clock = 0;     // (cooldown_len: doubles with every give-up in a row, up to 1024 launches)
+        struct Order {
+            int* lpt_buf = nullptr; int lpt_cap = 0;    // (resources: they survive every reset)
+            const void* lpt_rays = nullptr; int lpt_n = 0, lpt_blocks = 0, lpt_age = 0, lpt_period = 32;
+            int lpt_rot = 0;                            // positions the stored order is rotated by: its last lpt_rot tiles are the longest
+            bool lpt_valid = false; int lpt_epoch = 1;  // lpt_epoch: never 0: the pinned report word starts as 0 and is reset to -1
+            // ctx->image_serial the learned tile order belongs to; the report word (mailbox[kMbxOrderStale + slot]) as last seen
+            unsigned order_serial = 0; int last_report = -1;
+            unsigned long long relearn_clock = 0; int cooldown = 0, cooldown_len = 64;      // (cooldown_len: doubles with every give-up in a row, up to 1024 launches)
+        } order;
+        // the head share measures itself: launches in the learned order are timed (an event pair around the kernel, polled by later calls) without it and with it --
+        // three samples each, the smaller ones compared -- and a share that does not pay is dropped for as long as the order lives
+        // What the timed launches found: reset as a whole (`trial = {}`) wherever the order is learned again from nothing.
+        struct Trial {
+            bool rot_adopted = false, head_disabled = false;    // rot_adopted: the first suggestion of a sort was taken up by a sort of its own
+            float t_base = 0.0f, t_head = 0.0f, t_all = 0.0f; int n_base = 0, n_head = 0, n_all = 0;
+            bool learned_all = false; int all_stage = 0;        // all_stage: 0 not tried, 1 - 2 learning its own order, 3 timed, 4 decided
+            bool cmp_pending = false, cmp_done = false; // the order against the default order: three default-order launches timed next to the order's own samples
+            int n_conf = 0; float t_conf = 0.0f;        // (t_conf is written under `n_conf ? min : ms` and read only once n_conf >= 3: zeroing it with n_conf cannot be observed)
+        } trial;
+        // the timed launch in flight (trial_pending is cleared at slot take-over only); trial_kind: 0 the order alone, 1 with the head share, 2 with ALL tiles four lanes per ray
+        hipEvent_t trial_evt[2] = {nullptr, nullptr}; bool trial_pending = false; int trial_kind = 0;
+        int trial_opt = -1; unsigned head_serial = 0;   // the value of traverse.quad_head the trial belongs to, and the traversal image (ctx->image_serial)
         // the share trial of launches in the default order (traverse.hip "traverse.share_trial"): candidates = the rule's share of tiles with four lanes per ray, a half, none, all
         // (sample k = candidate k % share_ncand, each with its own event pair: all may be in flight at once)
-        hipEvent_t share_evt[12][2] = {}; int share_issued = 0, share_done = 0, share_choice = -1 /* index into share_cands; -1: being measured */, share_ncand = 0 /* candidates of the running trial */, share_shape_nc = 0 /* ... of the launch shape's first trial */, share_cands[4] = {0, 0, 0, 0} /* per cent */,
-            share_last = -1 /* the share (per cent) the last trial chose */, share_launches = 0; float share_t[4] = {0.0f, 0.0f, 0.0f, 0.0f}; unsigned share_serial = 0 /* ctx->image_serial the answer belongs to */;
-        int trial_kind = 0 /* the timed launch in flight: 0 the order alone, 1 with the head share, 2 with ALL tiles four lanes per ray */, n_all = 0, all_stage = 0 /* 0 not tried, 1 - 2 learning its own order, 3 timed, 4 decided */; float t_all = 0.0f; bool learned_all = false;
-        bool learned_once = false;          // the first share trial of this launch shape has been decided and the order learned behind it
-        unsigned order_serial = 0;          // ctx->image_serial the learned tile order belongs to
-        bool cmp_pending = false, cmp_done = false; int n_conf = 0; float t_conf = 0.0f;     // the order against the default order: three default-order launches timed next to the order's own samples
-        bool order_loses = false;           // the learned order's steady launches were not 3 % faster than the best default-order launch: not followed until the next trial
-        int last_report = -1;               // the report word (mailbox[kMbxOrderStale + slot]) as last seen
-        unsigned long long used = 0;                    // clock of the last call that used the slot
+        struct Share {
+            hipEvent_t share_evt[12][2] = {}; int share_issued = 0, share_done = 0;
+            int share_choice = -1;                      // index into share_cands; -1: being measured
+            int share_ncand = 0, share_shape_nc = 0;    // candidates of the running trial, ... of the launch shape's first trial
+            int share_cands[4] = {0, 0, 0, 0}; float share_t[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // per cent; milliseconds
+            int share_last = -1;                        // the share (per cent) the last trial chose
+            int share_launches = 0; unsigned share_serial = 0;      // share_serial: ctx->image_serial the answer belongs to
+            bool learned_once = false;                  // the first share trial of this launch shape has been decided and the order learned behind it
+            bool order_loses = false;                   // the learned order's steady launches were not 3 % faster than the best default-order launch: not followed until the next trial
+        } share;
     };
     static constexpr int kRayHints = 4;
     RayHints hints[kRayHints];

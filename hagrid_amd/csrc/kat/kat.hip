@@ -264,14 +264,14 @@ extern "C" int hagrid_kat_tile_order(hagrid_ctx* ctx, const int32_t* cost_in, in
         !order_out || !cost_after_out || !suggest_out || !sample_out8) return HAGRID_EINVAL;
     hagrid_ctx::RayHints h;
     if (!tile_order_buffers(ctx, h, n)) return HAGRID_ENOMEM;
-    struct Release { hagrid_ctx* ctx; hagrid_ctx::RayHints& h; ~Release() { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.lpt_buf); } } release{ctx, h};
-    if (h.lpt_cap < n) HG_FAIL(ctx, HAGRID_EINVAL, "kat_tile_order: buffers smaller than the launch");
+    struct Release { hagrid_ctx* ctx; hagrid_ctx::RayHints& h; ~Release() { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.order.lpt_buf); } } release{ctx, h};
+    if (h.order.lpt_cap < n) HG_FAIL(ctx, HAGRID_EINVAL, "kat_tile_order: buffers smaller than the launch");
     const int32_t unset = -1;
     Staged sg(ctx, &unset, sizeof(int));
     if (!sg.d) return HAGRID_ENOMEM;
-    HG_TRY(hagrid_mem_copy_h2d(ctx, h.lpt_buf, cost_in, size_t(n) * sizeof(int)));
+    HG_TRY(hagrid_mem_copy_h2d(ctx, h.order.lpt_buf, cost_in, size_t(n) * sizeof(int)));
     // (order and samples start as ones, not as the zeroes of a fresh buffer: a position the sort skips must not read as tile 0)
-    HG_HIP(ctx, hipMemsetAsync(h.lpt_buf + h.lpt_cap, 0xFF, size_t(h.lpt_cap) * sizeof(int) + 8 * sizeof(float4), ctx->stream));
+    HG_HIP(ctx, hipMemsetAsync(h.order.lpt_buf + h.order.lpt_cap, 0xFF, size_t(h.order.lpt_cap) * sizeof(int) + 8 * sizeof(float4), ctx->stream));
     TraverseArgs a;
     memset(&a, 0, sizeof(a));
     a.rays = static_cast<const float4*>(rays_dev); a.num_rays = num_rays;
@@ -280,8 +280,8 @@ extern "C" int hagrid_kat_tile_order(hagrid_ctx* ctx, const int32_t* cost_in, in
     launch_tile_order(ctx, h, n, a, rot, static_cast<int*>(sg.d));
     ctx->opt_quad_head = saved;
     HG_HIP(ctx, hipGetLastError());
-    HG_TRY(hagrid_mem_copy_d2h(ctx, order_out, h.lpt_buf + h.lpt_cap, size_t(n) * sizeof(int)));
-    HG_TRY(hagrid_mem_copy_d2h(ctx, cost_after_out, h.lpt_buf, size_t(n) * sizeof(int)));
+    HG_TRY(hagrid_mem_copy_d2h(ctx, order_out, h.order.lpt_buf + h.order.lpt_cap, size_t(n) * sizeof(int)));
+    HG_TRY(hagrid_mem_copy_d2h(ctx, cost_after_out, h.order.lpt_buf, size_t(n) * sizeof(int)));
     HG_TRY(hagrid_mem_copy_d2h(ctx, sample_out8, tile_order_samples(h), 2 * sizeof(float4)));
     return sg.fetch(suggest_out);
 }
@@ -408,9 +408,9 @@ extern "C" int hagrid_kat_order_state(hagrid_ctx* ctx, const void* rays, int32_t
     for (int i = 0; i < hagrid_ctx::kRayHints; i++) {
         const hagrid_ctx::RayHints& h = ctx->hints[i];
         if (h.key_rays != rays) continue;
-        const int v[12] = {i, h.lpt_valid, h.cooldown > 0, h.lpt_rot, h.head_disabled, h.n_base, h.n_head, h.share_choice >= 0 ? h.share_cands[h.share_choice] : -1, h.share_done + 100 * h.share_issued + 10000 * int(h.order_loses), h.n_all + 10 * int(h.learned_all) + 100 * h.cooldown, __atomic_load_n(ctx->mailbox + kMbxHeadSuggest + i, __ATOMIC_RELAXED), h.share_launches};
+        const int v[12] = {i, h.order.lpt_valid, h.order.cooldown > 0, h.order.lpt_rot, h.trial.head_disabled, h.trial.n_base, h.trial.n_head, h.share.share_choice >= 0 ? h.share.share_cands[h.share.share_choice] : -1, h.share.share_done + 100 * h.share.share_issued + 10000 * int(h.share.order_loses), h.trial.n_all + 10 * int(h.trial.learned_all) + 100 * h.order.cooldown, __atomic_load_n(ctx->mailbox + kMbxHeadSuggest + i, __ATOMIC_RELAXED), h.share.share_launches};
         for (int k = 0; k < 12; k++) out12[k] = v[k];
-        if (ms2) { ms2[0] = h.t_base; ms2[1] = h.t_head; ms2[2] = h.t_all; ms2[3] = h.share_choice >= 0 ? h.share_t[h.share_choice] : 0.0f; }
+        if (ms2) { ms2[0] = h.trial.t_base; ms2[1] = h.trial.t_head; ms2[2] = h.trial.t_all; ms2[3] = h.share.share_choice >= 0 ? h.share.share_t[h.share.share_choice] : 0.0f; }
         return HAGRID_OK;
     }
     return HAGRID_OK;
@@ -418,6 +418,6 @@ extern "C" int hagrid_kat_order_state(hagrid_ctx* ctx, const void* rays, int32_t
 
 extern "C" int hagrid_kat_forget_hints(hagrid_ctx* ctx) {
     if (!ctx) return HAGRID_EINVAL;
-    for (auto& h : ctx->hints) { h.key_rays = nullptr; h.key_n = 0; h.used = 0; h.lpt_rays = nullptr; h.lpt_valid = false; h.rowlen_rays = nullptr; h.rowlen_seen = 0; h.share_ncand = 0; h.share_shape_nc = 0; h.share_choice = -1; }
+    for (auto& h : ctx->hints) { h.key_rays = nullptr; h.key_n = 0; h.used = 0; h.order.lpt_rays = nullptr; h.order.lpt_valid = false; h.rows.rowlen_rays = nullptr; h.rows.rowlen_seen = 0; h.share.share_ncand = 0; h.share.share_shape_nc = 0; h.share.share_choice = -1; }
     return HAGRID_OK;
 }

@@ -379,23 +379,23 @@ void hagrid_trav::launch_detect(hagrid_ctx* ctx, const TraverseArgs& a, int num_
 
 // Tile order of the tail kernel (traverse.hip): the buffers of the context grown to `tiles` entries (cost, order; cost cleared)
 bool hagrid_trav::tile_order_buffers(hagrid_ctx* ctx, hagrid_ctx::RayHints& h, int tiles) {
-    if (h.lpt_cap >= tiles && h.lpt_buf) return true;
+    if (h.order.lpt_cap >= tiles && h.order.lpt_buf) return true;
     // two sizes only -- up to 16 384 tiles (1024^2 and smaller) or the largest launch the order is used for -- so a slot grows at most once
     // (growing waits for the stream: the old buffers may be in use)
-    if (h.lpt_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.lpt_buf); h.lpt_buf = nullptr; h.lpt_cap = 0; }
+    if (h.order.lpt_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(h.order.lpt_buf); h.order.lpt_buf = nullptr; h.order.lpt_cap = 0; }
     const int cap = tiles <= (1 << 14) ? (1 << 14) : kMaxOrderTiles;
-    h.lpt_buf = static_cast<int*>(device_request(ctx, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4), true));      // (optional: without it the launch keeps the default order)
-    if (!h.lpt_buf) return false;
-    (void)hipMemsetAsync(h.lpt_buf, 0, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4), ctx->stream);
-    h.lpt_cap = cap; h.lpt_valid = false;
+    h.order.lpt_buf = static_cast<int*>(device_request(ctx, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4), true));      // (optional: without it the launch keeps the default order)
+    if (!h.order.lpt_buf) return false;
+    (void)hipMemsetAsync(h.order.lpt_buf, 0, size_t(cap) * 2 * sizeof(int) + 8 * sizeof(float4), ctx->stream);
+    h.order.lpt_cap = cap; h.order.lpt_valid = false;
     return true;
 }
 void hagrid_trav::launch_tile_order(hagrid_ctx* ctx, hagrid_ctx::RayHints& h, int tiles, const TraverseArgs& a, int rot, int* suggest) {
-    int* cost = h.lpt_buf, *order = cost + h.lpt_cap;
+    int* cost = h.order.lpt_buf, *order = cost + h.order.lpt_cap;
     rot = std::max(0, std::min(rot, tiles));
     tile_order_kernel<<<1, kOrderBlock, 0, ctx->stream>>>(cost, order, tiles, rot, ctx->opt_quad_head, suggest, a.rays, a.num_rays, tile_order_samples(h)); HG_DBG(ctx);
-    h.lpt_rot = rot;
-    h.lpt_epoch++;
+    h.order.lpt_rot = rot;
+    h.order.lpt_epoch++;
 }
 
 namespace {

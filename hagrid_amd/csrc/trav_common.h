@@ -468,7 +468,7 @@ void launch_detect(hagrid_ctx* ctx, const TraverseArgs& a, int num_rays, int* ro
 constexpr int kMaxOrderTiles = 1 << 18;          // launches of more tiles keep the default order whatever the options say (the sort is one workgroup)
 bool tile_order_buffers(hagrid_ctx* ctx, hagrid_ctx::RayHints& h, int tiles);
 void launch_tile_order(hagrid_ctx* ctx, hagrid_ctx::RayHints& h, int tiles, const TraverseArgs& a, int rot, int* suggest);
-inline float4* tile_order_samples(const hagrid_ctx::RayHints& h) { return reinterpret_cast<float4*>(h.lpt_buf + 2 * size_t(h.lpt_cap)); }
+inline float4* tile_order_samples(const hagrid_ctx::RayHints& h) { return reinterpret_cast<float4*>(h.order.lpt_buf + 2 * size_t(h.order.lpt_cap)); }
 
 // Does the tile order still describe the rays in the buffer?  One sample ray (three eighths into the buffer) is compared BIT FOR BIT with the copy the sort
 // left behind the order: lanes 0 .. 7 of the launch's FIRST wavefront load one dword of each, one compare, one ballot; when they differ the pinned word

@@ -719,6 +719,58 @@ def test_share_trial_and_the_order_held_against_it_never_change_hits(mem):
     grid.free(); mem.free(d_tris)
 
 
+def test_tile_order_decisions_that_do_not_depend_on_measured_times(mem):
+    """The rules of the tile order's state (traverse.hip) that no measured time enters, launch by launch, through order_state: with "traverse.share_trial" and
+    "traverse.quad_head" off and a caller that synchronises after every launch, what a launch decides follows from the launches before it alone.  One 256 x 256
+    primary batch (1024 tiles: an order needs 64; an eighth of a round: no head share, no all-tiles candidate) over a 20 000-triangle soup, 95 launches:
+      * launch 1 looks for the row length, launch 2 has seen it: the order is valid from there, sorted behind launch 2 (which learns) and behind launch 3;
+      * a timed launch is one in the order's steady state (two launches behind a sort, none in flight): launches 5, 6, 7 -- n_base is 1, 2, 3 after launches
+        6, 7, 8 and stays;
+      * a refill with another camera (before launch 11): launch 11 follows the stale order and reports it, launch 12 learns again from nothing (n_base starts over
+        and reaches 3 again six launches later);
+      * a refill (before launch 20, learned again by launch 21) and a second one whose report is seen within four launches of that (before launch 23, seen by
+        launch 24): no order for 64 launches, one fewer with every launch; launch 89 learns again;
+      * the same pair once more (launches 91 / 92 and 94 / 95): 128 launches.
+    Every launch gives the oracle's hits."""
+    from oracle import oracle as O
+    from hagrid_amd import api
+    tris = scene.make_soup(20000, seed=53)
+    G = O.Grid.full(tris)
+    d_tris = mem.upload(tris); grid = upload_oracle_grid(mem, G)
+    lo, hi = np.asarray(G.bbox_min), np.asarray(G.bbox_max)
+    cams = [np.ascontiguousarray(scene.make_rays_primary(lo, hi, 256, 256, yaw=0.05 * k, strafe=0.03 * k), np.float32) for k in range(3)]
+    want = [G.traverse(tris, c, nthreads=8)[0] for c in cams]
+    n = 256 * 256
+    refill = {11: 1, 20: 2, 23: 0, 91: 1, 94: 2}                       # before this launch: that camera's rays into the buffer
+    def expected(launch):                                              # (valid, n_base, cooldown) behind the launch
+        if launch == 1: return (0, 0, 0)
+        if 24 <= launch <= 88: return (0, 0, 88 - launch)
+        if launch == 95: return (0, 0, 128)
+        if launch >= 89: return (1, 0, 0)                              # (learned at 89 and 92, never two launches behind a sort before the next report)
+        learned = max(l for l in (2, 12, 21) if l <= launch)           # the launch that learned from nothing; sorts behind it and the next, timed from three launches on
+        return (1, min(max(launch - learned - 3, 0), 3), 0)
+    api.setup_traversal(grid)
+    mem.forget_hints()                                                 # (no buffer of the same shape from another test stands in)
+    d_rays = mem.upload(cams[0]); d_hits = alloc_out(mem, 16 * n)
+    k = 0
+    try:
+        mem.set_option("traverse.share_trial", 0); mem.set_option("traverse.quad_head", 0)
+        for launch in range(1, 96):
+            if launch in refill:
+                k = refill[launch]; mem.copy_h2d(d_rays, cams[k])
+            poison(mem, d_hits, 16 * n)
+            api.traverse_grid(grid, d_tris, d_rays, d_hits, n)
+            mem.synchronize()
+            st = mem.order_state(d_rays)
+            got = fetch(mem, d_hits, api.HIT_DTYPE, n)
+            assert (got["id"] == want[k]["id"]).all() and (bits(got["t"]) == bits(want[k]["t"])).all(), (launch, st)
+            assert (st["valid"], st["n_base"], st["cooldown"]) == expected(launch) and st["cooling"] == (st["cooldown"] > 0), (launch, st)
+            assert st["slot"] >= 0 and st["head_tiles"] == 0 and st["n_head"] == 0 and st["n_all"] == 0 and st["share_choice"] == -1 and st["share_samples"] == 0, (launch, st)
+    finally:
+        mem.set_option("traverse.share_trial", 1); mem.set_option("traverse.quad_head", 20)
+    mem.free(d_rays); mem.free(d_hits); grid.free(); mem.free(d_tris)
+
+
 def test_policy_state_machine_under_a_random_sequence_of_launches(mem):
     """The measured dispatch policy (share trial, order or no order, head share, all tiles, re-trials, hint slots taken over by other buffers, another traversal image
     under the same buffers) is a state machine per ray buffer; whatever state a sequence of calls leaves it in, a launch gives the oracle's hits.  300 launches over SIX
