@@ -807,97 +807,113 @@ struct Arena {
     void drop(void* p) { if (!base || p < base || p >= base + size) tmp.drop(p); }
 };
 
-int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid* grid, BuildK k, const BBox& gb, float snd_density, Temps& tmp) {
-    hipStream_t st = ctx->stream;
+// One construction's level loop: the state the three phases share, the phases as its functions (hagrid_build_grid runs them in this order).
+struct LevelBuild {
+    hagrid_ctx* ctx; hipStream_t st; Arena ar;
+    const float4* tris; int num_tris; BuildK k; const BBox& gb; float snd_density;
+    std::vector<GLevel> levels;
+    hagrid_build_counts& bc;                     // sizes of this construction (diagnostics)
+    // top_level -> subdivide
+    int* log_dims = nullptr; int num_new_cells = 0, shift = 0;
+
+    LevelBuild(hagrid_ctx* c, Temps& tmp, const float4* t, int n, const BuildK& k_, const BBox& b, float snd)
+        : ctx(c), st(c->stream), ar(c, tmp, n), tris(t), num_tris(n), k(k_), gb(b), snd_density(snd), bc(c->counts) {}
+
+    // The per-cell buffers of a level of `cells` cells whose references fill at most `tiles` tiles (its references are requested by the caller: the top
+    // level asks for them first, a child level once their number is known).  All seven requests are made before any is checked.
+    bool get_cell_buffers(GLevel& V, size_t cells, size_t tiles) {
+        V.cells = ar.get<Cell>(cells); V.entries = ar.get<uint32_t>(cells + 1);
+        V.cell_counts = ar.get<int>(cells); V.seg_begin = ar.get<int>(cells + 1);
+        V.tile_first = ar.get<int>(tiles + 2);
+        V.start_cell = ar.get<int>(cells); V.ref_begin = ar.get<int>(cells);
+        return V.cells && V.entries && V.cell_counts && V.seg_begin && V.tile_first && V.start_cell && V.ref_begin;
+    }
+    void record_level(int level, const GLevel& P, int kept) {
+        if (level < HAGRID_MAX_LEVELS) { bc.level_refs[level] = P.num_refs; bc.level_cells[level] = P.num_cells; bc.level_kept[level] = kept; bc.num_levels = level + 1; }
+    }
+    int top_level();
+    int subdivide();
+    int concat_levels(hagrid_grid* grid);
+};
+
+// ---- reference counts, per-cell depth, shift (first_build_iter, build.cu:470-512) ----
+int LevelBuild::top_level() {
     int* dsc = ctx->dscratch;
-    Arena ar(ctx, tmp, num_tris);
     const ivec3 dims = k.dims;
     const int num_top = dims.x * dims.y * dims.z;
-
-    // ---- reference counts, per-cell depth, shift (first_build_iter, build.cu:470-512) ----
     int* counts = ar.get<int>(size_t(num_tris));
     int* start_emit = ar.get<int>(size_t(num_tris));
     int* refs_per_cell = ar.get<int>(size_t(num_top));
-    int* log_dims = ar.get<int>(size_t(num_top));
-    int* const partials = nullptr;               // (the look-back scans need none)
+    log_dims = ar.get<int>(size_t(num_top));
     if (!counts || !start_emit || !refs_per_cell || !log_dims) return HAGRID_ENOMEM;
     HG_HIP(ctx, hipMemsetAsync(refs_per_cell, 0, size_t(num_top) * sizeof(int), st));
-    int* big_list = ar.get<int>(size_t(num_tris));               // primitives of kCoopCells cells and more (top_range_sizes); their number in dsc[2]
+    int* big_list = ar.get<int>(size_t(num_tris));               // primitives of kCoopCells cells and more (top_range_sizes); their number in dsc[kScrBuildNumBig]
     if (!big_list) return HAGRID_ENOMEM;
-    top_range_sizes<<<grid_blocks(num_tris, kBlock), kBlock, 0, st>>>(tris, num_tris, k, counts, big_list, dsc + 2); HG_DBG(ctx);
-    if (!ctx_scan<int>(ctx, PlainIn{counts}, PlainOut{start_emit, dsc + 3}, num_tris, partials, (const int*)nullptr, dsc + 0)) return HAGRID_ENOMEM;
+    top_range_sizes<<<grid_blocks(num_tris, kBlock), kBlock, 0, st>>>(tris, num_tris, k, counts, big_list, dsc + kScrBuildNumBig); HG_DBG(ctx);
+    if (!ctx_scan<int>(ctx, PlainIn{counts}, PlainOut{start_emit, dsc + kScrBuildTooLarge}, num_tris, (int*)nullptr, (const int*)nullptr, dsc + kScrBuildTopRefs)) return HAGRID_ENOMEM;
     int R0 = 0, num_big = 0;
     {
         int h[4];
         HG_TRY(read_back(ctx, dsc, h, sizeof(h)));
-        R0 = h[0]; num_big = h[2];
-        if (h[3]) R0 = -1;                       // a prefix left the range (PlainOut): the true total is 2^30 or more, whatever its low 32 bits say
+        R0 = h[kScrBuildTopRefs]; num_big = h[kScrBuildNumBig];
+        if (h[kScrBuildTooLarge]) R0 = -1;       // a prefix left the range (PlainOut): the true total is 2^30 or more, whatever its low 32 bits say
     }
     if (R0 < 0 || R0 > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many top-level references");
     ar.drop(counts);
     int* pair_rank = ar.get<int>(size_t(R0) + 1);
     if (!pair_rank) return HAGRID_ENOMEM;
     const int prim_blocks = grid_blocks(num_tris, kBlock), big_blocks = std::min(num_big, 2048);      // (the large primitives' workgroups ride behind the others' in the same launches)
-    count_top_refs<<<prim_blocks + big_blocks, kBlock, 0, st>>>(tris, num_tris, k, start_emit, refs_per_cell, pair_rank, big_list, dsc + 2, prim_blocks); HG_DBG(ctx);
-    top_log_dims<<<grid_blocks(num_top, kBlock), kBlock, 0, st>>>(refs_per_cell, num_top, k, snd_density, log_dims, dsc + 1); HG_DBG(ctx);
+    count_top_refs<<<prim_blocks + big_blocks, kBlock, 0, st>>>(tris, num_tris, k, start_emit, refs_per_cell, pair_rank, big_list, dsc + kScrBuildNumBig, prim_blocks); HG_DBG(ctx);
+    top_log_dims<<<grid_blocks(num_top, kBlock), kBlock, 0, st>>>(refs_per_cell, num_top, k, snd_density, log_dims, dsc + kScrBuildShift); HG_DBG(ctx);
 
-    std::vector<GLevel> levels;
     GLevel L;
     L.num_refs = R0; L.num_cells = num_top;
     L.num_tiles = grid_blocks(R0, kTileRefs);
     L.refs = ar.get<int2>(size_t(R0) + 1);
-    L.cells = ar.get<Cell>(size_t(num_top)); L.entries = ar.get<uint32_t>(size_t(num_top) + 1);
-    L.cell_counts = ar.get<int>(size_t(num_top)); L.seg_begin = ar.get<int>(size_t(num_top) + 1);
-    L.tile_first = ar.get<int>(size_t(L.num_tiles) + 2);
-    L.start_cell = ar.get<int>(size_t(num_top)); L.ref_begin = ar.get<int>(size_t(num_top));
-    if (!L.refs || !L.cells || !L.entries || !L.cell_counts || !L.seg_begin || !L.tile_first || !L.start_cell || !L.ref_begin) return HAGRID_ENOMEM;
-    if (!ctx_scan<int>(ctx, SegIn{refs_per_cell}, SegOut{refs_per_cell, L.seg_begin, L.tile_first, L.cells, L.entries, L.cell_counts, log_dims, dsc + 1, dims}, num_top, partials,
+    const bool have_cell_buffers = get_cell_buffers(L, size_t(num_top), size_t(L.num_tiles));
+    if (!L.refs || !have_cell_buffers) return HAGRID_ENOMEM;
+    if (!ctx_scan<int>(ctx, SegIn{refs_per_cell}, SegOut{refs_per_cell, L.seg_begin, L.tile_first, L.cells, L.entries, L.cell_counts, log_dims, dsc + kScrBuildShift, dims}, num_top, (int*)nullptr,
                        (const int*)nullptr, (int*)nullptr)) return HAGRID_ENOMEM;
-    hagrid_build_counts& bc = ctx->counts;
     memset(&bc, 0, sizeof(bc));
     bc.num_tris = num_tris; bc.top_cells = num_top; bc.top_refs = R0;
-    emit_top_refs<<<prim_blocks + big_blocks, kBlock, 0, st>>>(tris, num_tris, k, dsc + 1, gb.extents(), start_emit, pair_rank, L.seg_begin, L.refs, log_dims, L.entries, big_list, dsc + 2, prim_blocks); HG_DBG(ctx);
+    emit_top_refs<<<prim_blocks + big_blocks, kBlock, 0, st>>>(tris, num_tris, k, dsc + kScrBuildShift, gb.extents(), start_emit, pair_rank, L.seg_begin, L.refs, log_dims, L.entries, big_list, dsc + kScrBuildNumBig, prim_blocks); HG_DBG(ctx);
     levels.push_back(L);
 
-    // ---- subdivision, one level per iteration (build_iter, build.cu:527-619) ----
-    // tot (four words per level, zeroed by the caller): {cells of the next level, kept references of this level, {references, cells} of the level after the
-    // next: the total of the scan over the new cells}
-    {
-        if (!ctx_scan<int>(ctx, ChildCountIn{L.entries}, UpdateEntriesOut{L.entries, dsc + 3}, num_top, (int*)nullptr, (const int*)nullptr, dsc + 8)) return HAGRID_ENOMEM;
-    }
-    int num_new_cells = 0, shift = 0;
-    {   // the shift (dsc[1], top_log_dims) and the cells of the next level (dsc[8]) in one round trip
+    // the cells of the next level: the first of the level totals that subdivide() goes on with
+    if (!ctx_scan<int>(ctx, ChildCountIn{L.entries}, UpdateEntriesOut{L.entries, dsc + kScrBuildTooLarge}, num_top, (int*)nullptr, (const int*)nullptr, dsc + kScrBuildLevelTotals)) return HAGRID_ENOMEM;
+    {   // the shift (top_log_dims) and the cells of the next level in one round trip: words [kScrBuildShift, kScrBuildLevelTotals]
         int h[8];
-        HG_TRY(read_back(ctx, dsc + 1, h, sizeof(h)));
-        shift = h[0]; num_new_cells = h[7];
-        if (h[2]) num_new_cells = -1;            // a prefix left the range (UpdateEntriesOut; dsc[3] was zero when the reference total passed)
+        HG_TRY(read_back(ctx, dsc + kScrBuildShift, h, sizeof(h)));
+        shift = h[0]; num_new_cells = h[kScrBuildLevelTotals - kScrBuildShift];
+        if (h[kScrBuildTooLarge - kScrBuildShift]) num_new_cells = -1;      // a prefix left the range (UpdateEntriesOut; the word was zero when the reference total passed)
     }
-    if (shift >= 24) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many levels");
+    if (shift >= kBuildMaxLevels) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many levels");
     k.shift = shift;
     k.cell_size = gb.extents() / vec3(dims << shift);
     ar.drop(start_emit); ar.drop(pair_rank); ar.drop(refs_per_cell);
+    return HAGRID_OK;
+}
+
+// ---- subdivision, one level per iteration (build_iter, build.cu:527-619) ----
+// tot (four words per level, zeroed by the caller): {cells of the next level, kept references of this level, {references, cells} of the level after the
+// next: the total of the scan over the new cells}
+int LevelBuild::subdivide() {
     for (int level = 0;; level++) {
         GLevel& P = levels.back();
-        int* tot = dsc + 8 + 4 * level;
+        int* tot = ctx->dscratch + kScrBuildLevelTotals + 4 * level;
         if (num_new_cells < 0 || num_new_cells > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: level too large");
-        if ((int)levels.size() >= 24) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many levels");
+        if ((int)levels.size() >= kBuildMaxLevels) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many levels");
         const bool last = num_new_cells == 0;
         if (last && level > 0) {
             // no cell of this level splits: its references stay where they are, every count is known (build.cu:583-587)
-            if (level < HAGRID_MAX_LEVELS) { bc.level_refs[level] = P.num_refs; bc.level_cells[level] = P.num_cells; bc.level_kept[level] = P.num_refs; bc.num_levels = level + 1; }
+            record_level(level, P, P.num_refs);
             break;
         }
         GLevel N;
         N.num_cells = num_new_cells;
         unsigned char* masks = ar.get<unsigned char>(size_t(P.num_refs) + 1);
         if (!masks) return HAGRID_ENOMEM;
-        if (!last) {
-            N.cells = ar.get<Cell>(size_t(num_new_cells)); N.entries = ar.get<uint32_t>(size_t(num_new_cells) + 1);
-            N.cell_counts = ar.get<int>(size_t(num_new_cells)); N.seg_begin = ar.get<int>(size_t(num_new_cells) + 1);
-            N.tile_first = ar.get<int>(size_t(grid_blocks(8ll * P.num_refs, kTileRefs)) + 2);
-            N.start_cell = ar.get<int>(size_t(num_new_cells)); N.ref_begin = ar.get<int>(size_t(num_new_cells));
-            if (!N.cells || !N.entries || !N.cell_counts || !N.seg_begin || !N.tile_first || !N.start_cell || !N.ref_begin) return HAGRID_ENOMEM;
-        }
+        if (!last && !get_cell_buffers(N, size_t(num_new_cells), size_t(grid_blocks(8ll * P.num_refs, kTileRefs)))) return HAGRID_ENOMEM;
         if (P.num_refs > 0) {
             classify_refs<<<std::min(P.num_tiles, 4096), kBlock, 0, st>>>(P.refs, P.seg_begin, P.num_cells, P.num_refs, P.tile_first, P.num_tiles, level == 0 ? 1 : 0,
                                                                              tris, P.cells, P.entries, k, masks, P.cell_counts, N.cells, N.cell_counts, N.entries, tot + 1); HG_DBG(ctx);
@@ -910,7 +926,7 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
         int h3[3] = {0, 0, 0};                        // kept, references of the next level, cells of the level after it
         HG_TRY(read_back(ctx, tot + 1, h3, sizeof(h3)));
         if (h3[0] < 0) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: level too large");       // (ChildSegOut: a prefix of the next level's references or cells left the range)
-        if (level < HAGRID_MAX_LEVELS) { bc.level_refs[level] = P.num_refs; bc.level_cells[level] = P.num_cells; bc.level_kept[level] = h3[0]; bc.num_levels = level + 1; }
+        record_level(level, P, h3[0]);
         if (last) { ar.drop(masks); break; }
         const int num_children = h3[1];
         if (num_children < 0 || num_children > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: level too large");
@@ -926,19 +942,21 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
         levels.push_back(N);
     }
     ar.drop(log_dims);
+    return HAGRID_OK;
+}
 
-    // ---- concat_levels (build.cu:621-716) ----
+// ---- concat_levels (build.cu:621-716) ----
+int LevelBuild::concat_levels(hagrid_grid* grid) {
+    const ivec3 dims = k.dims;
     const int num_levels = (int)levels.size();
     long long total_cells_ll = 0;
-    int max_cells = 0;
-    for (auto& V : levels) { total_cells_ll += V.num_cells; max_cells = std::max(max_cells, V.num_cells); }
+    for (auto& V : levels) total_cells_ll += V.num_cells;
     if (total_cells_ll > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: too many voxel map entries");
     const int total_cells = int(total_cells_ll);
-    Int2* const part2 = nullptr;                           // (the look-back scans need no partials)
-    Int2* carry = reinterpret_cast<Int2*>(dsc + 128);      // one Int2 per level, chained on the device
+    Int2* carry = reinterpret_cast<Int2*>(ctx->dscratch + kScrBuildCarry);      // one Int2 per level, chained on the device
     for (int l = 0; l < num_levels; l++) {
         GLevel& V = levels[l];
-        if (!ctx_scan<Int2>(ctx, LeafIn{V.entries, V.cell_counts}, LeafOut{V.start_cell, V.ref_begin}, V.num_cells, part2,
+        if (!ctx_scan<Int2>(ctx, LeafIn{V.entries, V.cell_counts}, LeafOut{V.start_cell, V.ref_begin}, V.num_cells, (Int2*)nullptr,
                             l ? carry + (l - 1) : (const Int2*)nullptr, carry + l)) return HAGRID_ENOMEM;
     }
     int hf[2];
@@ -980,6 +998,19 @@ int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid*
     return HAGRID_OK;
 }
 
+int build_levels(hagrid_ctx* ctx, const float4* tris, int num_tris, hagrid_grid* grid, const BuildK& k, const BBox& gb, float snd_density, Temps& tmp) {
+    LevelBuild b(ctx, tmp, tris, num_tris, k, gb, snd_density);
+    HG_TRY(b.top_level());
+    HG_TRY(b.subdivide());
+    return b.concat_levels(grid);
+}
+
+int check_box_extent(hagrid_ctx* ctx, const BBox& gb) {
+    const vec3 e = gb.extents();
+    if (!(e.x <= FLT_MAX && e.y <= FLT_MAX && e.z <= FLT_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: the extent of the scene box is not finite");
+    return HAGRID_OK;
+}
+
 } // namespace
 
 extern "C" int hagrid_build_grid(hagrid_ctx* ctx, const void* tris_v, int num_tris, hagrid_grid* grid,
@@ -991,7 +1022,7 @@ extern "C" int hagrid_build_grid(hagrid_ctx* ctx, const void* tris_v, int num_tr
     const float4* tris = static_cast<const float4*>(tris_v);
     hipStream_t st = ctx->stream;
     Temps tmp(ctx);
-    int* dsc = ctx->dscratch;                       // device scalars
+    int* dsc = ctx->dscratch;                       // device scalars: ALL of them are cleared, the fixed-owner words of ctx.h (traversal's cached row lengths) included
     HG_HIP(ctx, hipMemsetAsync(dsc, 0, 256 * sizeof(int), st));
 
     // ---- scene box, top-level resolution (build.cu:725-740) ----
@@ -1011,10 +1042,7 @@ extern "C" int hagrid_build_grid(hagrid_ctx* ctx, const void* tris_v, int num_tr
         HG_FAIL(ctx, HAGRID_EINVAL, msg);
     }
     BBox gb(vec3(hb[0], hb[1], hb[2]), vec3(hb[3], hb[4], hb[5]));
-    {
-        const vec3 e = gb.extents();
-        if (!(e.x <= FLT_MAX && e.y <= FLT_MAX && e.z <= FLT_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: the extent of the scene box is not finite");
-    }
+    HG_TRY(check_box_extent(ctx, gb));
     if (!grid_dims_defined(gb, num_tris, top_density)) gb = widen_scene_box(gb);      // a flat scene: the widened box is the grid's
     ivec3 dims = compute_grid_dims(gb, num_tris, top_density);
     if (dims.x > 0x3fffffff || dims.y > 0x3fffffff || dims.z > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: top-level grid too large");
@@ -1024,10 +1052,7 @@ extern "C" int hagrid_build_grid(hagrid_ctx* ctx, const void* tris_v, int num_tr
     gb.max += ext * 0.001f;
     const long long num_top_ll = (long long)dims.x * dims.y * dims.z;
     if (num_top_ll > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: top-level grid too large");
-    {   // the enlarged box of an admissible scene can still leave float's range
-        const vec3 e = gb.extents();
-        if (!(e.x <= FLT_MAX && e.y <= FLT_MAX && e.z <= FLT_MAX)) HG_FAIL(ctx, HAGRID_ERANGE, "build_grid: the extent of the scene box is not finite");
-    }
+    HG_TRY(check_box_extent(ctx, gb));      // the enlarged box of an admissible scene can still leave float's range
 
     BuildK k;
     k.dims = dims; k.shift = 0; k.bmin = gb.min; k.bmax = gb.max; k.cell_size = vec3(0.0f);

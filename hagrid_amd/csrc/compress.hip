@@ -57,7 +57,7 @@ extern "C" int hagrid_compress_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
     if (!partials || !small) { hagrid_mem_free(ctx, partials); hagrid_mem_free(ctx, small); return HAGRID_ENOMEM; }
     // the list lengths are known from the cells alone: total first (one small reduction + read-back), then
     // a single scan whose output functor writes the small cells and copies the lists
-    int* total = ctx->dscratch;
+    int* total = ctx->dscratch + kScrCompressTotal;
     scan_partials<int, SentinelIn><<<std::max(scan_num_tiles(n), 1), kBlock, 0, st>>>(SentinelIn{cells}, n, partials); HG_DBG(ctx);
     scan_spine<int><<<1, kBlock, 0, st>>>(partials, scan_num_tiles(n), nullptr, total); HG_DBG(ctx);
     int h = 0;

@@ -55,9 +55,14 @@ struct TravImageCache {
 
 } // namespace hagrid_impl
 
-// Words of the context's pinned mailbox and of its device scratch that have a fixed owner (the first 256 mailbox words are the read-back area of the
-// construction passes; every other use of dscratch is a pass-local counter named where it is used).
+// Words of the context's pinned mailbox and of its device scratch (the first 256 mailbox words are the read-back area of the construction passes).
+// Scratch words are of two kinds: the four of ScratchWord have a fixed owner and keep their value between calls; every other word belongs to the pass that
+// is running and is named in that pass's enum below.  A pass may use any word below kScrRowLenBinned; the static_asserts behind the enums say that the
+// ranges of one pass do not meet each other and stay below that word.
+// One crossing is known and kept: hagrid_build_grid clears ALL kScratchWords words, the fixed-owner words included -- a construction also forgets the row
+// lengths that traversal caches per ray buffer in dscratch[kScrRowLen + slot].
 namespace hagrid_impl {
+constexpr int kScratchWords = 256;
 enum MailboxWord : int {
     kMbxRowLen = 300,          // + hint slot (4): row length found for a ray buffer (traverse.hip; copied behind the launch, polled)
     kMbxOrderStale = 304,      // + hint slot (4): epoch of a tile order whose buffer holds other rays now (written by the kernel's first wavefront, polled)
@@ -71,6 +76,50 @@ enum ScratchWord : int {
     kScrMaxRef = 240,          // trav_image.hip: largest reference id
     kScrBlobFlag = 250,        // blob.hip: validation flag
 };
+
+// ---- the words of the running pass ----
+constexpr int kBuildMaxLevels = 24;        // build_grid: a grid of this many levels is refused ("too many levels"), so level < kBuildMaxLevels wherever a level indexes scratch
+constexpr int kExpandMaxListed = 48;       // expand_grid: listed passes that have a count word ("expand.max_listed" is capped here)
+constexpr int kImageMaxLevels = 16;        // trav_image.hip, general layout: levels the listing follows (level <= kImageMaxLevels indexes a count word)
+enum BuildScratch : int {                  // build.hip (the whole scratch is zero when the level loop starts)
+    kScrBuildTopRefs = 0,                  // references of the top level (total of the scan over the primitives' counts)
+    kScrBuildShift = 1,                    // top_log_dims: the deepest level any top-level cell asks for
+    kScrBuildNumBig = 2,                   // top_range_sizes: primitives of kCoopCells cells and more
+    kScrBuildTooLarge = 3,                 // a prefix of a scan left the range (PlainOut, UpdateEntriesOut)
+    kScrBuildLevelTotals = 8,              // + 4 * level: {cells of the next level, kept references, {references, cells} of the level after the next}
+    kScrBuildCarry = 128,                  // + 2 * level: an Int2 {cells, references} per level, chained on the device (concat_levels)
+};
+enum MergeScratch : int {                  // merge.hip
+    kScrMergeTotals = 0,                   // + 2 * axis: the Int2 {cells, references} behind every compacting pass of an iteration
+    kScrMergeBooks = 16,                   // in place: cursor, live cells, live references, overflow (1 + axis of the first pass that did not fit)
+    kScrMergeSnapshots = 20,               // + 2 * axis: live cells / references behind each of the three passes in place (read back with the books)
+    kScrMergeIpTotal = 26,                 // in place: the Int2 total of a pass's scan
+};
+enum FlattenScratch : int { kScrFlattenCarry = 0 };        // + group: carry[0] = offsets[0], carry[1 + g] = end of group g; at most HAGRID_MAX_LEVELS + 2 words are read back
+enum CompressScratch : int { kScrCompressTotal = 0 };      // references of the compressed grid
+enum ExpandScratch : int { kScrExpandCounts = 160 };       // + listed pass (kExpandMaxListed): the length of its list
+enum DistanceScratch : int { kScrDistTasks = 0, kScrDistTooLarge = 1 };      // distance.hip: the number of tasks; their sum left 31 bits
+enum ImageScratch : int {                  // trav_image.hip (hagrid_setup_traversal)
+    kScrImgStatus = 160,                   // general layout: [0] does not fit | [1] lists with an id beyond the field | [2] wide records
+    kScrImgLevelCounts = 164,              // general layout, + level (<= kImageMaxLevels): inner entries listed per level
+    kScrImgClearedWords = 24,              // ... status and counts are cleared together: this many words from kScrImgStatus
+    kScrImgTableTotal = 224,               // block layouts: records of the table layout (total of the scan over the block sizes)
+    kScrImgSlimStatus = 228,               // block layouts: the three status words of image_slim_fill
+};
+constexpr bool scr_apart(int a, int na, int b, int nb) { return a + na <= b || b + nb <= a; }      // [a, a + na) and [b, b + nb) do not meet
+constexpr bool scr_free(int a, int n) { return a >= 0 && a + n <= kScrRowLenBinned; }                // [a, a + n) is the running pass's to use
+static_assert(kScrRowLenBinned + 2 <= kScrRowLen && kScrRowLen + 4 <= kScrMaxRef && kScrMaxRef < kScrBlobFlag && kScrBlobFlag < kScratchWords, "fixed-owner words");
+// build_grid: four scalars, four totals per level, a carry per level; the read-backs take [0, 4) and [kScrBuildShift, kScrBuildShift + 8) in one piece each
+static_assert(kScrBuildTooLarge + 1 <= kScrBuildLevelTotals && kScrBuildShift + 8 == kScrBuildLevelTotals + 1, "build_grid: scalars and the first level's total");
+static_assert(scr_apart(kScrBuildLevelTotals, 4 * kBuildMaxLevels, kScrBuildCarry, 2 * kBuildMaxLevels), "build_grid: totals and carries");
+static_assert(scr_free(kScrBuildLevelTotals, 4 * kBuildMaxLevels) && scr_free(kScrBuildCarry, 2 * kBuildMaxLevels), "build_grid: level-indexed words");
+// merge_grid: the books and the snapshots are read back as ten consecutive words
+static_assert(kScrMergeTotals + 6 <= kScrMergeBooks && kScrMergeBooks + 4 == kScrMergeSnapshots && kScrMergeSnapshots + 6 == kScrMergeIpTotal && scr_free(kScrMergeIpTotal, 2), "merge_grid");
+static_assert(scr_free(kScrFlattenCarry, HAGRID_MAX_LEVELS + 2), "flatten_grid: a carry per group of levels");
+static_assert(scr_free(kScrExpandCounts, kExpandMaxListed), "expand_grid");
+static_assert(kScrDistTasks + 1 == kScrDistTooLarge && scr_free(kScrDistTasks, 2) && scr_free(kScrCompressTotal, 1), "distance_lattice (its two words are cleared together), compress_grid");
+static_assert(kScrImgStatus + 3 <= kScrImgLevelCounts && kScrImgLevelCounts + kImageMaxLevels + 1 <= kScrImgStatus + kScrImgClearedWords, "setup_traversal: the general layout's words are cleared together");
+static_assert(scr_apart(kScrImgStatus, kScrImgClearedWords, kScrImgTableTotal, 1) && scr_apart(kScrImgTableTotal, 1, kScrImgSlimStatus, 3) && scr_free(kScrImgSlimStatus, 3), "setup_traversal");
 } // namespace hagrid_impl
 
 struct hagrid_ctx {
@@ -109,7 +158,7 @@ struct hagrid_ctx {
     int opt_expand_voxel_map = 1;     // expand_grid: the voxel map resolved into one word per voxel for the passes' look-ups (expand.hip); 0: the chain through the levels
     int opt_expand_subset_only = 1;   // expand_grid: 1 = the reference's compiled setting, 0 = precise (compute_overlap)
     int opt_expand_listed = 1;        // expand_grid, tests: 0 = the optional list of cells is not taken, as if its allocation had failed (every iteration is an all-cells pass)
-    int opt_expand_max_listed = 48;   // expand_grid, tests: listed passes before the all-cells pass takes over again (0 .. 48: their counts live in dscratch[160 .. 208))
+    int opt_expand_max_listed = hagrid_impl::kExpandMaxListed;   // expand_grid, tests: listed passes before the all-cells pass takes over again (0 .. kExpandMaxListed: a count word each, kScrExpandCounts)
     int opt_distance_by_triangle = 0; // distance_lattice, tests: 1 = the splat takes triangles, as when the sum of the task counts leaves 31 bits
     int opt_image_width = 0;    // tile packets: -1 off, 0 detect the row length on the device, > 0 row length given by the caller
     int opt_band_rows = 0;      // tile packets: rows of super-tiles per band; 0 = as many as make the in-flight tiles a square block of the image

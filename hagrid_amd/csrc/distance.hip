@@ -155,16 +155,16 @@ extern "C" int hagrid_distance_lattice(hagrid_ctx* ctx, const hagrid_grid* grid,
     HG_HIP(ctx, hipMemsetAsync(workspace, 0xff, size_t(voxels) * 8, st));
     PoolTemps tmp(ctx);
     if (a.num_tris > 0) {
-        int* dsc = ctx->dscratch;              // [0]: the number of tasks, [1]: the sum left 31 bits
+        int* tasks = ctx->dscratch + kScrDistTasks; int* too_large = ctx->dscratch + kScrDistTooLarge;      // the number of tasks; their sum left 31 bits
         a.sizes = tmp.get<int>(size_t(a.num_tris));
         if (!a.sizes) return HAGRID_ENOMEM;
-        a.total = dsc + 0; a.too_large = dsc + 1;
-        HG_HIP(ctx, hipMemsetAsync(dsc, 0, 2 * sizeof(int), st));
+        a.total = tasks; a.too_large = too_large;
+        HG_HIP(ctx, hipMemsetAsync(tasks, 0, 2 * sizeof(int), st));
         const int waves = std::max(ctx->num_cus, 1) * 32;
         a.mode = kSize;
         distance_kernel<<<std::min(grid_blocks(a.num_tris, 64), waves), 64, 0, st>>>(a); HG_DBG(ctx);
-        HG_TRY(scan_plain(ctx, a.sizes, a.sizes, a.num_tris, dsc + 0, dsc + 1));
-        if (ctx->opt_distance_by_triangle) HG_HIP(ctx, hipMemsetAsync(dsc + 1, 0x01, sizeof(int), st));      // (tests: the word a sum beyond 31 bits leaves)
+        HG_TRY(scan_plain(ctx, a.sizes, a.sizes, a.num_tris, tasks, too_large));
+        if (ctx->opt_distance_by_triangle) HG_HIP(ctx, hipMemsetAsync(too_large, 0x01, sizeof(int), st));      // (tests: the word a sum beyond 31 bits leaves)
         a.mode = kSplat;
         distance_kernel<<<waves, 64, 0, st>>>(a); HG_DBG(ctx);
     }

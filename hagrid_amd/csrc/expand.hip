@@ -276,6 +276,25 @@ void listed_step(hipStream_t st, const ExpandK& k, const Entry* entries, const i
     expand_listed<axis, SUBSET_ONLY><<<grid_blocks(2ll * n, kBlock), kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, list, count);
 }
 
+// One iteration (expansion_iter, expand.cu:184-197): a pass per axis, `cells` and `other` swapping behind each.  Listed: over the cells the pass before
+// touched, counts[0 .. 3) taking the lengths of the three lists; all cells: over every cell.
+template <bool SUBSET_ONLY>
+void listed_iteration(hipStream_t st, const ExpandK& k, const Entry* entries, const int* refs, const float4* tris, Cell*& cells, Cell*& other,
+                      unsigned char* flags, int n, int* list, int* counts) {
+    listed_step<0, SUBSET_ONLY>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + 0); std::swap(cells, other);
+    listed_step<1, SUBSET_ONLY>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + 1); std::swap(cells, other);
+    listed_step<2, SUBSET_ONLY>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + 2); std::swap(cells, other);
+}
+template <bool SUBSET_ONLY>
+void all_cells_iteration(hagrid_ctx* ctx, const ExpandK& k, const Entry* entries, const int* refs, const float4* tris, Cell*& cells, Cell*& other,
+                         unsigned char* flags, int n) {
+    hipStream_t st = ctx->stream;
+    const int blocks = grid_blocks(n, kBlock);
+    overlap_step<0, SUBSET_ONLY><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
+    overlap_step<1, SUBSET_ONLY><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
+    overlap_step<2, SUBSET_ONLY><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
+}
+
 } // namespace
 
 extern "C" int hagrid_expand_grid(hagrid_ctx* ctx, hagrid_grid* grid, const void* tris_v, int iters) {
@@ -304,38 +323,24 @@ extern "C" int hagrid_expand_grid(hagrid_ctx* ctx, hagrid_grid* grid, const void
     (void)hipMemsetAsync(flags, 0xFF, size_t(n), st);                     // expand.cu:206 (errors surface at the final check)
     const Entry* entries = static_cast<const Entry*>(grid->entries);
     const int* refs = static_cast<const int*>(grid->ref_ids);
-    const int blocks = grid_blocks(n, kBlock);
     int* list = iters > 1 && ctx->opt_expand_listed ? pool_try_alloc<int>(ctx, size_t(n)) : nullptr;      // (without it the later iterations fall back to the all-cells pass)
     const long long voxels = (long long)k.dims.x * k.dims.y * k.dims.z;
     int* voxel_cells = (ctx->opt_expand_voxel_map && voxels <= (1ll << 28)) ? pool_try_alloc<int>(ctx, size_t(voxels)) : nullptr;   // (without it: the chain through the voxel map)
     k.voxel_cells = voxel_cells;
     if (voxel_cells) { ExpandK kf = k; kf.voxel_cells = nullptr; fill_voxel_cells<<<grid_blocks(voxels, kBlock), kBlock, 0, st>>>(kf, entries, voxel_cells, int(voxels)); HG_DBG(ctx); }
-    int* counts = ctx->dscratch + 160;             // one list length per listed pass
-    const int max_listed = std::min(std::max(ctx->opt_expand_max_listed, 0), 48);     // (48 unless a test lowers it: the switch back in mid-growth)
-    if (list) (void)hipMemsetAsync(counts, 0, 48 * sizeof(int), st);
+    int* counts = ctx->dscratch + kScrExpandCounts;      // one list length per listed pass
+    const int max_listed = std::min(std::max(ctx->opt_expand_max_listed, 0), kExpandMaxListed);     // (all of them unless a test lowers it: the switch back in mid-growth)
+    if (list) (void)hipMemsetAsync(counts, 0, kExpandMaxListed * sizeof(int), st);
     int listed = 0;
     for (int it = 0; it < iters; it++) {                                               // expansion_iter, expand.cu:184-197
         if (it > 0 && list && listed + 3 <= max_listed) {
-            if (subset_only) {
-                listed_step<0, true>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed++); std::swap(cells, other);
-                listed_step<1, true>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed++); std::swap(cells, other);
-                listed_step<2, true>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed++); std::swap(cells, other);
-            } else {
-                listed_step<0, false>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed++); std::swap(cells, other);
-                listed_step<1, false>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed++); std::swap(cells, other);
-                listed_step<2, false>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed++); std::swap(cells, other);
-            }
+            if (subset_only) listed_iteration<true>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed);
+            else             listed_iteration<false>(st, k, entries, refs, tris, cells, other, flags, n, list, counts + listed);
+            listed += 3;
             continue;
         }
-        if (subset_only) {
-            overlap_step<0, true><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
-            overlap_step<1, true><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
-            overlap_step<2, true><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
-        } else {
-            overlap_step<0, false><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
-            overlap_step<1, false><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
-            overlap_step<2, false><<<blocks, kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, n); HG_DBG(ctx); std::swap(cells, other);
-        }
+        if (subset_only) all_cells_iteration<true>(ctx, k, entries, refs, tris, cells, other, flags, n);
+        else             all_cells_iteration<false>(ctx, k, entries, refs, tris, cells, other, flags, n);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -97,14 +97,14 @@ extern "C" int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
     const uint32_t* entries = static_cast<const uint32_t*>(grid->entries);
     auto first_of = [&](int i) { return i > 0 ? grid->offsets[i - 1] : 0; };
 
-    int* depths = pool_alloc<int>(ctx, size_t(num_entries) + 8);
-    int* start = pool_alloc<int>(ctx, size_t(num_entries) + 8);
-    uint32_t* collapsed = pool_alloc<uint32_t>(ctx, size_t(num_entries) + 8);      // the voxel map with its uniform subtrees collapsed (flatten.cu:115-124 does it in place)
+    PoolTemps tmp(ctx);                          // released on every exit
+    int* depths = tmp.get<int>(size_t(num_entries) + 8);
+    int* start = tmp.get<int>(size_t(num_entries) + 8);
+    uint32_t* collapsed = tmp.get<uint32_t>(size_t(num_entries) + 8);      // the voxel map with its uniform subtrees collapsed (flatten.cu:115-124 does it in place)
     int max_level = 0;
     for (int i = 0; i <= shift; i++) max_level = std::max(max_level, grid->offsets[i] - first_of(i));
-    int* partials = pool_alloc<int>(ctx, size_t(scan_num_tiles(max_level)) + 1);
-    auto release = [&]() { hagrid_mem_free(ctx, depths); hagrid_mem_free(ctx, start); hagrid_mem_free(ctx, partials); hagrid_mem_free(ctx, collapsed); };
-    if (!depths || !start || !partials || !collapsed) { release(); return HAGRID_ENOMEM; }
+    int* partials = tmp.get<int>(size_t(scan_num_tiles(max_level)) + 1);
+    if (!depths || !start || !partials || !collapsed) return HAGRID_ENOMEM;
     // (words no level covers -- none in a map of build_grid -- are taken over as they are)
     if (grid->offsets[shift] != num_entries) (void)hipMemcpyAsync(collapsed, entries, size_t(num_entries) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);      // (errors surface at the final check)
 
@@ -115,22 +115,22 @@ extern "C" int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
     }
     // insertion position of every flattened block (flatten.cu:127-141): the scans of levels 0, 3, 6, ... chain
     // through a device carry initialised with the number of top-level entries
-    int* carry = ctx->dscratch;                 // carry[0] = offsets[0], carry[1 + g] = end of group g
+    int* carry = ctx->dscratch + kScrFlattenCarry;      // carry[0] = offsets[0], carry[1 + g] = end of group g
     const int top_entries = grid->offsets[0];
     HG_HIP(ctx, hipMemcpyAsync(carry, &top_entries, sizeof(int), hipMemcpyHostToDevice, st));
     int groups = 0;
     for (int i = 0; i < shift; i += kFlatLevels, groups++) {
         const int first = first_of(i), num = grid->offsets[i] - first;
-        if (!ctx_scan<int>(ctx, BlockSizeIn{depths + first}, StartOut{start + first}, num, partials, carry + groups, carry + groups + 1)) { release(); return HAGRID_ENOMEM; }
+        if (!ctx_scan<int>(ctx, BlockSizeIn{depths + first}, StartOut{start + first}, num, partials, carry + groups, carry + groups + 1)) return HAGRID_ENOMEM;
     }
     int h[HAGRID_MAX_LEVELS + 2];
     int rc = read_back(ctx, carry, h, sizeof(int) * size_t(groups + 1));
-    if (rc != HAGRID_OK) { release(); return rc; }
+    if (rc != HAGRID_OK) return rc;
     const int total_entries = h[groups];
-    if (total_entries < top_entries || total_entries > 0x3fffffff) { release(); HG_FAIL(ctx, HAGRID_ERANGE, "flatten_grid: voxel map too large"); }
+    if (total_entries < top_entries || total_entries > 0x3fffffff) HG_FAIL(ctx, HAGRID_ERANGE, "flatten_grid: voxel map too large");
 
     uint32_t* out = pool_alloc<uint32_t>(ctx, size_t(total_entries));
-    if (!out) { release(); return HAGRID_ENOMEM; }
+    if (!out) return HAGRID_ENOMEM;
     copy_top<<<grid_blocks(top_entries, kBlock), kBlock, 0, st>>>(collapsed, start, depths, out, top_entries); HG_DBG(ctx);
     int new_offsets[HAGRID_MAX_LEVELS], num_new = 0;
     for (int i = 0, g = 0; i < shift; i += kFlatLevels, g++) {
@@ -141,8 +141,7 @@ extern "C" int hagrid_flatten_grid(hagrid_ctx* ctx, hagrid_grid* grid) {
     new_offsets[num_new++] = total_entries;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { release(); hagrid_mem_free(ctx, out); HG_FAIL(ctx, HAGRID_EHIP, hipGetErrorString(e)); }
-    release();
+    if (e != hipSuccess) { hagrid_mem_free(ctx, out); HG_FAIL(ctx, HAGRID_EHIP, hipGetErrorString(e)); }
     hagrid_mem_free(ctx, grid->entries);         // flatten.cu:168-170
     ctx->counts.flatten_entries_in = num_entries; ctx->counts.flatten_entries_out = total_entries;
     grid->entries = out;

@@ -210,7 +210,7 @@ extern "C" int hagrid_kat_lookup_entry(hagrid_ctx* ctx, const uint32_t* entries,
 
 extern "C" int hagrid_kat_detect_ray_rows(hagrid_ctx* ctx, const void* rays_dev, int num_rays, float bbox_diag, int32_t* row_len) {
     if (!ctx || !rays_dev || num_rays < 0 || !row_len) return HAGRID_EINVAL;
-    int* d = ctx->dscratch + 232;
+    int* d = ctx->dscratch + kScrRowLenBinned;
     TraverseArgs a;
     memset(&a, 0, sizeof(a));
     a.rays = static_cast<const float4*>(rays_dev);

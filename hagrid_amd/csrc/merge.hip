@@ -632,227 +632,225 @@ __global__ void __launch_bounds__(kBlock) remap_entries_kernel(uint32_t* __restr
     }
 }
 
-} // namespace
-
-extern "C" int hagrid_merge_grid(hagrid_ctx* ctx, hagrid_grid* grid, float alpha) {
-    if (!ctx || !grid) return HAGRID_EINVAL;
-    if (!grid->cells || !grid->entries || !grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, "merge_grid: incomplete (or compressed) grid");
-    trav_image_drop(ctx);            // the traversal image of this context describes a grid that is about to change
-    ctx->counts.merge_passes = 0;
-    ctx->counts.merged_cells = grid->num_cells; ctx->counts.merged_refs = grid->num_refs;
-    if (!(alpha > 0)) return HAGRID_OK;
-    HG_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
+// ---- one run of hagrid_merge_grid (host side): its state by owner, its phases as functions ----
+// hagrid_merge_grid: validate, allocate(), the iterations -- in_place_iteration / leave_in_place / compacting_passes / enter_in_place --, finish(rc).
+struct MergeRun {
+    hagrid_ctx* ctx; hagrid_grid* grid; hipStream_t st;
+    // the grid and its constants
     MergeK k;
-    k.top = ivec3(grid->dims[0], grid->dims[1], grid->dims[2]);
-    k.dims = k.top << grid->shift;
-    k.shift = grid->shift;
-    k.cell_size = (vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]) - vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2])) / vec3(k.dims);
-
-    // buffers sized for the un-merged grid (merge.cu:334-347); cells and refs ping-pong with grid arrays
-    const size_t nc0 = size_t(grid->num_cells), nr0 = size_t(grid->num_refs);
-    Cell* cells_b = pool_alloc<Cell>(ctx, nc0);
-    int* refs_b = pool_alloc<int>(ctx, nr0);
-    int* merge_counts = pool_alloc<int>(ctx, nc0 + 1);
-    int* nexts = pool_alloc<int>(ctx, nc0 + 1);
-    unsigned char* prevs = pool_alloc<unsigned char>(ctx, nc0 + 4);
-    unsigned char* cell_flags = pool_alloc<unsigned char>(ctx, nc0 + 4);
-    // per cell: the pass that made it (0: the construction); two buffers that swap with the cells.  One allocation: the halves are 256-byte aligned
-    const size_t stamp_stride = (nc0 + 4 + 255) & ~size_t(255);
-    unsigned char* stamps = pool_alloc<unsigned char>(ctx, 2 * stamp_stride);
-    unsigned char* stamps_other = stamps ? stamps + stamp_stride : nullptr;
-    unsigned char* const stamps_base = stamps;
-    const int max_tiles = grid_blocks(grid->num_cells, kMergeTile);
-    Int2* tile_sums = pool_alloc<Int2>(ctx, size_t(max_tiles) + 1);
-    Int2* partials = pool_alloc<Int2>(ctx, size_t(scan_num_tiles(max_tiles)) + 1);
-    Int2* total = reinterpret_cast<Int2*>(ctx->dscratch);
-    auto release = [&]() {
-        hagrid_mem_free(ctx, merge_counts); hagrid_mem_free(ctx, nexts); hagrid_mem_free(ctx, prevs); hagrid_mem_free(ctx, cell_flags);
-        hagrid_mem_free(ctx, tile_sums); hagrid_mem_free(ctx, partials); hagrid_mem_free(ctx, stamps_base);
-    };
-    if (!cells_b || !refs_b || !merge_counts || !nexts || !prevs || !cell_flags || !tile_sums || !partials || !stamps) {
-        // (nothing is queued yet, but the promise of the header is ONE state for every failure of this pass: the grid is gone)
-        release(); hagrid_mem_free(ctx, cells_b); hagrid_mem_free(ctx, refs_b);
-        hagrid_mem_free(ctx, grid->cells); hagrid_mem_free(ctx, grid->ref_ids);
-        grid->cells = nullptr; grid->ref_ids = nullptr; grid->num_cells = 0; grid->num_refs = 0;
-        return HAGRID_ENOMEM;
-    }
-
-    void* cells = grid->cells;
-    void* cells_other = cells_b;
-    int* refs = static_cast<int*>(grid->ref_ids);
-    uint32_t* entries = static_cast<uint32_t*>(grid->entries);
-    int num_cells = grid->num_cells, num_refs = grid->num_refs;
-    const int num_entries = grid->num_entries;
-    // 16-byte working records between the passes (CellFmt<true>) when the bounds fit 16 bits
-    const bool narrow = ctx->opt_merge_narrow && std::max(k.dims.x, std::max(k.dims.y, k.dims.z)) < 65536;
-
-    int rc = HAGRID_OK;
-    int prev_num_cells = 0, iter = 0, pass_tag = 0;
-    bool in_narrow = false;                                                // the caller's cells are 32-byte records
-    (void)hipMemsetAsync(prevs, 0, nc0, st);                               // tag 0 = never had a predecessor
-    hagrid_build_counts& bc = ctx->counts;                                 // sizes that entered the passes (diagnostics)
-    auto record = [&](int c, int r) {
-        if (bc.merge_passes < HAGRID_MAX_MERGE_PASSES) { bc.merge_cells[bc.merge_passes] = c; bc.merge_refs[bc.merge_passes] = r; bc.merge_passes++; }
-    };
-
+    size_t nc0, nr0;                               // cells and references of the un-merged grid: what every buffer is sized for
+    uint32_t* entries; int num_entries;
+    bool narrow;                                   // 16-byte working records between the passes (CellFmt<true>) when the bounds fit 16 bits
+    // the nine pool buffers, sized for the un-merged grid (merge.cu:334-347); the first two are the spares of the live arrays
+    void* cells_other = nullptr; int* refs_b = nullptr;
+    int* merge_counts = nullptr; int* nexts = nullptr; unsigned char* prevs = nullptr; unsigned char* cell_flags = nullptr;
+    unsigned char* stamps_base = nullptr;          // per cell: the pass that made it (0: the construction); two buffers that swap with the cells.  One allocation: the halves are 256-byte aligned
+    Int2* tile_sums = nullptr; Int2* partials = nullptr;
+    // the live arrays (they ping-pong with their spares, cells and refs with the grid's arrays)
+    void* cells; int* refs; int num_cells, num_refs;
+    bool in_narrow = false;                        // the caller's cells are 32-byte records
+    int pass_tag = 0;                              // the tag of the running pass in `prevs` (tags are bytes: 1 .. 255)
+    // the stamps
+    unsigned char* stamps = nullptr; unsigned char* stamps_other = nullptr;
+    int global_pass = 0;                           // passes run so far (the stamp of the cells the next one makes is global_pass + 1)
+    bool have_stamps = false;                      // `stamps` describes `cells`
+    int since[3] = {0, 0, 0};                      // the pass of the last evaluation of every axis
     // ---- iterations in place (see the kernels above): state of the mode ----
     // No buffer of its own: the explicit list ends live in `merge_counts`, the per-slot scratch of the mode (merged size / disappearing references,
     // dirty bytes per axis, "evaluated" tags) in the cell buffer that is not in use, and the merged lists go behind the live references of `refs`.
-    int global_pass = 0;                                                   // passes run so far (the stamp of the cells the next one makes is global_pass + 1)
-    bool have_stamps = false;                                              // `stamps` describes `cells`
-    int since[3] = {0, 0, 0};                                              // the pass of the last evaluation of every axis
     bool in_place = false;
-    int ip_slots = 0, ip_iters = 0, prev_mask = 0;
-    int* list_end = merge_counts;
+    int ip_slots = 0, ip_iters = 0;
+    int* list_end = nullptr;
     Int2* minfo = nullptr; unsigned char* dirty = nullptr; unsigned char* evaluated = nullptr;
-    int* books = ctx->dscratch + 16;                                      // cursor, live cells, live references, overflow (1 + axis of the first pass that did not fit)
-    int* snap = ctx->dscratch + 20;                                       // live cells / references behind each of the three passes
-    Int2* ip_total = reinterpret_cast<Int2*>(ctx->dscratch + 26);
-    int* tile_removed = nullptr;                                          // references that disappear, per tile of the pass
-    const int ip_capacity = int(std::min<size_t>(nr0, 0x7fffffff));       // both reference buffers hold nr0 ints
-    // Enters the mode behind a compacting iteration (cells: num_cells working records, refs: num_refs references, compact).
-    size_t ip_dstride = 0;                                                // bytes between the dirty flags of two axes (a multiple of 256: the sweeps load four flags at a time)
-    // (returns false -- and the merge goes on compacting -- when the scratch of the mode does not fit the idle cell buffer: grids of a few dozen cells)
-    auto ip_enter = [&]() -> bool {
-        const auto r256 = [](size_t n) { return (n + 255) & ~size_t(255); };
-        const size_t slots = size_t(num_cells), dstride = r256(slots);
-        const size_t off_dirty = r256(slots * 8), off_eval = off_dirty + 3 * dstride, off_removed = off_eval + r256(slots);
-        if (off_removed + r256(size_t(grid_blocks(num_cells, kIpTile)) * sizeof(int)) > nc0 * sizeof(Cell)) return false;
-        ip_slots = num_cells; ip_dstride = dstride;
-        char* scratch = static_cast<char*>(cells_other);                   // 32 bytes per cell of the un-merged grid: 12 per slot are used
-        minfo = reinterpret_cast<Int2*>(scratch);
-        dirty = reinterpret_cast<unsigned char*>(scratch + off_dirty);
-        evaluated = reinterpret_cast<unsigned char*>(scratch + off_eval);
-        tile_removed = reinterpret_cast<int*>(scratch + off_removed);
-        // dirty cells: the ones made after the last evaluation of the axis (their stamps say so) and the cells behind their lower corners
-        const unsigned char* stp = have_stamps ? stamps : nullptr;
-        ip_begin<<<grid_blocks(ip_slots, kBlock), kBlock, 0, st>>>(cells, ip_slots, list_end, dirty, stp, since[0], since[1], since[2],
-                                                                   evaluated, cell_flags /* the mode's `absorbs` tags */, books, num_refs, ip_dstride); HG_DBG(ctx);
-        if (stp) ip_mark_entry<<<grid_blocks(ip_slots, kIpTile), kBlock, 0, st>>>(k, reinterpret_cast<const Entry*>(entries), cells, ip_slots, dirty, stp, since[0], since[1], since[2], ip_dstride); HG_DBG(ctx);
-        in_place = true;
-        return true;
-    };
-    // Leaves the mode: the live cells become public 32-byte records in `cells_other` (the scratch above is dead by then), their lists go to the
-    // reference buffer that is not in use, the voxel map is rewritten once.  Afterwards the grid is in the state a compacting pass with 32-byte
-    // output leaves it in.
-    auto ip_leave = [&]() -> int {
-        const int tiles = grid_blocks(ip_slots, kMergeTile);
-        ip_live_sums<<<grid_blocks(tiles, kWaves), kBlock, 0, st>>>(cells, list_end, ip_slots, tile_sums, tiles); HG_DBG(ctx);
-        if (!ctx_scan<Int2>(ctx, SumsIn{tile_sums}, SumsOut{tile_sums}, tiles, partials, (const Int2*)nullptr, ip_total)) return HAGRID_ENOMEM;
-        ip_compact<<<tiles, kBlock, 0, st>>>(cells, list_end, refs, ip_slots, tile_sums, static_cast<Cell*>(cells_other), refs_b, nexts); HG_DBG(ctx);
-        ip_resolve_tombs<<<grid_blocks(ip_slots, kBlock), kBlock, 0, st>>>(nexts, ip_slots); HG_DBG(ctx);
-        remap_entries_kernel<<<grid_blocks((num_entries + 3) / 4, kBlock), kBlock, 0, st>>>(entries, nexts, num_entries); HG_DBG(ctx);
-        std::swap(cells, cells_other);
-        std::swap(refs, refs_b);
-        int h[2];
-        HG_TRY(read_back(ctx, ip_total, h, sizeof(h)));
-        if (h[0] != num_cells) return fail(ctx, HAGRID_EHIP, __FILE__, __LINE__, "merge_grid: the books of the in-place iterations do not add up");
-        num_refs = h[1];
-        in_place = false; in_narrow = false; ip_iters = 0;
-        have_stamps = false;                                               // (the compaction does not carry them: a later entry starts with every cell dirty)
-        return HAGRID_OK;
-    };
-    // The compacting passes of one iteration from `first_axis` on (merge_iteration<axis>, merge.cu:292-329).  They run back to back: the cell count
-    // of the second and third pass is only known to the device (the previous pass's scan total); their kernels are launched for the count the first
-    // of them starts from and read the real one.  One host round trip per iteration instead of three.
-    int last_pass_in = 0, last_pass_out = 0;
-    auto compacting_passes = [&](int first_axis, int mask) -> int {
-        for (int axis = first_axis; axis < 3; axis++) {
-            const int blocks = grid_blocks(num_cells, kBlock);
-            Int2* tot = total + axis;
-            const int* n_dev = axis > first_axis ? &total[axis - 1].a : nullptr;
-            const Entry* ent = reinterpret_cast<const Entry*>(entries);
-            if (++pass_tag == 256) { pass_tag = 1; (void)hipMemsetAsync(prevs, 0, nc0, st); }      // tags are bytes
-            if (in_narrow) merge_counts_kernel<true><<<blocks, kBlock, 0, st>>>(axis, k, ent, cells, refs, merge_counts, nexts, prevs, pass_tag, mask, num_cells, n_dev);
-            else           merge_counts_kernel<false><<<blocks, kBlock, 0, st>>>(axis, k, ent, cells, refs, merge_counts, nexts, prevs, pass_tag, mask, num_cells, n_dev);
-            HG_DBG(ctx);
-            cell_flags_kernel<<<grid_blocks((num_cells + 3) / 4, kBlock), kBlock, 0, st>>>(nexts, prevs, pass_tag, cell_flags, num_cells, n_dev); HG_DBG(ctx);
-            const int tiles = grid_blocks(num_cells, kMergeTile);
-            merge_tile_sums<<<grid_blocks(tiles, kWaves), kBlock, 0, st>>>(cell_flags, merge_counts, num_cells, n_dev, tile_sums, tiles); HG_DBG(ctx);
-            if (!ctx_scan<Int2>(ctx, SumsIn{tile_sums}, SumsOut{tile_sums}, tiles, partials, (const Int2*)nullptr, tot)) return HAGRID_ENOMEM;
-            // (new_cell_ids = nexts: dead after the flags)
-            // (stamps are bytes: a merge of more than 250 passes goes on without them -- and without the in-place mode)
-            global_pass++;
-            const bool stamping = global_pass < 250 && (have_stamps || global_pass == 1);
-            const unsigned char* st_in = stamping && have_stamps ? stamps : nullptr;
-            unsigned char* st_out = stamping ? stamps_other : nullptr;
-            if (in_narrow)   merge_kernel<true, true><<<tiles, kBlock, 0, st>>>(axis, k, ent, cells, refs, cell_flags, tile_sums, merge_counts, nexts, cells_other, refs_b, num_cells, n_dev, tot, st_in, st_out, global_pass);
-            else if (narrow) merge_kernel<false, true><<<tiles, kBlock, 0, st>>>(axis, k, ent, cells, refs, cell_flags, tile_sums, merge_counts, nexts, cells_other, refs_b, num_cells, n_dev, tot, st_in, st_out, global_pass);
-            else             merge_kernel<false, false><<<tiles, kBlock, 0, st>>>(axis, k, ent, cells, refs, cell_flags, tile_sums, merge_counts, nexts, cells_other, refs_b, num_cells, n_dev, tot, st_in, st_out, global_pass);
-            HG_DBG(ctx);
-            have_stamps = stamping; since[axis] = global_pass;
-            std::swap(stamps, stamps_other);
-            in_narrow = narrow;
-            remap_entries_kernel<<<grid_blocks((num_entries + 3) / 4, kBlock), kBlock, 0, st>>>(entries, nexts, num_entries); HG_DBG(ctx);
-            std::swap(cells, cells_other);
-            std::swap(refs, refs_b);
-        }
-        int h[6];
-        HG_TRY(read_back(ctx, total, h, sizeof(int) * 6));
-        for (int axis = first_axis; axis < 3; axis++) {
-            record(num_cells, num_refs);
-            if (axis == 2) { last_pass_in = num_cells; last_pass_out = h[4]; }
-            num_cells = h[2 * axis]; num_refs = h[2 * axis + 1];
-        }
-        return HAGRID_OK;
-    };
+    int* tile_removed = nullptr;                   // references that disappear, per tile of the pass
+    int ip_capacity;                               // both reference buffers hold nr0 ints
+    size_t ip_dstride = 0;                         // bytes between the dirty flags of two axes (a multiple of 256: the sweeps load four flags at a time)
+    // the scratch words (ctx.h: MergeScratch)
+    Int2* total;                                   // one per axis: the cells and references behind a compacting pass
+    int* books;                                    // cursor, live cells, live references, overflow (1 + axis of the first pass that did not fit)
+    int* snap;                                     // live cells / references behind each of the three passes
+    Int2* ip_total;
 
-    do {                                                                   // merge.cu:357-367
-        prev_num_cells = num_cells;
-        const int mask = iter > 3 ? 0 : (1 << (iter + 1)) - 1;
-        if (in_place && ctx->opt_merge_inplace_iters > 0 && ip_iters >= ctx->opt_merge_inplace_iters) {      // (tests: alternate the modes)
-            rc = ip_leave();
-            if (rc != HAGRID_OK) break;
+    MergeRun(hagrid_ctx* c, hagrid_grid* g) : ctx(c), grid(g), st(c->stream) {
+        k.top = ivec3(grid->dims[0], grid->dims[1], grid->dims[2]);
+        k.dims = k.top << grid->shift;
+        k.shift = grid->shift;
+        k.cell_size = (vec3(grid->bbox_max[0], grid->bbox_max[1], grid->bbox_max[2]) - vec3(grid->bbox_min[0], grid->bbox_min[1], grid->bbox_min[2])) / vec3(k.dims);
+        nc0 = size_t(grid->num_cells); nr0 = size_t(grid->num_refs);
+        entries = static_cast<uint32_t*>(grid->entries); num_entries = grid->num_entries;
+        narrow = ctx->opt_merge_narrow && std::max(k.dims.x, std::max(k.dims.y, k.dims.z)) < 65536;
+        cells = grid->cells; refs = static_cast<int*>(grid->ref_ids);
+        num_cells = grid->num_cells; num_refs = grid->num_refs;
+        ip_capacity = int(std::min<size_t>(nr0, 0x7fffffff));
+        total = reinterpret_cast<Int2*>(ctx->dscratch + kScrMergeTotals);
+        books = ctx->dscratch + kScrMergeBooks;
+        snap = ctx->dscratch + kScrMergeSnapshots;
+        ip_total = reinterpret_cast<Int2*>(ctx->dscratch + kScrMergeIpTotal);
+    }
+
+    // All nine requests are made before any is checked; false: one of them failed (the caller gives the grid up).
+    bool allocate() {
+        cells_other = pool_alloc<Cell>(ctx, nc0);
+        refs_b = pool_alloc<int>(ctx, nr0);
+        merge_counts = pool_alloc<int>(ctx, nc0 + 1);
+        nexts = pool_alloc<int>(ctx, nc0 + 1);
+        prevs = pool_alloc<unsigned char>(ctx, nc0 + 4);
+        cell_flags = pool_alloc<unsigned char>(ctx, nc0 + 4);
+        const size_t stamp_stride = (nc0 + 4 + 255) & ~size_t(255);
+        stamps = pool_alloc<unsigned char>(ctx, 2 * stamp_stride);
+        stamps_other = stamps ? stamps + stamp_stride : nullptr;
+        stamps_base = stamps;
+        const int max_tiles = grid_blocks(grid->num_cells, kMergeTile);
+        tile_sums = pool_alloc<Int2>(ctx, size_t(max_tiles) + 1);
+        partials = pool_alloc<Int2>(ctx, size_t(scan_num_tiles(max_tiles)) + 1);
+        if (!cells_other || !refs_b || !merge_counts || !nexts || !prevs || !cell_flags || !tile_sums || !partials || !stamps) return false;
+        list_end = merge_counts;
+        (void)hipMemsetAsync(prevs, 0, nc0, st);                           // tag 0 = never had a predecessor
+        return true;
+    }
+    // The temporaries and whichever buffers are not the live ones (merge.cu:375-376) go back to the pool.
+    void release() {
+        hagrid_mem_free(ctx, merge_counts); hagrid_mem_free(ctx, nexts); hagrid_mem_free(ctx, prevs); hagrid_mem_free(ctx, cell_flags);
+        hagrid_mem_free(ctx, tile_sums); hagrid_mem_free(ctx, partials); hagrid_mem_free(ctx, stamps_base);
+        hagrid_mem_free(ctx, cells_other);
+        hagrid_mem_free(ctx, refs_b);
+    }
+    // The ONE state the header promises for every failure of this pass: the grid is gone -- cells and references back in the pool and NULL, counts 0;
+    // entries stay the caller's to free.
+    int give_up(int rc) {
+        hagrid_mem_free(ctx, cells); hagrid_mem_free(ctx, refs);
+        grid->cells = nullptr; grid->ref_ids = nullptr; grid->num_cells = 0; grid->num_refs = 0;
+        return rc;
+    }
+    void record(int c, int r) {                                            // sizes that entered the passes (diagnostics)
+        hagrid_build_counts& bc = ctx->counts;
+        if (bc.merge_passes < HAGRID_MAX_MERGE_PASSES) { bc.merge_cells[bc.merge_passes] = c; bc.merge_refs[bc.merge_passes] = r; bc.merge_passes++; }
+    }
+    void swap_live() { std::swap(cells, cells_other); std::swap(refs, refs_b); }
+
+    bool enter_in_place();
+    int in_place_iteration(int mask, int prev_mask);
+    int leave_in_place();
+    int compacting_passes(int first_axis, int mask);
+    int finish(int rc);
+};
+
+// Enters the mode behind a compacting iteration (cells: num_cells working records, refs: num_refs references, compact).
+// (returns false -- and the merge goes on compacting -- when the scratch of the mode does not fit the idle cell buffer: grids of a few dozen cells)
+bool MergeRun::enter_in_place() {
+    const auto r256 = [](size_t n) { return (n + 255) & ~size_t(255); };
+    const size_t slots = size_t(num_cells), dstride = r256(slots);
+    const size_t off_dirty = r256(slots * 8), off_eval = off_dirty + 3 * dstride, off_removed = off_eval + r256(slots);
+    if (off_removed + r256(size_t(grid_blocks(num_cells, kIpTile)) * sizeof(int)) > nc0 * sizeof(Cell)) return false;
+    ip_slots = num_cells; ip_dstride = dstride;
+    char* scratch = static_cast<char*>(cells_other);                   // 32 bytes per cell of the un-merged grid: 12 per slot are used
+    minfo = reinterpret_cast<Int2*>(scratch);
+    dirty = reinterpret_cast<unsigned char*>(scratch + off_dirty);
+    evaluated = reinterpret_cast<unsigned char*>(scratch + off_eval);
+    tile_removed = reinterpret_cast<int*>(scratch + off_removed);
+    // dirty cells: the ones made after the last evaluation of the axis (their stamps say so) and the cells behind their lower corners
+    const unsigned char* stp = have_stamps ? stamps : nullptr;
+    ip_begin<<<grid_blocks(ip_slots, kBlock), kBlock, 0, st>>>(cells, ip_slots, list_end, dirty, stp, since[0], since[1], since[2],
+                                                               evaluated, cell_flags /* the mode's `absorbs` tags */, books, num_refs, ip_dstride); HG_DBG(ctx);
+    if (stp) ip_mark_entry<<<grid_blocks(ip_slots, kIpTile), kBlock, 0, st>>>(k, reinterpret_cast<const Entry*>(entries), cells, ip_slots, dirty, stp, since[0], since[1], since[2], ip_dstride); HG_DBG(ctx);
+    in_place = true;
+    return true;
+}
+
+// One iteration in place: the three axis passes over the dirty cells, then the books.  Returns the passes that were applied -- the ones before the first whose
+// lists did not fit; fewer than three: no room, the caller leaves the mode and the rest of the iteration compacts -- or an error code (negative).
+int MergeRun::in_place_iteration(int mask, int prev_mask) {
+    // every cell looks again when the mask lets merges through that it held back before (merge.cu:361: from the fifth iteration on)
+    if (prev_mask & ~mask) (void)hipMemsetAsync(dirty, 1, 3 * ip_dstride, st);
+    const int blocks = grid_blocks(ip_slots, kIpTile), tiles = blocks;
+    const Entry* ent = reinterpret_cast<const Entry*>(entries);
+    for (int axis = 0; axis < 3; axis++) {
+        global_pass++;
+        if (++pass_tag == 256) {                                   // tags are bytes
+            pass_tag = 1;
+            (void)hipMemsetAsync(prevs, 0, nc0, st); (void)hipMemsetAsync(evaluated, 0, size_t(ip_slots), st); (void)hipMemsetAsync(cell_flags, 0, size_t(ip_slots), st);
         }
-        int first_compacting_axis = 0;
-        if (in_place) {
-            // every cell looks again when the mask lets merges through that it held back before (merge.cu:361: from the fifth iteration on)
-            if (prev_mask & ~mask) (void)hipMemsetAsync(dirty, 1, 3 * ip_dstride, st);
-            const int blocks = grid_blocks(ip_slots, kIpTile), tiles = blocks;
-            const Entry* ent = reinterpret_cast<const Entry*>(entries);
-            for (int axis = 0; axis < 3 && rc == HAGRID_OK; axis++) {
-                global_pass++;
-                if (++pass_tag == 256) {                                   // tags are bytes
-                    pass_tag = 1;
-                    (void)hipMemsetAsync(prevs, 0, nc0, st); (void)hipMemsetAsync(evaluated, 0, size_t(ip_slots), st); (void)hipMemsetAsync(cell_flags, 0, size_t(ip_slots), st);
-                }
-                ip_counts<<<blocks, kBlock, 0, st>>>(axis, k, ent, cells, list_end, refs, ip_slots, dirty + size_t(axis) * ip_dstride, minfo, nexts, evaluated, prevs, pass_tag, mask); HG_DBG(ctx);
-                ip_chains<<<blocks, kBlock, 0, st>>>(ip_slots, nexts, evaluated, prevs, cell_flags, pass_tag); HG_DBG(ctx);
-                ip_tile_sums<<<tiles, kBlock, 0, st>>>(cell_flags, pass_tag, minfo, ip_slots, tile_sums, tile_removed); HG_DBG(ctx);
-                if (!ctx_scan<Int2>(ctx, SumsIn{tile_sums}, SumsOut{tile_sums}, tiles, partials, (const Int2*)nullptr, ip_total)) { rc = HAGRID_ENOMEM; break; }
-                ip_apply<<<tiles, kBlock, 0, st>>>(cells, list_end, refs, cell_flags, pass_tag, minfo, nexts, tile_sums, ip_slots, books, ip_total,
-                                                    ctx->opt_merge_inplace_room > 0 ? std::min(ip_capacity, ctx->opt_merge_inplace_room) : ip_capacity, axis); HG_DBG(ctx);
-                ip_mark<<<blocks, kBlock, 0, st>>>(k, ent, cells, cell_flags, pass_tag, ip_slots, dirty, ip_total, tile_removed, tiles, books, snap + 2 * axis, ip_dstride); HG_DBG(ctx);
-            }
-            if (rc != HAGRID_OK) break;
-            int h[10];                                                     // books (4), the three snapshots
-            rc = read_back(ctx, books, h, sizeof(h));
-            if (rc != HAGRID_OK) break;
-            const int applied = h[3] > 0 ? h[3] - 1 : 3;                   // the passes before the first one whose lists did not fit
-            for (int axis = 0; axis < applied; axis++) { record(num_cells, num_refs); num_cells = h[4 + 2 * axis]; num_refs = h[5 + 2 * axis]; }
-            ip_iters++;
-            if (applied < 3) {                                             // no room: back to the public arrays; the rest of the iteration compacts
-                rc = ip_leave();
-                if (rc != HAGRID_OK) break;
-                first_compacting_axis = applied;
-            }
-        }
-        if (!in_place) {
-            if (first_compacting_axis < 3) rc = compacting_passes(first_compacting_axis, mask);
-            if (rc != HAGRID_OK) break;
-            // The next iterations in place: once an iteration merges less than half of its cells (working records only: below 65536 per axis).  The
-            // first in-place iteration looks at the cells the last compacting one made and at the cells behind them (stamps): about two cells per merge
-            // and axis.  1M-triangle soup: the first iteration merges 39 % of the cells, the second 5.7 %, the third 0.4 %; a compacting pass costs ~160 us
-            // whatever it merges, a pass in place 75 - 130 us in the second iteration and ~45 us in the third (profiles/NOTES.md "Round 4").
-            const int div = ctx->opt_merge_inplace_div > 0 ? ctx->opt_merge_inplace_div : 2;
-            if (in_narrow && ctx->opt_merge_inplace && (long long)div * (prev_num_cells - num_cells) < prev_num_cells && num_cells < alpha * prev_num_cells) (void)ip_enter();
-        }
-        prev_mask = mask;
-        iter++;
-    } while (rc == HAGRID_OK && num_cells < alpha * prev_num_cells);
-    if (rc == HAGRID_OK && in_place) rc = ip_leave();
+        ip_counts<<<blocks, kBlock, 0, st>>>(axis, k, ent, cells, list_end, refs, ip_slots, dirty + size_t(axis) * ip_dstride, minfo, nexts, evaluated, prevs, pass_tag, mask); HG_DBG(ctx);
+        ip_chains<<<blocks, kBlock, 0, st>>>(ip_slots, nexts, evaluated, prevs, cell_flags, pass_tag); HG_DBG(ctx);
+        ip_tile_sums<<<tiles, kBlock, 0, st>>>(cell_flags, pass_tag, minfo, ip_slots, tile_sums, tile_removed); HG_DBG(ctx);
+        if (!ctx_scan<Int2>(ctx, SumsIn{tile_sums}, SumsOut{tile_sums}, tiles, partials, (const Int2*)nullptr, ip_total)) return HAGRID_ENOMEM;
+        ip_apply<<<tiles, kBlock, 0, st>>>(cells, list_end, refs, cell_flags, pass_tag, minfo, nexts, tile_sums, ip_slots, books, ip_total,
+                                            ctx->opt_merge_inplace_room > 0 ? std::min(ip_capacity, ctx->opt_merge_inplace_room) : ip_capacity, axis); HG_DBG(ctx);
+        ip_mark<<<blocks, kBlock, 0, st>>>(k, ent, cells, cell_flags, pass_tag, ip_slots, dirty, ip_total, tile_removed, tiles, books, snap + 2 * axis, ip_dstride); HG_DBG(ctx);
+    }
+    int h[10];                                                     // books (4), the three snapshots
+    HG_TRY(read_back(ctx, books, h, sizeof(h)));
+    const int applied = h[3] > 0 ? h[3] - 1 : 3;                   // the passes before the first one whose lists did not fit
+    for (int axis = 0; axis < applied; axis++) { record(num_cells, num_refs); num_cells = h[4 + 2 * axis]; num_refs = h[5 + 2 * axis]; }
+    ip_iters++;
+    return applied;
+}
+
+// Leaves the mode: the live cells become public 32-byte records in `cells_other` (the scratch above is dead by then), their lists go to the
+// reference buffer that is not in use, the voxel map is rewritten once.  Afterwards the grid is in the state a compacting pass with 32-byte
+// output leaves it in.
+int MergeRun::leave_in_place() {
+    const int tiles = grid_blocks(ip_slots, kMergeTile);
+    ip_live_sums<<<grid_blocks(tiles, kWaves), kBlock, 0, st>>>(cells, list_end, ip_slots, tile_sums, tiles); HG_DBG(ctx);
+    if (!ctx_scan<Int2>(ctx, SumsIn{tile_sums}, SumsOut{tile_sums}, tiles, partials, (const Int2*)nullptr, ip_total)) return HAGRID_ENOMEM;
+    ip_compact<<<tiles, kBlock, 0, st>>>(cells, list_end, refs, ip_slots, tile_sums, static_cast<Cell*>(cells_other), refs_b, nexts); HG_DBG(ctx);
+    ip_resolve_tombs<<<grid_blocks(ip_slots, kBlock), kBlock, 0, st>>>(nexts, ip_slots); HG_DBG(ctx);
+    remap_entries_kernel<<<grid_blocks((num_entries + 3) / 4, kBlock), kBlock, 0, st>>>(entries, nexts, num_entries); HG_DBG(ctx);
+    swap_live();
+    int h[2];
+    HG_TRY(read_back(ctx, ip_total, h, sizeof(h)));
+    if (h[0] != num_cells) return fail(ctx, HAGRID_EHIP, __FILE__, __LINE__, "merge_grid: the books of the in-place iterations do not add up");
+    num_refs = h[1];
+    in_place = false; in_narrow = false; ip_iters = 0;
+    have_stamps = false;                                               // (the compaction does not carry them: a later entry starts with every cell dirty)
+    return HAGRID_OK;
+}
+
+// The compacting passes of one iteration from `first_axis` on (merge_iteration<axis>, merge.cu:292-329).  They run back to back: the cell count
+// of the second and third pass is only known to the device (the previous pass's scan total); their kernels are launched for the count the first
+// of them starts from and read the real one.  One host round trip per iteration instead of three.
+int MergeRun::compacting_passes(int first_axis, int mask) {
+    for (int axis = first_axis; axis < 3; axis++) {
+        const int blocks = grid_blocks(num_cells, kBlock);
+        Int2* tot = total + axis;
+        const int* n_dev = axis > first_axis ? &total[axis - 1].a : nullptr;
+        const Entry* ent = reinterpret_cast<const Entry*>(entries);
+        if (++pass_tag == 256) { pass_tag = 1; (void)hipMemsetAsync(prevs, 0, nc0, st); }      // tags are bytes
+        if (in_narrow) merge_counts_kernel<true><<<blocks, kBlock, 0, st>>>(axis, k, ent, cells, refs, merge_counts, nexts, prevs, pass_tag, mask, num_cells, n_dev);
+        else           merge_counts_kernel<false><<<blocks, kBlock, 0, st>>>(axis, k, ent, cells, refs, merge_counts, nexts, prevs, pass_tag, mask, num_cells, n_dev);
+        HG_DBG(ctx);
+        cell_flags_kernel<<<grid_blocks((num_cells + 3) / 4, kBlock), kBlock, 0, st>>>(nexts, prevs, pass_tag, cell_flags, num_cells, n_dev); HG_DBG(ctx);
+        const int tiles = grid_blocks(num_cells, kMergeTile);
+        merge_tile_sums<<<grid_blocks(tiles, kWaves), kBlock, 0, st>>>(cell_flags, merge_counts, num_cells, n_dev, tile_sums, tiles); HG_DBG(ctx);
+        if (!ctx_scan<Int2>(ctx, SumsIn{tile_sums}, SumsOut{tile_sums}, tiles, partials, (const Int2*)nullptr, tot)) return HAGRID_ENOMEM;
+        // (new_cell_ids = nexts: dead after the flags)
+        // (stamps are bytes: a merge of more than 250 passes goes on without them -- and without the in-place mode)
+        global_pass++;
+        const bool stamping = global_pass < 250 && (have_stamps || global_pass == 1);
+        const unsigned char* st_in = stamping && have_stamps ? stamps : nullptr;
+        unsigned char* st_out = stamping ? stamps_other : nullptr;
+        if (in_narrow)   merge_kernel<true, true><<<tiles, kBlock, 0, st>>>(axis, k, ent, cells, refs, cell_flags, tile_sums, merge_counts, nexts, cells_other, refs_b, num_cells, n_dev, tot, st_in, st_out, global_pass);
+        else if (narrow) merge_kernel<false, true><<<tiles, kBlock, 0, st>>>(axis, k, ent, cells, refs, cell_flags, tile_sums, merge_counts, nexts, cells_other, refs_b, num_cells, n_dev, tot, st_in, st_out, global_pass);
+        else             merge_kernel<false, false><<<tiles, kBlock, 0, st>>>(axis, k, ent, cells, refs, cell_flags, tile_sums, merge_counts, nexts, cells_other, refs_b, num_cells, n_dev, tot, st_in, st_out, global_pass);
+        HG_DBG(ctx);
+        have_stamps = stamping; since[axis] = global_pass;
+        std::swap(stamps, stamps_other);
+        in_narrow = narrow;
+        remap_entries_kernel<<<grid_blocks((num_entries + 3) / 4, kBlock), kBlock, 0, st>>>(entries, nexts, num_entries); HG_DBG(ctx);
+        swap_live();
+    }
+    int h[6];
+    HG_TRY(read_back(ctx, total, h, sizeof(int) * 6));
+    for (int axis = first_axis; axis < 3; axis++) {
+        record(num_cells, num_refs);
+        num_cells = h[2 * axis]; num_refs = h[2 * axis + 1];
+    }
+    return HAGRID_OK;
+}
+
+// The end of every run that got its buffers: the live cells become public records, the temporaries go back, the grid takes the live arrays -- or is given up.
+int MergeRun::finish(int rc) {
+    if (rc == HAGRID_OK && in_place) rc = leave_in_place();
     else if (rc == HAGRID_OK && in_narrow) {                               // back to the public record
         widen_cells_kernel<<<grid_blocks(num_cells, kBlock), kBlock, 0, st>>>(cells, static_cast<Cell*>(cells_other), total + 2); HG_DBG(ctx);
         std::swap(cells, cells_other);
@@ -863,19 +861,65 @@ extern "C" int hagrid_merge_grid(hagrid_ctx* ctx, hagrid_grid* grid, float alpha
         if (e != hipSuccess) rc = fail(ctx, HAGRID_EHIP, __FILE__, __LINE__, hipGetErrorString(e));
     }
     release();
-    hagrid_mem_free(ctx, cells_other);   // whichever buffers are not the live ones (merge.cu:375-376)
-    hagrid_mem_free(ctx, refs_b);
     if (rc != HAGRID_OK) {
         // A pass failed half way: the voxel map may already point at the new cell numbers and the cells may be 16-byte working
-        // records.  Nothing of that is a grid (the reference aborts here, common.h:103-108): cells and references go back to the
-        // pool and the descriptor says so; entries stay the caller's to free.
+        // records.  Nothing of that is a grid (the reference aborts here, common.h:103-108).
         (void)hipStreamSynchronize(st);
-        hagrid_mem_free(ctx, cells); hagrid_mem_free(ctx, refs);
-        grid->cells = nullptr; grid->ref_ids = nullptr; grid->num_cells = 0; grid->num_refs = 0;
-        return rc;
+        return give_up(rc);
     }
     grid->cells = cells; grid->ref_ids = refs;
     grid->num_cells = num_cells; grid->num_refs = num_refs;
     ctx->counts.merged_cells = num_cells; ctx->counts.merged_refs = num_refs;
     return rc;
 }
+
+} // namespace
+
+extern "C" int hagrid_merge_grid(hagrid_ctx* ctx, hagrid_grid* grid, float alpha) {
+    if (!ctx || !grid) return HAGRID_EINVAL;
+    if (!grid->cells || !grid->entries || !grid->ref_ids) HG_FAIL(ctx, HAGRID_EINVAL, "merge_grid: incomplete (or compressed) grid");
+    trav_image_drop(ctx);            // the traversal image of this context describes a grid that is about to change
+    ctx->counts.merge_passes = 0;
+    ctx->counts.merged_cells = grid->num_cells; ctx->counts.merged_refs = grid->num_refs;
+    if (!(alpha > 0)) return HAGRID_OK;
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+
+    MergeRun m(ctx, grid);
+    // (nothing is queued yet, but the promise of the header is ONE state for every failure of this pass: the grid is gone)
+    if (!m.allocate()) { m.release(); return m.give_up(HAGRID_ENOMEM); }
+
+    int rc = HAGRID_OK;
+    int prev_num_cells = 0, iter = 0, prev_mask = 0;
+    do {                                                                   // merge.cu:357-367
+        prev_num_cells = m.num_cells;
+        const int mask = iter > 3 ? 0 : (1 << (iter + 1)) - 1;
+        if (m.in_place && ctx->opt_merge_inplace_iters > 0 && m.ip_iters >= ctx->opt_merge_inplace_iters) {      // (tests: alternate the modes)
+            rc = m.leave_in_place();
+            if (rc != HAGRID_OK) break;
+        }
+        int first_compacting_axis = 0;
+        if (m.in_place) {
+            const int applied = m.in_place_iteration(mask, prev_mask);
+            if (applied < 0) { rc = applied; break; }
+            if (applied < 3) {                                             // no room: back to the public arrays; the rest of the iteration compacts
+                rc = m.leave_in_place();
+                if (rc != HAGRID_OK) break;
+                first_compacting_axis = applied;
+            }
+        }
+        if (!m.in_place) {
+            if (first_compacting_axis < 3) rc = m.compacting_passes(first_compacting_axis, mask);
+            if (rc != HAGRID_OK) break;
+            // The next iterations in place: once an iteration merges less than half of its cells (working records only: below 65536 per axis).  The
+            // first in-place iteration looks at the cells the last compacting one made and at the cells behind them (stamps): about two cells per merge
+            // and axis.  1M-triangle soup: the first iteration merges 39 % of the cells, the second 5.7 %, the third 0.4 %; a compacting pass costs ~160 us
+            // whatever it merges, a pass in place 75 - 130 us in the second iteration and ~45 us in the third (profiles/NOTES.md "Round 4").
+            const int div = ctx->opt_merge_inplace_div > 0 ? ctx->opt_merge_inplace_div : 2;
+            if (m.in_narrow && ctx->opt_merge_inplace && (long long)div * (prev_num_cells - m.num_cells) < prev_num_cells && m.num_cells < alpha * prev_num_cells) (void)m.enter_in_place();
+        }
+        prev_mask = mask;
+        iter++;
+    } while (rc == HAGRID_OK && m.num_cells < alpha * prev_num_cells);
+    return m.finish(rc);
+}
+

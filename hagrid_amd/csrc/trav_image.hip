@@ -262,18 +262,18 @@ int build_general(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img) {
     int* claim = pool_alloc<int>(ctx, size_t(num_cells));
     auto release = [&]() { hagrid_mem_free(ctx, items[0]); hagrid_mem_free(ctx, items[1]); hagrid_mem_free(ctx, claim); };
     if (!recs || !items[0] || !items[1] || !claim) { release(); hagrid_mem_free(ctx, recs); return HAGRID_ENOMEM; }
-    int* status = ctx->dscratch + 160;           // [0] does not fit | [1] lists with an id beyond the field | [2] wide records
-    int* counts = ctx->dscratch + 164;           // inner entries listed per level
+    int* status = ctx->dscratch + kScrImgStatus;           // [0] does not fit | [1] lists with an id beyond the field | [2] wide records
+    int* counts = ctx->dscratch + kScrImgLevelCounts;           // inner entries listed per level
     int rc = 1;
     for (int idb : {20, 26}) {
         if (idb == 20 && ctx->opt_image_slim == 2) continue;           // "traverse.image_slim" = 2: the 26-bit form whatever the ids (tests)
-        (void)hipMemsetAsync(status, 0, 24 * sizeof(int), st);
+        (void)hipMemsetAsync(status, 0, kScrImgClearedWords * sizeof(int), st);
         (void)hipMemsetAsync(claim, 0xFF, size_t(num_cells) * sizeof(int), st);
         image_general_top<<<grid_blocks(k.num_top, kBlock), kBlock, 0, st>>>(k, idb, recs, items[0], counts, claim, status);
         HG_DBG(ctx);
         int level = 0, n = 0;
         rc = read_back(ctx, counts, &n, sizeof(int));
-        while (rc == HAGRID_OK && n > 0 && level < 16) {
+        while (rc == HAGRID_OK && n > 0 && level < kImageMaxLevels) {
             GenItem* in = items[level & 1]; GenItem* out = items[(level + 1) & 1];
             image_general_level<<<grid_blocks(n, kWaves), kBlock, 0, st>>>(k, idb, recs, in, counts + level, out, counts + level + 1, claim, status);
             HG_DBG(ctx);
@@ -391,7 +391,7 @@ int build_slim(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img, uint2* table
     long long records = (long long)k.num_top << (3 * D);
     if (!uniform) {              // (the caller scanned the block sizes into `offsets`; the total stands in its scratch word)
         int h = 0;
-        const int rc = read_back(ctx, ctx->dscratch + 224, &h, sizeof(h));
+        const int rc = read_back(ctx, ctx->dscratch + kScrImgTableTotal, &h, sizeof(h));
         if (rc != HAGRID_OK) return rc;
         records = h;
     }
@@ -401,7 +401,7 @@ int build_slim(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img, uint2* table
     if (!recs) return HAGRID_ENOMEM;
     int* claim = uniform ? nullptr : pool_alloc<int>(ctx, size_t(k.num_cells));       // table layout: the wide record of every cell that needs one
     if (!uniform && !claim) { hagrid_mem_free(ctx, recs); return HAGRID_ENOMEM; }
-    int* status = ctx->dscratch + 228;
+    int* status = ctx->dscratch + kScrImgSlimStatus;
     int result = 1;
     for (int idb : {20, 26}) {
         if (idb == 20 && ctx->opt_image_slim == 2) continue;           // "traverse.image_slim" = 2: the 26-bit form whatever the ids (tests)
@@ -446,7 +446,7 @@ int build_blocks(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img) {
     auto release = [&]() { hagrid_mem_free(ctx, metas); hagrid_mem_free(ctx, offs); hagrid_mem_free(ctx, partials); };
     if (!metas || !offs || !partials || !table) { release(); hagrid_mem_free(ctx, table); return HAGRID_ENOMEM; }
     image_depths<<<k.num_top, 64, 0, ctx->stream>>>(k, D, metas); HG_DBG(ctx);
-    int* total = ctx->dscratch + 224;
+    int* total = ctx->dscratch + kScrImgTableTotal;
     if (!ctx_scan<int>(ctx, SlimSizeIn{metas}, SlimSizeOut{offs}, k.num_top, partials, (const int*)nullptr, total)) { release(); hagrid_mem_free(ctx, table); return HAGRID_ENOMEM; }
     int table_records = 0;
     int rc = read_back(ctx, total, &table_records, sizeof(int));

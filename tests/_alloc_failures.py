@@ -28,12 +28,12 @@ SITE_NAMES = ("pool_alloc<", "pool_try_alloc<", ".get<", "hagrid_mem_alloc(", "l
 SITES = {
     "assemble.hip": ({"hagrid_mem_alloc(": 1}, ("scene_create",)),
     "blob.hip": ({".get<": 2, "hagrid_mem_alloc(": 3}, ("grid_pack", "grid_save", "grid_load")),          # (.get<, one hagrid_mem_alloc: hagrid_grid_broadcast, needs RCCL ranks)
-    "build.hip": ({"pool_alloc<": 3, "pool_try_alloc<": 1, ".get<": 25, "ctx_scan<": 6, "scan_plain(": 1}, ("build_grid",)),
+    "build.hip": ({"pool_alloc<": 3, "pool_try_alloc<": 1, ".get<": 18, "ctx_scan<": 6, "scan_plain(": 1}, ("build_grid",)),
     "compress.hip": ({"pool_alloc<": 2, "hagrid_mem_alloc(": 1}, ("compress_grid",)),
     "ctx.hip": ({"pool_alloc<": 3, "hagrid_mem_alloc(": 1, "lookback_state(": 1, "device_request(": 2}, ()),
     "distance.hip": ({".get<": 1, "scan_plain(": 1}, ("distance_lattice",)),
     "expand.hip": ({"pool_alloc<": 2, "pool_try_alloc<": 2}, ("expand_grid",)),
-    "flatten.hip": ({"pool_alloc<": 5, "ctx_scan<": 1}, ("flatten_grid",)),
+    "flatten.hip": ({"pool_alloc<": 1, ".get<": 4, "ctx_scan<": 1}, ("flatten_grid",)),
     "merge.hip": ({"pool_alloc<": 9, "ctx_scan<": 3}, ("merge_grid",)),
     # (.get< and ctx_scan<: the binning buffers and their scan, both modes; device_request(: bin_diff -- automatic binning --, row_scores -- automatic binning and
     # the row detection, from 2^18 rays on --, lpt_buf -- un-binned launches that know their rows)

@@ -98,6 +98,7 @@ def test_merge_iterations_in_place_and_compacting_agree_with_the_oracle(mem, n, 
     tris = scene.make_soup(n, seed=seed)
     d_tris = mem.upload(tris)
     G = O.Grid.build(tris, td, sd).merge(alpha)
+    passes = {}
     try:
         # room: the in-place mode appends its merged lists behind the live references of the same buffer; a pass whose lists do not fit is not
         # applied and the rest of its iteration compacts -- forced here by capping the buffer (1: the very first pass; final size + a little: a later one)
@@ -113,7 +114,11 @@ def test_merge_iterations_in_place_and_compacting_agree_with_the_oracle(mem, n, 
             assert_same_grid(grid.download(), G, ("merge", inplace, iters, room, div))
             bc = mem.build_counts()
             assert bc["merged_cells"] == G.num_cells and bc["merged_refs"] == G.num_refs
+            # the settings differ in mechanism only: the sizes that entered every axis pass are those of the all-compacting run
+            passes[(inplace, iters, room, div)] = (bc["merge_passes"], list(bc["merge_cells"]), list(bc["merge_refs"]))
             grid.free()
+        for setting, p in passes.items():
+            assert p == passes[(0, 0, 0, 0)], ("merge passes", setting, p, passes[(0, 0, 0, 0)])
     finally:
         mem.set_option("merge.inplace", 1); mem.set_option("merge.inplace_iters", 0); mem.set_option("merge.inplace_room", 0); mem.set_option("merge.inplace_div", 0)
     mem.free(d_tris)
