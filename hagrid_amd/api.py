@@ -28,7 +28,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import Camera, GridPOD, HagridError, TraversalStats
-from .scene import BOX_QUERY_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, NEAREST_ENTRY_DTYPE, POINT_QUERY_DTYPE, SEGMENT_DTYPE, SEGMENT_RECORD_DTYPE, SMALL_CELL_DTYPE
+from .scene import BOX_QUERY_DTYPE, OBB_DTYPE, CELL_DTYPE, CLOSEST_DTYPE, HIT_DTYPE, NEAREST_ENTRY_DTYPE, POINT_QUERY_DTYPE, SEGMENT_DTYPE, SEGMENT_RECORD_DTYPE, SMALL_CELL_DTYPE
 
 _current = None  # the most recently created MemManager (profile / setup_traversal take no manager)
 
@@ -587,6 +587,87 @@ def self_intersections(grid: Grid, tris, labels, k: int = MAX_OVERLAP_IDS):
     return ids, counts
 
 
+def overlap_obbs(grid: Grid, tris: int, obbs: int, n: int, k: int, ids: int, counts: int = 0, counters: int = 0, flags: int = 0, query_labels: int = 0,
+                 tri_labels: int = 0):
+    """Extension (hagrid_overlap_obbs): ORIENTED-BOX queries -- for each of n boxes (64 bytes: OBB_DTYPE -- c, first, u, 0, v, 0, w, 0; the box is
+    c + a u + b v + g w with |a|, |b|, |g| <= 1, the axes neither normalised nor orthogonal) the k smallest ids >= first of the scene triangles that meet it,
+    into ids and counts exactly as overlap_boxes writes them (ANY likewise).  A triangle meets the box when no axis of the separating-axis test separates
+    them (include/hagrid/obb.h; scene.obb_pairs) and it meets the box's bounding box grown by the grid's margin.  query_labels (int32[n], one per box) and
+    tri_labels (int32[3 per scene triangle]): both or neither; a pair is left out when the box's label is >= 0 and one of the triangle's three -- with
+    body ids a body's box does not see the body's own triangles.  A record with a component that is not finite gets count 0.  counters: as for
+    overlap_boxes; the third total counts the pairs offered to the box / triangle test.  All arguments are device addresses; asynchronous on the manager's
+    stream.  scene.overlap_obbs states the results in numpy.  Walks the construction format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_overlap_obbs(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(obbs or 0), int(n), C.c_void_p(query_labels or 0),
+                                           C.c_void_p(tri_labels or 0), int(k), C.c_void_p(ids or 0), C.c_void_p(counts or 0), C.c_void_p(counters or 0), int(flags)),
+           "overlap_obbs")
+
+
+def obb_records(centres, rotations_or_axes, half_extents=None, first=None):
+    """OBB records for overlap_obbs from torch tensors on the device: a float32 tensor (n, 16).  centres (n, 3); rotations_or_axes (n, 3, 3) whose COLUMNS
+    are the directions of the box's three axes (a rotation matrix, or any frame -- a sheared one is legal); half_extents (n, 3) scales the columns, None
+    takes them as they are (u, v, w themselves).  first: None (0) or an int32 tensor (n,).  Runs on torch's current stream."""
+    import torch
+    c = centres.to(torch.float32).reshape(-1, 3)
+    A = rotations_or_axes.to(torch.float32).reshape(-1, 3, 3)
+    if half_extents is not None:
+        A = A * half_extents.to(torch.float32).reshape(-1, 1, 3)
+    rec = torch.zeros((c.shape[0], 4, 4), dtype=torch.float32, device=c.device)
+    rec[:, 0, :3] = c
+    rec[:, 1:, :3] = A.transpose(1, 2)
+    if first is not None:
+        rec[:, 0, 3] = first.to(torch.int32).reshape(-1).view(torch.float32)
+    return rec.reshape(-1, 16)
+
+
+def tris_in_obbs(grid: Grid, tris, obbs, k: int = MAX_OVERLAP_IDS, query_labels=None, tri_labels=None, max_pages=None) -> dict:
+    """ALL the triangles that meet every oriented box, ascending by id, in CSR form: overlap_obbs paged on torch tensors.  Page by page the boxes whose
+    count came back k + 1 are asked again with first = last id + 1; ONE scalar per page goes to the host (how many lists go on).  obbs: a float32 tensor
+    (n, 16) on the device (obb_records; its `first` words are respected and left unchanged), query_labels ((n,) int32) and tri_labels ((N, 3) int32): torch
+    tensors on the device (tris and tri_labels may be device addresses).  The manager must run on torch's current stream.  Returns "offsets" int64
+    (n + 1,), "ids" int32 (total,), "pages" and "complete" (False only when max_pages ended the paging early; the lists are then prefixes).  _paged_csr
+    serves the cursor-paged distance lists and does not fit: here a page is continued by `first` inside the record, and the entries carry no distance."""
+    import torch
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    k = int(k)
+    rec = obbs.reshape(-1, 16).clone()
+    n = int(rec.shape[0])
+    dev = rec.device
+    active = torch.arange(n, dtype=torch.int64, device=dev)
+    lab = query_labels
+    page_q, page_ids = [], []
+    pages, complete = 0, True
+    while active.numel():
+        if max_pages is not None and pages >= int(max_pages):
+            complete = False
+            break
+        pages += 1
+        m = int(active.numel())
+        ids = torch.empty((m, k), dtype=torch.int32, device=dev)
+        counts = torch.empty((m,), dtype=torch.int32, device=dev)
+        overlap_obbs(grid, ptr(tris), rec.data_ptr(), m, k, ids.data_ptr(), counts.data_ptr(), query_labels=ptr(lab) if query_labels is not None else 0,
+                     tri_labels=ptr(tri_labels) if query_labels is not None else 0)
+        page_q.append(active); page_ids.append(ids)
+        more = counts > k
+        if int(more.sum().item()) == 0:
+            break
+        active = active[more]
+        rec = rec[more].contiguous()
+        rec[:, 3] = (ids[more][:, k - 1] + 1).view(torch.float32)
+        if query_labels is not None:
+            lab = lab[more].contiguous()
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if not page_q:
+        return {"offsets": offsets, "ids": torch.zeros(0, dtype=torch.int32, device=dev), "pages": 0, "complete": complete}
+    q = torch.cat([a[:, None].expand(-1, k).reshape(-1) for a in page_q])
+    e = torch.cat([x.reshape(-1) for x in page_ids])
+    used = e >= 0
+    q, e = q[used], e[used]
+    e = e[torch.sort(q, stable=True)[1]]
+    torch.cumsum(torch.bincount(q, minlength=n), 0, out=offsets[1:])
+    return {"offsets": offsets, "ids": e.contiguous(), "pages": pages, "complete": complete}
+
+
 INSIDE_WINDING = 1       # HAGRID_INSIDE_WINDING
 
 
@@ -981,5 +1062,5 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "traverse_grid_filtered", "skip_filters", "RAY_MASK_ALL",
            "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "segment_tris", "tris_near_segments", "SEGMENT_DTYPE", "SEGMENT_RECORD_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
-           "overlap_tris", "self_intersections",
+           "overlap_tris", "self_intersections", "overlap_obbs", "obb_records", "tris_in_obbs", "OBB_DTYPE",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

@@ -9,6 +9,7 @@
 //   bcast   header first (256 bytes, the receivers size their buffer), then the payload, straight from / into pool memory.
 //           RCCL is bound at run time (dlopen), so the library itself carries no dependency on it.
 #include "ctx.h"
+#include "wave_prims.h"
 
 #include <dlfcn.h>
 
@@ -74,9 +75,18 @@ int check_header(hagrid_ctx* ctx, const hagrid_blob_header& h, size_t bytes) {
 
 // One pass over the arrays of an unpacked blob: every index a traversal will follow stays inside its array.  A file is foreign
 // data; the walk itself checks nothing.  flag bits: 1 entry, 2 cell, 4 reference.
-__global__ void validate_arrays(const uint32_t* entries, int num_entries, const int4* cells, const uint4* small_cells, int num_cells,
-                                const int* refs, int num_refs, int num_tris, int* flag) {
+// The same scan answers grid_max_ref below (max_out not null: no entries, no cells, and nothing is checked): the largest id among the references -- two
+// one-shot scans over grid arrays, one kernel of the library's budget.
+__global__ void __launch_bounds__(kBlock) validate_arrays(const uint32_t* entries, int num_entries, const int4* cells, const uint4* small_cells, int num_cells,
+                                                          const int* refs, int num_refs, int num_tris, int* flag, int* max_out) {
     const int stride = gridDim.x * blockDim.x;
+    if (max_out) {                                  // sentinels of a compressed grid are negative
+        int m = -1;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < num_refs; i += stride) m = max(m, refs[i]);
+        m = wave_max(m);
+        if (lane_id() == 0 && m >= 0) atomicMax(max_out, m);
+        return;
+    }
     int bad = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < num_entries; i += stride) {
         const uint32_t e = entries[i], log_dim = e & 3u, begin = e >> 2;
@@ -105,8 +115,9 @@ int validate_unpacked(hagrid_ctx* ctx, const hagrid_grid& g, int num_tris) {
     HG_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
     const long long most = std::max<long long>(std::max(g.num_entries, g.num_cells), g.num_refs);
     const int blocks = int(std::min<long long>((most + 255) / 256, 4096));
-    validate_arrays<<<std::max(blocks, 1), 256, 0, ctx->stream>>>(static_cast<const uint32_t*>(g.entries), g.num_entries, static_cast<const int4*>(g.cells),
-                                                                  static_cast<const uint4*>(g.small_cells), g.num_cells, static_cast<const int*>(g.ref_ids), g.num_refs, num_tris, flag);
+    validate_arrays<<<std::max(blocks, 1), kBlock, 0, ctx->stream>>>(static_cast<const uint32_t*>(g.entries), g.num_entries, static_cast<const int4*>(g.cells),
+                                                                     static_cast<const uint4*>(g.small_cells), g.num_cells, static_cast<const int*>(g.ref_ids), g.num_refs, num_tris, flag,
+                                                                     nullptr);
     HG_HIP(ctx, hipGetLastError());
     int bad = 0;
     HG_TRY(read_back(ctx, flag, &bad, sizeof(int)));
@@ -165,6 +176,12 @@ constexpr int kNcclUint8 = 1;      // ncclUint8 (rccl.h: ncclInt8 = 0, ncclUint8
 constexpr int kNcclInt32 = 2, kNcclSum = 0;
 
 } // namespace
+
+// trav_image.hip's grid_max_ref: the largest primitive id among n references into *word (which holds -1); at most 2048 workgroups stride over them
+int hagrid_impl::launch_max_ref(hagrid_ctx* ctx, const int* refs, int n, int* word) {
+    validate_arrays<<<std::min(grid_blocks(n, kBlock), 2048), kBlock, 0, ctx->stream>>>(nullptr, 0, nullptr, nullptr, 0, refs, n, 0, nullptr, word); HG_DBG(ctx);
+    return HAGRID_OK;
+}
 
 extern "C" size_t hagrid_grid_blob_bytes(const hagrid_grid* grid, int num_tris) {
     hagrid_blob_header h;

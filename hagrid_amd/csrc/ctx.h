@@ -358,6 +358,8 @@ bool trav_image_stale(const hagrid_ctx* ctx);        // a borrowed image whose o
 void trav_image_source_touched(hagrid_ctx* ctx, const void* ptr, size_t bytes);
 // the largest primitive id the grid refers to (-1: none): the image's when the context holds the image of this grid, else one pass over ref_ids and a read-back
 int grid_max_ref(hagrid_ctx* ctx, const hagrid_grid* grid, int* max_ref);
+// blob.hip: that pass -- the largest of n references (DEVICE) is atomicMax-ed into *word (DEVICE, holds -1); the kernel is the one that validates an unpacked blob
+int launch_max_ref(hagrid_ctx* ctx, const int* refs, int n, int* word);
 
 // build.hip: out[i] = in[0] + .. + in[i - 1] for i < n (in place when out == in), *total = the sum, *too_large = 1 when a prefix is 2^30 or more (never cleared
 // here) -- the construction's own plain scan (wave_prims.h: ctx_scan), for passes of other translation units.  All pointers DEVICE.  HAGRID_ENOMEM: no status words.

@@ -15,9 +15,13 @@
 // (overlap.h: query_box) and every triangle that has met the box passes the pair filter -- labels, surface, tri_meets of hagrid/tri_tri.h -- before the list
 // takes it.  The query record is read again for every such candidate instead of being held across the walk, and the 17 axes are evaluated one at a time in
 // rolled loops; the kernel is compiled for four wavefronts per SIMD (amdgpu_waves_per_eu), which the allocator meets with 128 VGPRs and no scratch.
+//
+// ORIENTED BOXES (hagrid_overlap_obbs, DESIGN.md 4.16, include/hagrid/obb.h) have a kernel of their own further down, obb_tris_kernel: the one above has no
+// register left for a third mode.
 #include "trav_common.h"
 #include "wave_prims.h"
 
+#include "hagrid/obb.h"
 #include "hagrid/overlap.h"
 
 #include <string>
@@ -27,6 +31,7 @@ using namespace hagrid_impl;
 using namespace hagrid_trav;
 namespace hc = hagrid::closest;
 namespace ho = hagrid::overlap;
+namespace hb = hagrid::obb;
 
 namespace {
 
@@ -143,7 +148,127 @@ int launch(hagrid_ctx* ctx, const char* who, const hagrid_grid* grid, const void
     return HAGRID_OK;
 }
 
+// ---- oriented boxes (hagrid_overlap_obbs; include/hagrid/obb.h) --------------------------------------------------------------------
+// A kernel of its own, not a mode of the one above (that one is at its register limit), with its shape: one query per lane, one wavefront per workgroup,
+// the stack in LDS, streaming loads of the records and streaming stores of the ids.  Across the walk a lane keeps its bounding box and the margin, nothing else
+// of the box: the record is read again for every candidate that has met the bounding box, as the contact form reads its query, and again for every block the
+// prune is asked about, which makes its three face normals anew (held across the walk they are 15 floats, and the kernel spilled: DESIGN.md 4.16).
+
+struct ObbArgs {
+    const float4* __restrict__ obbs;
+    const int* __restrict__ query_labels;    // one label per query and three per scene triangle, both given or both null
+    const int* __restrict__ tri_labels;
+    int* __restrict__ ids;
+    int* __restrict__ counts;                // may be null
+    unsigned long long* __restrict__ counters;   // may be null
+    int n, k, any;
+};
+
+__device__ __forceinline__ hb::Obb load_obb(const float4* __restrict__ obbs, int i) {
+    const float4* p = obbs + 4 * size_t(i);
+    const float4 c = p[0], u = p[1], v = p[2], w = p[3];
+    hb::Obb b;
+    b.c = vec3(c.x, c.y, c.z); b.u = vec3(u.x, u.y, u.z); b.v = vec3(v.x, v.y, v.z); b.w = vec3(w.x, w.y, w.z);
+    return b;
+}
+
+// the query of obb.h's ObbFilter for one lane
+struct DevObb {
+    const float4* __restrict__ obbs;
+    const int* __restrict__ labels;          // of the queries, or null
+    const int* __restrict__ tri_labels;
+    int i;
+    __device__ __forceinline__ hb::Obb box() const {
+        int j = i;
+        HAGRID_MADE_HERE(j);                  // the record is read HERE, at every use: no load of it is moved ahead of the walk's loops and kept
+        return load_obb(obbs, j);
+    }
+    __device__ __forceinline__ bool labelled() const { return labels != nullptr; }
+    __device__ __forceinline__ int label() const { return labels[i]; }
+    __device__ __forceinline__ int tri_label(int id, int j) const { return tri_labels[3 * size_t(id) + j]; }
+};
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) obb_tris_kernel(const OverlapGrid g, const ObbArgs a) {
+    __shared__ uint32_t s_w[hc::kMaxLevels][64], s_i[hc::kMaxLevels][64];
+    const int lane = threadIdx.x;
+    const int id = xcd_split(blockIdx.x, gridDim.x) * 64 + lane;
+    const bool live = id < a.n;
+    ho::Counts cnt;
+    cnt.cells = 0; cnt.sats = 0; cnt.pruned = 0;
+    if (live) {
+        vec3 lo, hi;
+        hb::ObbFilter<DevObb> filter;
+        filter.q.obbs = a.obbs; filter.q.labels = a.query_labels; filter.q.tri_labels = a.tri_labels; filter.q.i = id;
+        hb::FacePrune<DevObb> prune;
+        bool active;
+        int first;
+        {
+            const float4 r0 = nt_load4(a.obbs + 4 * size_t(id)), r1 = nt_load4(a.obbs + 4 * size_t(id) + 1), r2 = nt_load4(a.obbs + 4 * size_t(id) + 2),
+                         r3 = nt_load4(a.obbs + 4 * size_t(id) + 3);
+            hb::Obb b;
+            b.c = vec3(r0.x, r0.y, r0.z); b.u = vec3(r1.x, r1.y, r1.z); b.v = vec3(r2.x, r2.y, r2.z); b.w = vec3(r3.x, r3.y, r3.z);
+            first = __float_as_int(r0.w);
+            active = hb::obb_box(b, g.c.eps, lo, hi);
+            prune.set(filter.q, b, g.c.eps, true);
+        }
+        LdsStack st;
+        st.w_ = &s_w[0][lane]; st.i_ = &s_i[0][lane];
+        ho::IdList<ho::kMaxIds> list;
+        list.init(a.k, first);
+        if (active) ho::overlap_query(g, st, lo, hi, a.any != 0, list, cnt, filter, prune);
+        int* out = a.ids + size_t(id) * size_t(a.k);
+        if (a.k == 8) {         // the base is 16-byte aligned (checked on the host): two streaming stores
+            nt_store4(reinterpret_cast<float4*>(out), __int_as_float(list.id[0]), __int_as_float(list.id[1]), __int_as_float(list.id[2]), __int_as_float(list.id[3]));
+            nt_store4(reinterpret_cast<float4*>(out) + 1, __int_as_float(list.id[4]), __int_as_float(list.id[5]), __int_as_float(list.id[6]), __int_as_float(list.id[7]));
+        } else if (a.k == 4) {
+            nt_store4(reinterpret_cast<float4*>(out), __int_as_float(list.id[0]), __int_as_float(list.id[1]), __int_as_float(list.id[2]), __int_as_float(list.id[3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < ho::kMaxIds; j++)
+                if (j < a.k) __builtin_nontemporal_store(list.id[j], out + j);
+        }
+        if (a.counts) __builtin_nontemporal_store(list.count(), a.counts + id);
+    }
+    if (a.counters) add_batch_counters(a.counters, lane, live ? 1 : 0, cnt.cells, cnt.sats, cnt.pruned);
+}
+
 } // namespace
+
+extern "C" int hagrid_overlap_obbs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* obbs, int num_obbs, const void* query_labels,
+                                   const void* tri_labels, int k, void* ids, void* counts, void* counters, uint32_t flags) {
+    if (!ctx) return HAGRID_EINVAL;
+    if (num_obbs < 0) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: negative num_obbs");
+    if (num_obbs > 0 && !obbs) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: null box buffer");
+    if ((query_labels != nullptr) != (tri_labels != nullptr)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: query_labels and tri_labels are given together or not at all");
+    if (!aligned(query_labels, 4) || !aligned(tri_labels, 4)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: the labels must be 4-byte aligned");
+    if (flags & ~HAGRID_OVERLAP_ANY) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: unknown flag (HAGRID_OVERLAP_ANY is the only one)");
+    if (k < 1 || k > HAGRID_MAX_OVERLAP_IDS) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: k must be 1 .. HAGRID_MAX_OVERLAP_IDS");
+    if ((flags & HAGRID_OVERLAP_ANY) && k != 1) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: HAGRID_OVERLAP_ANY needs k = 1");
+    HG_TRY(check_walk_grid(ctx, "overlap_obbs", grid));
+    if (!aligned(counters, 8)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: the counters must be 8-byte aligned");
+    if (!aligned(counts, 4)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: the counts must be 4-byte aligned");
+    if (num_obbs == 0) return HAGRID_OK;
+    if (!tris || !ids) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: null triangle or id buffer");
+    if (!aligned(tris, 16) || !aligned(obbs, 16)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: triangles and boxes must be 16-byte aligned");
+    if (!aligned(ids, (k == 4 || k == 8) ? 16 : 4)) HG_FAIL(ctx, HAGRID_EINVAL, "overlap_obbs: the ids must be 16-byte aligned for k = 4 and k = 8, 4-byte aligned otherwise");
+    HG_HIP(ctx, hipSetDevice(ctx->device));
+    OverlapGrid g;
+    g.set(grid, tris);
+    g.clip.set(g.c.lo, g.c.hi);
+    ObbArgs a = {};
+    a.obbs = static_cast<const float4*>(obbs);
+    a.query_labels = static_cast<const int*>(query_labels);
+    a.tri_labels = static_cast<const int*>(tri_labels);
+    a.ids = static_cast<int*>(ids);
+    a.counts = static_cast<int*>(counts);
+    a.counters = static_cast<unsigned long long*>(counters);
+    a.n = num_obbs; a.k = k;
+    a.any = (flags & HAGRID_OVERLAP_ANY) ? 1 : 0;
+    obb_tris_kernel<<<grid_blocks(num_obbs, 64), 64, 0, ctx->stream>>>(g, a);
+    HG_DBG(ctx);
+    HG_HIP(ctx, hipGetLastError());
+    return HAGRID_OK;
+}
 
 extern "C" int hagrid_overlap_boxes(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* boxes, int num_boxes, int k, void* ids, void* counts,
                                     void* counters, uint32_t flags) {

@@ -531,17 +531,12 @@ void hagrid_impl::trav_image_source_touched(hagrid_ctx* ctx, const void* ptr, si
 }
 
 namespace {
-// the largest primitive id the grid refers to (sentinels of a compressed grid are negative): traverse_grid sizes its padded triangle copy by it
-__global__ void __launch_bounds__(kBlock) max_ref_kernel(const int* __restrict__ refs, int n, int* __restrict__ out) {
-    int m = -1;
-    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) m = max(m, refs[i]);
-    m = wave_max(m);
-    if (lane_id() == 0 && m >= 0) atomicMax(out, m);
-}
+// the largest primitive id the grid refers to (sentinels of a compressed grid are negative): traverse_grid sizes its padded triangle copy by it.  The scan
+// is blob.hip's, which reads the same array when it validates an unpacked grid (launch_max_ref).
 int read_max_ref(hagrid_ctx* ctx, const hagrid_grid* g, int* max_ref) {
     int* word = ctx->dscratch + kScrMaxRef;
     HG_HIP(ctx, hipMemsetAsync(word, 0xff, sizeof(int), ctx->stream));
-    max_ref_kernel<<<std::min(grid_blocks(g->num_refs, kBlock), 2048), kBlock, 0, ctx->stream>>>(static_cast<const int*>(g->ref_ids), g->num_refs, word); HG_DBG(ctx);
+    HG_TRY(launch_max_ref(ctx, static_cast<const int*>(g->ref_ids), g->num_refs, word));
     return read_back(ctx, word, max_ref, sizeof(int));
 }
 } // namespace

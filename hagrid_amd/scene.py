@@ -28,6 +28,7 @@ SEGMENT_RECORD_DTYPE = np.dtype([("q", "<f4", 3), ("d2", "<f4"), ("id", "<i4"), 
 # box-overlap queries (hagrid_overlap_boxes): 32 bytes per box, the layout of BBox with `first` in the pad slot after min
 BOX_QUERY_DTYPE = np.dtype([("min", "<f4", 3), ("first", "<i4"), ("max", "<f4", 3), ("pad", "<i4")])
 OVERLAP_ANY = 1
+OBB_DTYPE = np.dtype([("c", "<f4", 3), ("first", "<i4"), ("u", "<f4", 3), ("pad_u", "<i4"), ("v", "<f4", 3), ("pad_v", "<i4"), ("w", "<f4", 3), ("pad_w", "<i4")])
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 
@@ -1201,6 +1202,139 @@ def overlap_tris(tris: np.ndarray, queries: np.ndarray, k: int = 8, first=None, 
                 keep = ~labels_shared(np.asarray(query_labels).reshape(-1, 3)[o + rows], np.asarray(tri_labels).reshape(-1, 3)[col])
                 rows, col = rows[keep], col[keep]
             keep = overlap_pairs(T[col], b[rows]) & tri_tri_pairs(Q[o + rows], T[col])
+            rows, col = rows[keep], col[keep]
+            sz = np.bincount(rows, minlength=b.shape[0])
+            sizes[o:o + b.shape[0]] = sz
+            pos = np.arange(rows.size) - (np.cumsum(sz) - sz)[rows]
+            sel = pos < k
+            ids[o + rows[sel], pos[sel]] = col[sel]
+    return {"ids": ids, "counts": np.minimum(sizes, k + 1).astype(np.int32), "sizes": sizes}
+
+
+# ---- oriented-box queries: the numpy statement of include/hagrid/obb.h (same operations, same order, same truth values) ----------------------------
+
+def _obb_rows(obbs) -> np.ndarray:
+    return np.ascontiguousarray(obbs).view(np.float32).reshape(-1, 16)
+
+
+def make_obbs(centres, u, v, w, first=None) -> np.ndarray:
+    """OBB_DTYPE records from (n, 3) arrays: the box of record i is centres[i] + a u[i] + b v[i] + g w[i], |a|, |b|, |g| <= 1"""
+    c = np.asarray(centres, np.float32).reshape(-1, 3)
+    out = np.zeros(c.shape[0], dtype=OBB_DTYPE)
+    out["c"] = c; out["u"] = np.asarray(u, np.float32).reshape(-1, 3); out["v"] = np.asarray(v, np.float32).reshape(-1, 3); out["w"] = np.asarray(w, np.float32).reshape(-1, 3)
+    if first is not None:
+        out["first"] = np.asarray(first, np.int32)
+    return out
+
+
+def make_rotations(seed: int, count: int) -> np.ndarray:
+    """(count, 3, 3) float32 rotation matrices (columns: the axes) from normalised quaternions: +, *, / and a correctly rounded square root only"""
+    q = np.float32(2.0) * _uniform_rows(seed, count, 4) - np.float32(1.0)
+    q[(q * q).sum(axis=1) < np.float32(1e-3)] = np.float32([1, 0, 0, 0])
+    q = (q / np.sqrt((q * q).sum(axis=1, dtype=np.float32))[:, None]).astype(np.float32)
+    a, b, c, d = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    two = np.float32(2.0)
+    R = np.stack([np.stack([a * a + b * b - c * c - d * d, two * (b * c - a * d), two * (b * d + a * c)], axis=1),
+                  np.stack([two * (b * c + a * d), a * a - b * b + c * c - d * d, two * (c * d - a * b)], axis=1),
+                  np.stack([two * (b * d - a * c), two * (c * d + a * b), a * a - b * b - c * c + d * d], axis=1)], axis=1)
+    return R.astype(np.float32)
+
+
+def _unit_rows(x):
+    """rows of x scaled to length 1 (float32; a correctly rounded square root)"""
+    return (x / np.sqrt((x * x).sum(axis=1, dtype=np.float32))[:, None]).astype(np.float32)
+
+
+def make_obb_planks(lo, hi, count: int, seed: int) -> np.ndarray:
+    """thin diagonal planks: half extents 50 %, 2 %, 2 % of the diagonal, the long axis along one of the four body diagonals of the box, the centre within
+    10 % of the extent of the box's centre"""
+    lo = np.asarray(lo, np.float32); hi = np.asarray(hi, np.float32)
+    diag = bbox_diagonal(lo, hi)
+    ext = (hi - lo).astype(np.float32)
+    signs = np.float32([[1, 1, 1], [1, 1, -1], [1, -1, 1], [-1, 1, 1]])[np.arange(count) % 4]
+    u = (np.float32(0.5) * ext * signs).astype(np.float32)
+    e = np.eye(3, dtype=np.float32)[(np.arange(count) // 4) % 3]
+    v = _unit_rows(np.cross(u, e).astype(np.float32)) * (np.float32(0.02) * diag)
+    w = _unit_rows(np.cross(u, v).astype(np.float32)) * (np.float32(0.02) * diag)
+    c = ((lo + hi) * np.float32(0.5) + (np.float32(0.2) * _uniform_rows(seed, count, 3) - np.float32(0.1)) * ext).astype(np.float32)
+    return make_obbs(c, u, v.astype(np.float32), w.astype(np.float32))
+
+
+def _obb_tri(O, T):
+    """obb_meets of obb.h on broadcastable float32 arrays: O = the 16 columns of the box records, T = the 12 columns of the Tri records"""
+    c, u, v, w = (O[0], O[1], O[2]), (O[4], O[5], O[6]), (O[8], O[9], O[10]), (O[12], O[13], O[14])
+    v0 = (T[0], T[1], T[2]); v1 = _sub3(v0, (T[4], T[5], T[6])); v2 = (v0[0] + T[8], v0[1] + T[9], v0[2] + T[10])
+    edges = (_sub3(v0, v1), _sub3(v2, v0), _sub3(v2, v1))
+
+    def separates(L):
+        centre = _dot3(L, c)
+        radius = (np.abs(_dot3(L, u)) + np.abs(_dot3(L, v))) + np.abs(_dot3(L, w))
+        p0, p1, p2 = _dot3(L, v0), _dot3(L, v1), _dot3(L, v2)
+        return (np.fmin(p0, np.fmin(p1, p2)) > centre + radius) | (np.fmax(p0, np.fmax(p1, p2)) < centre - radius)
+
+    axes = [_cross3(v, w), _cross3(w, u), _cross3(u, v), (T[3], T[7], T[11])] + [_cross3(a, e) for a in (u, v, w) for e in edges]
+    ok = ~separates(axes[0])
+    for L in axes[1:]:
+        ok = ok & ~separates(L)
+    return ok
+
+
+def obb_pairs(tris: np.ndarray, obbs: np.ndarray) -> np.ndarray:
+    """Triangle i against oriented box i ((n, 16) float32 rows or OBB_DTYPE; `first` is not looked at): does the triangle MEET the box -- obb_meets of
+    include/hagrid/obb.h, the separating-axis test over 13 axes (the box's three face normals, the stored normal, the nine cross products of a box axis
+    with a triangle edge).  This is the pair alone: a query also asks that the triangle meet the box's bounding box (obb_boxes)."""
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); O = _obb_rows(obbs)
+    with np.errstate(all="ignore"):
+        return _obb_tri([O[:, i] for i in range(16)], [T[:, i] for i in range(12)])
+
+
+def obb_boxes(obbs: np.ndarray, grid_lo, grid_hi) -> np.ndarray:
+    """obb_box of obb.h: (n, 8) float32 box rows -- c -+ ((|u| + |v|) + |w|) per component, grown by eps = 2^-16 of the largest |coordinate| of the grid box
+    on every side, `first` kept; an INACTIVE record (a component that is not finite) gets the inactive box min = 1, max = 0.  Not clipped yet."""
+    O = _obb_rows(obbs)
+    glo = np.asarray(grid_lo, np.float32); ghi = np.asarray(grid_hi, np.float32)
+    eps = np.float32(max(np.abs(glo).max(), np.abs(ghi).max())) * np.float32(1.52587890625e-05)
+    B = np.zeros((O.shape[0], 8), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        r = (np.abs(O[:, 4:7]) + np.abs(O[:, 8:11])) + np.abs(O[:, 12:15])
+        B[:, 0:3] = (O[:, 0:3] - r) - eps
+        B[:, 4:7] = (O[:, 0:3] + r) + eps
+    off = ~np.isfinite(O[:, [0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14]]).all(axis=1)
+    B[off, 0:3] = np.float32(1.0); B[off, 4:7] = np.float32(0.0)
+    B[:, 3] = O[:, 3]
+    return B
+
+
+def overlap_obbs(tris: np.ndarray, obbs: np.ndarray, k: int = 8, query_labels=None, tri_labels=None, grid=None, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of hagrid_overlap_obbs by brute force.  With aabb(box) = obb_boxes, clipped (clip_boxes) to the box of the grid the query runs over
+    (`grid` = (min, max), None: grid_box(tris)), S_i = {j >= first_i : the label of box i (>= 0) is no label of triangle j, triangle j has a surface,
+    triangle j meets aabb(box_i) (overlap_pairs), obb_pairs(triangle j, box_i)}: "ids" (n, k) int32 = the min(k, |S|) smallest ids ascending, unused slots
+    -1; "counts" = min(|S|, k + 1); "sizes" = |S|.  query_labels (n,) and tri_labels (N, 3) int32: both or neither.  Pairs whose bounding intervals miss
+    each other are left out before the tests: the triangle / box test says the same of them."""
+    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
+    glo, ghi = grid_box(tris) if grid is None else grid
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); O = _obb_rows(obbs)
+    B = clip_boxes(obb_boxes(O, glo, ghi), glo, ghi)
+    n, N = O.shape[0], T.shape[0]
+    first = O[:, 3].view(np.int32).astype(np.int64)
+    ids = np.full((n, k), -1, dtype=np.int32); sizes = np.zeros(n, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        V = tri_vertices(T)
+        tmin = np.fmin(V[:, 0], np.fmin(V[:, 1], V[:, 2])); tmax = np.fmax(V[:, 0], np.fmax(V[:, 1], V[:, 2]))
+        surface = tris_have_surface(T)
+        tid = np.arange(N, dtype=np.int64)[None, :]
+        m = max(1, chunk_pairs // max(N, 1))
+        for o in range(0, n if N else 0, m):
+            b = B[o:o + m]
+            active = (b[:, 0:3] <= b[:, 4:7]).all(axis=1)
+            near = ~((tmin[None, :, :] > b[:, None, 4:7]) | (tmax[None, :, :] < b[:, None, 0:3])).any(axis=2)      # the bounds check of the triangle / box test
+            near &= active[:, None] & surface[None, :] & (tid >= first[o:o + m, None])
+            rows, col = np.nonzero(near)                       # by row, then by id ascending
+            if query_labels is not None:
+                ql = np.asarray(query_labels, np.int32).reshape(-1)[o + rows]
+                keep = ~((ql >= 0)[:, None] & (ql[:, None] == np.asarray(tri_labels, np.int32).reshape(-1, 3)[col])).any(axis=1)
+                rows, col = rows[keep], col[keep]
+            keep = overlap_pairs(T[col], b[rows]) & obb_pairs(T[col], O[o + rows])
             rows, col = rows[keep], col[keep]
             sz = np.bincount(rows, minlength=b.shape[0])
             sizes[o:o + b.shape[0]] = sz

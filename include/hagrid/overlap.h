@@ -55,7 +55,8 @@
 //       voxel (the same test in float, the truncating casts of compute_range) by a few more: all far inside eps = 128 ulp -- and the
 //       leaf of that voxel is reached, because the integer range of every sub-block above it contains the voxel; by (a) the cell of the
 //       leaf lists the triangle.
-// Three counts per box: cells visited, triangle / box tests evaluated, sub-blocks pruned.
+// Three counts per box: cells visited, triangle / box tests evaluated, sub-blocks pruned.  A query may bring a BLOCK PRUNE of its own (NoPrune, the
+// default, drops nothing; obb.h's FacePrune): it is asked of every sub-block next to the integer range, and of every top-level cell of the range.
 //
 // ---- contact queries (hagrid_amd.h: hagrid_overlap_tris) ----------------------------------------------------------
 // A query may be a TRIANGLE A instead of a box: S = {j >= first : no label >= 0 of A is a label of j, j has a surface, j meets box(A), tri_meets(A, j)} with
@@ -170,6 +171,12 @@ struct NoFilter {
     HOST DEVICE bool accept(int, const Tri&, int&) const { return true; }
 };
 
+/// The block prune of a query: drops(c, x, y, z, s) -> true leaves out the block of 2^s voxels per axis at voxel (x, y, z) -- a sub-block, or a top-level
+/// cell before its word is read -- although its integer voxel range meets the box's.  This one drops nothing: the box and contact queries.  (obb.h: FacePrune)
+struct NoPrune {
+    HOST DEVICE bool drops(const GridConsts&, int, int, int, int) const { return false; }
+};
+
 /// the definition: every triangle, in order, against the clipped box.  tri_at(j) -> Tri.  Returns the number of tests evaluated.
 template <typename F, typename L, typename P = NoFilter>
 HOST DEVICE inline int brute_force(F tri_at, int num_tris, const Clip& clip, const vec3& box_lo, const vec3& box_hi, bool any, L& list, const P& filter = P()) {
@@ -236,12 +243,12 @@ HOST DEVICE inline void test_cell(const G& g, const vec3& lo, const vec3& hi, bo
 }
 
 /// one top-level cell of the range: descend its sub-blocks (block_walk.h) while their voxel ranges meet the box's
-template <typename G, typename S, typename L, typename P = NoFilter>
+template <typename G, typename S, typename L, typename P = NoFilter, typename B = NoPrune>
 HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3& hi, bool any, const VoxelRange& r, int tx, int ty, int tz, uint32_t& last_cell,
-                                  L& list, Counts& n, const P& filter = P()) {
+                                  L& list, Counts& n, const P& filter = P(), const B& region = B()) {
     const GridConsts& c = g.c;
     auto prune = [&](int x, int y, int z, int s) {
-        const bool out = misses(r, x, y, z, s);
+        const bool out = misses(r, x, y, z, s) || region.drops(c, x, y, z, s);
         if (out) n.pruned++;
         return out;
     };
@@ -258,8 +265,8 @@ HOST DEVICE inline void visit_top(const G& g, S& st, const vec3& lo, const vec3&
 
 /// the answer for the box [lo, hi] over the grid g: equal to brute_force over all triangles (with ANY: some member of S, or none).
 /// `list` arrives initialised (init(k, first)).
-template <typename G, typename S, typename L, typename P = NoFilter>
-HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, const vec3& box_hi, bool any, L& list, Counts& n, const P& filter = P()) {
+template <typename G, typename S, typename L, typename P = NoFilter, typename B = NoPrune>
+HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, const vec3& box_hi, bool any, L& list, Counts& n, const P& filter = P(), const B& region = B()) {
     const GridConsts& c = g.c;
     n.cells = 0; n.sats = 0; n.pruned = 0;
     vec3 lo = box_lo, hi = box_hi;
@@ -271,7 +278,8 @@ HOST DEVICE inline void overlap_query(const G& g, S& st, const vec3& box_lo, con
     for (int z = z0; z <= z1; z++)
         for (int y = y0; y <= y1; y++)
             for (int x = x0; x <= x1; x++) {
-                visit_top(g, st, lo, hi, any, r, x, y, z, last_cell, list, n, filter);
+                if (region.drops(c, x << c.shift, y << c.shift, z << c.shift, c.shift)) { n.pruned++; continue; }
+                visit_top(g, st, lo, hi, any, r, x, y, z, last_cell, list, n, filter, region);
                 if (any && list.found()) return;
             }
 }

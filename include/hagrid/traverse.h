@@ -95,6 +95,15 @@ inline void overlap_tris(const Grid& grid, const Tri* tris, const Tri* queries, 
     detail::check(detail::current_ctx(), hagrid_overlap_tris(detail::current_ctx(), &p, tris, queries, num_queries, first, query_labels, tri_labels, k, ids, counts, counters,
                                                              any ? HAGRID_OVERLAP_ANY : 0u));
 }
+/// Extension: oriented-box queries (hagrid_amd.h: hagrid_overlap_obbs; the pair, the query and the prune: obb.h).  obbs: num_obbs records of 64 bytes
+/// (c.xyz, first, u.xyz, 0, v.xyz, 0, w.xyz, 0), query_labels (1 per box) and tri_labels (3 per scene triangle): both or neither; ids, counts, counters and
+/// any as for overlap_boxes -- all DEVICE pointers.  Asynchronous on the context's stream.
+inline void overlap_obbs(const Grid& grid, const Tri* tris, const void* obbs, int num_obbs, int k, int* ids, int* counts = nullptr, void* counters = nullptr, bool any = false,
+                         const int* query_labels = nullptr, const int* tri_labels = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_overlap_obbs(detail::current_ctx(), &p, tris, obbs, num_obbs, query_labels, tri_labels, k, ids, counts, counters,
+                                                             any ? HAGRID_OVERLAP_ANY : 0u));
+}
 
 /// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice, hagrid_fill_lattice; the record, the paging and the walk:
 /// crossings.h).  records: num_rays Hit-shaped records (count, t_first, length, winding bits); counters: nullptr or int64[4] -- DEVICE pointers.  Asynchronous.

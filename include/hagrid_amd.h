@@ -459,6 +459,25 @@ int hagrid_overlap_lattice(hagrid_ctx* ctx, const hagrid_grid* grid, const void*
 int hagrid_overlap_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* queries, int num_queries, const void* first,
                         const void* query_labels, const void* tri_labels, int k, void* ids, void* counts, void* counters, uint32_t flags);
 
+/* Extension (no reference counterpart): ORIENTED-BOX queries -- for every rotated (or sheared) box of a batch, which triangles of the scene meet it (a rigid
+ * body's bounding box, a robot link, a plank or a camera-aligned slab against a mesh; "is this rotated region empty?").  A record is 64 bytes, four float4:
+ * float32 c.xyz and int32 first (the pad slot, as a box record carries it), then float32 u.xyz, v.xyz, w.xyz, each with pad 0: the box is
+ * {c + a u + b v + g w : |a|, |b|, |g| <= 1}.  The axes need be neither normalised nor orthogonal; nothing is divided or normalised.  A triangle MEETS the
+ * box exactly when obb_meets of include/hagrid/obb.h says so: no axis of the separating-axis test -- the three face normals of the box, the stored normal
+ * of the triangle, the nine cross products of a box axis with a triangle edge -- strictly separates them; float32 without contraction in the expression
+ * order of that header, exact on half-integer coordinates up to 16.  With
+ *   S_i = {j >= first_i : pair (i, j) is not skipped, triangle j has a surface, triangle j meets aabb(box_i), obb_meets(box_i, triangle j)},
+ * m = |S_i| and 1 <= k <= HAGRID_MAX_OVERLAP_IDS, ids, counts, paging and HAGRID_OVERLAP_ANY are those of hagrid_overlap_boxes.  aabb(box) is
+ * c -+ (|u| + |v| + |w|) per component, grown by the grid's margin on every side and clipped as every box is; in exact arithmetic it removes nothing.  A
+ * record with a component that is not finite is INACTIVE: count 0, ids -1.  A zero axis (a flat box) is legal; the test is then conservative where the pair
+ * is coplanar.  query_labels: DEVICE int32[num_obbs], tri_labels: DEVICE int32[3 per scene triangle], both given or both NULL: pair (i, j) is SKIPPED when
+ * the label of box i is >= 0 and is one of the three of triangle j -- with body ids as labels a body's box does not see the body's own triangles.  The
+ * walk also leaves out every block of the grid that a face normal of the box separates from the box, so a thin diagonal box does not visit its bounding
+ * box.  counters: as for boxes; the third total counts the pairs offered to obb_meets.  HAGRID_EINVAL: as for hagrid_overlap_boxes
+ * (records 16-byte aligned, labels 4), and one label array without the other.  num_obbs = 0 is HAGRID_OK. */
+int hagrid_overlap_obbs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* obbs, int num_obbs, const void* query_labels,
+                        const void* tri_labels, int k, void* ids, void* counts, void* counters, uint32_t flags);
+
 /* Extension (no reference counterpart): CROSSING queries -- ALL the surfaces a ray crosses, and from that whether a point lies inside a closed surface
  * (thickness and path length through a solid, signed distance = hagrid_closest_points + inside, solid voxelization = hagrid_overlap_lattice + inside;
  * Embree's rtcIntersect with a collecting filter, Open3D's compute_occupancy).  Ray i CROSSES triangle j exactly when intersect_prim_ray of
