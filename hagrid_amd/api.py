@@ -498,8 +498,76 @@ def tris_within(grid: Grid, tris, points, k: int = MAX_NEAREST, query_labels=Non
     (n + 1,), "ids" int32 and "d2" float32 (total,): the triangles of point i are offsets[i] .. offsets[i + 1], sorted by (d2, id) -- what scene.tris_within
     states -- and "pages", how many launches it took, and "complete": False only when max_pages (None: no bound) ended the paging before every list had
     ended; the lists are then prefixes.  Meant for radii that hold tens of triangles: every page walks the ball of the pages before it again, so a list of L
-    triangles costs L / k launches over O(L) triangles each, and r = inf lists the whole scene for every point, k at a time."""
+    triangles costs L / k launches over O(L) triangles each, and r = inf lists the whole scene for every point, k at a time.  ball_lists gives the same lists
+    in one pass."""
     return _paged_csr(nearest_tris, 4, grid, tris, points, k, query_labels, tri_labels, max_pages)
+
+
+def ball_refs(grid: Grid, tris: int, points: int, n: int, counts: int = 0, offsets: int = 0, entries: int = 0, capacity: int = 0, query_labels: int = 0,
+              tri_labels: int = 0, counters: int = 0):
+    """Extension (hagrid_ball_refs): stage 1 of the BALL LISTS -- the walk of nearest_tris with a bound that stays r * r, so that it sees every candidate.  A
+    REFERENCE is one accepted offer; a triangle arrives once per visit of a cell that lists it, so references hold duplicates.  Count mode (offsets = 0,
+    entries = 0, capacity = 0): counts[i] (int32[n]) = R_i, the references of query i.  Fill mode: offsets int64[n + 1] -- query i owns the slots
+    [offsets[i], offsets[i + 1]) of `entries` (capacity slots of NEAREST_ENTRY_DTYPE) and writes its first min(R_i, room) references in walk order, then the
+    empty entry (+inf, -1); the room rule is list_crossings'.  counters: 0, or a device int64[6] added to (queries, cells visited, triangles tested,
+    sub-blocks pruned, references written, queries that did not fit).  Device addresses; asynchronous on the manager's stream.  Walks the construction
+    format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_ball_refs(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(points or 0), int(n), C.c_void_p(query_labels or 0),
+                                        C.c_void_p(tri_labels or 0), C.c_void_p(offsets or 0), C.c_void_p(counts or 0), C.c_void_p(entries or 0), int(capacity),
+                                        C.c_void_p(counters or 0), 0), "ball_refs")
+
+
+def unique_lists(num_lists: int, offsets: int, entries: int, capacity: int, counts: int, counters: int = 0, mem=None):
+    """Extension (hagrid_unique_lists): stage 2 -- every segment [offsets[i], offsets[i + 1]) of `entries` in place: entries with id < 0 or a NaN d2 dropped, the
+    rest sorted by (d2, id), equal ids reduced to one (equal ids must carry equal d2 bits), the survivors at the front, the empty entry behind them;
+    counts[i] (int32) = how many survive.  Needs no grid.  counters: 0, or a device int64[4] added to (lists, slots, survivors, lists sorted in global
+    memory).  scene.unique_lists states it in numpy.  mem: the manager whose stream it runs on (None: the most recent one)."""
+    mem = mem or _current
+    _check(mem, mem._L.hagrid_unique_lists(mem._ctx, int(num_lists), C.c_void_p(offsets or 0), C.c_void_p(entries or 0), int(capacity), C.c_void_p(counts or 0),
+                                           C.c_void_p(counters or 0), 0), "unique_lists")
+
+
+def compact_lists(num_lists: int, offsets: int, entries: int, capacity: int, counts: int, out_offsets: int, out_entries: int, out_capacity: int, counters: int = 0,
+                  mem=None):
+    """Extension (hagrid_compact_lists): stage 3 -- the first min(counts[i], room of the source, room of the destination) entries of segment i go to
+    [out_offsets[i], out_offsets[i + 1]) of out_entries, the rest of that room gets the empty entry.  counters: 0, or a device int64[4] added to (lists,
+    entries copied, lists cut short, 0).  scene.compact_lists states it in numpy."""
+    mem = mem or _current
+    _check(mem, mem._L.hagrid_compact_lists(mem._ctx, int(num_lists), C.c_void_p(offsets or 0), C.c_void_p(entries or 0), int(capacity), C.c_void_p(counts or 0),
+                                            C.c_void_p(out_offsets or 0), C.c_void_p(out_entries or 0), int(out_capacity), C.c_void_p(counters or 0), 0), "compact_lists")
+
+
+def ball_lists(grid: Grid, tris, points, query_labels=None, tri_labels=None) -> dict:
+    """ALL the triangles within r of every point, nearest first, in CSR form, WITHOUT paging: ball_refs (count), torch.cumsum, ball_refs (fill), unique_lists,
+    torch.cumsum, compact_lists on torch tensors; TWO scalars go to the host (the totals that size the scratch and the output).  Arguments as tris_within;
+    the manager must run on torch's current stream (mem.use_stream(torch.cuda.current_stream().cuda_stream)).  Returns "offsets" int64 (n + 1,), "ids" int32
+    and "d2" float32 (total,) exactly as tris_within does -- what scene.tris_within states -- and "refs", the total of R_i: the scratch (8 bytes each) a
+    caller of the staged entry points needs.  Linear in the ball's content where tris_within is quadratic; r = inf lists the whole scene for every point."""
+    import torch
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    mem = grid.mem or _current
+    pts = points.reshape(-1, 4)
+    n = int(pts.shape[0])
+    dev = pts.device
+    ql = ptr(query_labels) if query_labels is not None else 0
+    tl = ptr(tri_labels) if query_labels is not None else 0
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    ball_refs(grid, ptr(tris), pts.data_ptr(), n, counts=counts.data_ptr(), query_labels=ql, tri_labels=tl)
+    ref_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum(counts, 0, dtype=torch.int64, out=ref_offsets[1:])
+    refs = int(ref_offsets[-1].item())
+    scratch = torch.empty((refs, 2), dtype=torch.int32, device=dev)
+    ball_refs(grid, ptr(tris), pts.data_ptr(), n, offsets=ref_offsets.data_ptr(), entries=scratch.data_ptr() if refs else 0, capacity=refs, query_labels=ql, tri_labels=tl)
+    unique_lists(n, ref_offsets.data_ptr(), scratch.data_ptr() if refs else 0, refs, counts.data_ptr(), mem=mem)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[-1].item())
+    out = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    compact_lists(n, ref_offsets.data_ptr(), scratch.data_ptr() if refs else 0, refs, counts.data_ptr(), offsets.data_ptr(), out.data_ptr() if total else 0, total, mem=mem)
+    return {"offsets": offsets, "ids": out[:, 1].contiguous(), "d2": out[:, 0].contiguous().view(torch.float32), "refs": refs}
 
 
 def segment_tris(grid: Grid, tris: int, segments: int, n: int, k: int, entries: int = 0, records: int = 0, cursors: int = 0, query_labels: int = 0,
@@ -1061,6 +1129,6 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "traverse_grid_filtered", "skip_filters", "RAY_MASK_ALL",
-           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "segment_tris", "tris_near_segments", "SEGMENT_DTYPE", "SEGMENT_RECORD_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "ball_refs", "unique_lists", "compact_lists", "ball_lists", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "segment_tris", "tris_near_segments", "SEGMENT_DTYPE", "SEGMENT_RECORD_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
            "overlap_tris", "self_intersections", "overlap_obbs", "obb_records", "tris_in_obbs", "OBB_DTYPE",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

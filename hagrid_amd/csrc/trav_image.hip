@@ -138,7 +138,7 @@ __device__ __forceinline__ bool general_record(const ImgK& k, const int IDB, uin
     for (int i = 0; i < n; i++) wide_ids = wide_ids || uint32_t(k.refs[begin + i]) >= NONE - 3u;
     if (wide_ids) atomicAdd(status + 1, 1);
     if (!fits) {
-        // the cell's wide record: the first entry that names the cell draws its index; the record holds the CELL until image_general_patch
+        // the cell's wide record: the first entry that names the cell draws its index; the record holds the CELL until image_general_wide
         // replaces it by that index (the winner's store may not be visible to the other entries of the cell during this launch)
         if (atomicCAS(claim + c, -1, -2) == -1) claim[c] = atomicAdd(status + 2, 1);
         put_bits(rl, rh, 48, 32, uint32_t(c));
@@ -212,12 +212,11 @@ __global__ void __launch_bounds__(kBlock) image_general_vtop(const ImgK k, const
     if ((e & 3u) == 1u) general_record(k, IDB, k.entries[(e >> 2) + oct], ox, oy, oz, rec, claim, status);      // the child: its cell or its link
     else general_record(k, IDB, e, ox, oy, oz, rec, claim, status, 1u);                                           // a leaf (its cell from here), or a larger block from one level down
 }
-// records that name a wide cell get the index of its wide record; the wide records themselves
-__global__ void __launch_bounds__(kBlock) image_general_patch(const int IDB, uint4* __restrict__ recs, int num_entries, const int* __restrict__ claim, int first_wide) {
+// records that name a wide cell get the index of its wide record; the wide records themselves.  ONE launch over max(records, cells) threads (the product
+// library's kernel budget): thread i patches record i and writes the wide record of cell i; the two halves read `claim` and write different arrays.
+__device__ __forceinline__ void general_patch(const int IDB, uint4* __restrict__ recs, int i, const int* __restrict__ claim, int first_wide) {
     const int NI = 80 / IDB, LAST = 48 + (NI - 1) * IDB;
     const uint32_t NONE = (1u << IDB) - 1u;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= num_entries) return;
     uint4 r = recs[i];
     unsigned long long rl = r.x | (unsigned long long)r.y << 32, rh = r.z | (unsigned long long)r.w << 32;
     const uint32_t last = uint32_t(rh >> (LAST - 64)) & NONE;
@@ -226,8 +225,10 @@ __global__ void __launch_bounds__(kBlock) image_general_patch(const int IDB, uin
     put_bits(rl, rh, 48, 32, uint32_t(first_wide + claim[c]));
     recs[i] = make_uint4(uint32_t(rl), uint32_t(rl >> 32), uint32_t(rh), uint32_t(rh >> 32));
 }
-__global__ void __launch_bounds__(kBlock) image_general_wide(const ImgK k, int num_cells, const int* __restrict__ claim, uint4* __restrict__ wide) {
+__global__ void __launch_bounds__(kBlock) image_general_wide(const ImgK k, const int IDB, uint4* __restrict__ recs, int num_records, int first_wide, int num_cells,
+                                                             const int* __restrict__ claim, uint4* __restrict__ wide) {
     const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c < num_records) general_patch(IDB, recs, c, claim, first_wide);
     if (c >= num_cells || claim[c] < 0) return;
     uint4 w;
     if (k.small_cells) {
@@ -291,9 +292,8 @@ int build_general(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img) {
         uint4* wide = static_cast<uint4*>(hagrid_mem_alloc(ctx, size_t(std::max(h[2], 1)) * 16u));
         if (!wide) { rc = HAGRID_ENOMEM; break; }
         if (h[2] > 0) {
-            image_general_patch<<<grid_blocks((long long)records, kBlock), kBlock, 0, st>>>(idb, recs, int(records), claim, 0);
+            image_general_wide<<<grid_blocks(std::max((long long)records, (long long)num_cells), kBlock), kBlock, 0, st>>>(k, idb, recs, int(records), 0, num_cells, claim, wide);
             HG_DBG(ctx);
-            image_general_wide<<<grid_blocks(num_cells, kBlock), kBlock, 0, st>>>(k, num_cells, claim, wide); HG_DBG(ctx);
         }
         img.vtop_k = vtop ? 1 : 0; img.vtop_base = vtop ? uint32_t(k.num_entries) : 0u;
         img.blocks = recs; img.block_bytes = records * 16u; img.table = wide; img.table_bytes = size_t(std::max(h[2], 1)) * 16u;
@@ -311,10 +311,10 @@ int build_general(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img) {
 // TABLE: the block of top-level cell T has depth metas[T] & 3 and starts at record offsets[T]; its bound bytes count from the origin
 // of the top-level cell, biased by 128.
 // TABLE only: a cell whose bounds do not fit the bytes (the large cells of empty space) gets a WIDE record, as in the general layout below: the record names the
-// cell (image_general_patch replaces it by the index of the cell's wide record), status word 2 counts the wide records, claim[c] holds their indices.
-template <bool TABLE>
-__global__ void __launch_bounds__(64) image_slim_fill(const ImgK k, const int D, const int IDB, uint4* __restrict__ recs, uint2* __restrict__ table, int* __restrict__ status,
-                                                      const uint32_t* __restrict__ metas, const int* __restrict__ offsets, int* __restrict__ claim) {
+// cell (image_general_wide replaces it by the index of the cell's wide record), status word 2 counts the wide records, claim[c] holds their indices.
+// (TABLE is an ARGUMENT, uniform over the launch, like D and IDB: one kernel for both layouts -- the product library's kernel budget; the records are the same bits.)
+__global__ void __launch_bounds__(64) image_slim_fill(const ImgK k, const int D, const int IDB, const bool TABLE, uint4* __restrict__ recs, uint2* __restrict__ table,
+                                                      int* __restrict__ status, const uint32_t* __restrict__ metas, const int* __restrict__ offsets, int* __restrict__ claim) {
     const int NI = 80 / IDB;
     const uint32_t NONE = (1u << IDB) - 1u;
     const int T = blockIdx.x, lane = threadIdx.x;
@@ -407,8 +407,8 @@ int build_slim(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img, uint2* table
         if (idb == 20 && ctx->opt_image_slim == 2) continue;           // "traverse.image_slim" = 2: the 26-bit form whatever the ids (tests)
         (void)hipMemsetAsync(status, 0, 3 * sizeof(int), ctx->stream);
         if (claim) (void)hipMemsetAsync(claim, 0xFF, size_t(k.num_cells) * sizeof(int), ctx->stream);
-        if (uniform) image_slim_fill<false><<<k.num_top, 64, 0, ctx->stream>>>(k, D, idb, recs, table, status, nullptr, nullptr, nullptr);
-        else         image_slim_fill<true><<<k.num_top, 64, 0, ctx->stream>>>(k, D, idb, recs, table, status, metas, offsets, claim);
+        if (uniform) image_slim_fill<<<k.num_top, 64, 0, ctx->stream>>>(k, D, idb, false, recs, table, status, nullptr, nullptr, nullptr);
+        else         image_slim_fill<<<k.num_top, 64, 0, ctx->stream>>>(k, D, idb, true, recs, table, status, metas, offsets, claim);
         HG_DBG(ctx);
         int h[3] = {0, 0, 0};
         const int rc = read_back(ctx, status, h, sizeof(h));
@@ -422,9 +422,9 @@ int build_slim(hagrid_ctx* ctx, const ImgK& k, TravImageCache& img, uint2* table
             uint4* both = static_cast<uint4*>(hagrid_mem_alloc(ctx, (table16 + size_t(h[2])) * 16u));
             if (!both) { result = HAGRID_ENOMEM; break; }
             (void)hipMemcpyAsync(both, table, size_t(k.num_top) * 8u, hipMemcpyDeviceToDevice, ctx->stream);
-            image_general_patch<<<grid_blocks(records, kBlock), kBlock, 0, ctx->stream>>>(idb, recs, int(records), claim, int(table16));
+            image_general_wide<<<grid_blocks(std::max(records, (long long)k.num_cells), kBlock), kBlock, 0, ctx->stream>>>(k, idb, recs, int(records), int(table16), k.num_cells, claim,
+                                                                                                                         both + table16);
             HG_DBG(ctx);
-            image_general_wide<<<grid_blocks(k.num_cells, kBlock), kBlock, 0, ctx->stream>>>(k, k.num_cells, claim, both + table16); HG_DBG(ctx);
             img.table = both; img.table_bytes = (table16 + size_t(h[2])) * 16u; img.wide_records = h[2];      // (the caller's table is released with its other temporaries)
         } else { img.table = nullptr; img.table_bytes = size_t(k.num_top) * 8u; img.wide_records = 0; }
         img.blocks = recs; img.block_bytes = bytes; img.slim = idb;

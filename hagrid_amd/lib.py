@@ -139,6 +139,9 @@ SIGNATURES = {
     "hagrid_traverse_grid_filtered": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.c_uint32]),
     "hagrid_closest_points": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _vp, C.c_uint32]),
     "hagrid_nearest_tris": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
+    "hagrid_ball_refs": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_uint32]),
+    "hagrid_unique_lists": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _vp, C.c_uint32]),
+    "hagrid_compact_lists": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, C.c_uint32]),
     "hagrid_segment_tris": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_boxes": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_lattice": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), _i32, _vp, _vp, _vp, C.c_uint32]),

@@ -790,6 +790,59 @@ def tris_within(tris: np.ndarray, points: np.ndarray, query_labels=None, tri_lab
     return _all_lists(tris, points, 4, query_labels, tri_labels, chunk_pairs)
 
 
+# ---- ball lists, stages 2 and 3: the numpy statement of include/hagrid/unique_lists.h ----------------------------------------------
+
+def _segment_ranges(offsets, capacity: int):
+    """the room rule of hagrid_list_crossings for CSR segments: (first, room) per segment"""
+    off = np.asarray(offsets, dtype=np.int64)
+    b, e = off[:-1], off[1:]
+    ok = (b >= 0) & (e >= b) & (e <= int(capacity))
+    return np.where(ok, b, 0), np.where(ok, e - b, 0)
+
+
+def empty_entry() -> np.ndarray:
+    e = np.zeros((), dtype=NEAREST_ENTRY_DTYPE)
+    e["d2"] = np.float32(np.inf); e["id"] = -1
+    return e
+
+
+def unique_lists(offsets, entries: np.ndarray, capacity=None):
+    """The definition of hagrid_unique_lists: every segment [offsets[i], offsets[i + 1]) of entries (NEAREST_ENTRY_DTYPE (capacity,)) -- entries with id < 0 or a
+    NaN d2 dropped, the rest sorted by (d2 by float comparison, id), equal ids reduced to one (equal ids carry equal d2 bits: the contract), the survivors at
+    the front, (+inf, -1) in every other slot.  Returns (the entries afterwards, counts int32 (n,)); slots outside every segment are unchanged."""
+    out = np.ascontiguousarray(entries).view(NEAREST_ENTRY_DTYPE).reshape(-1).copy()
+    cap = out.size if capacity is None else int(capacity)
+    first, room = _segment_ranges(offsets, cap)
+    counts = np.zeros(first.size, dtype=np.int32)
+    for i in range(first.size):
+        seg = out[first[i]:first[i] + room[i]]
+        with np.errstate(invalid="ignore"):
+            v = seg[(seg["id"] >= 0) & ~np.isnan(seg["d2"])]
+        # (d2 + 0 turns -0.0 into +0.0: the sort key is the float VALUE; the bits that travel are the entry's own)
+        v = v[np.lexsort((v["id"], v["d2"] + np.float32(0.0)))]
+        if v.size:
+            v = v[np.concatenate([[True], v["id"][1:] != v["id"][:-1]])]
+        seg[:v.size] = v
+        seg[v.size:] = empty_entry()
+        counts[i] = v.size
+    return out, counts
+
+
+def compact_lists(offsets, entries: np.ndarray, counts, out_offsets, out_capacity: int, capacity=None, fill=None) -> np.ndarray:
+    """The definition of hagrid_compact_lists: out_entries (out_capacity,) -- the first min(counts[i], room of the source, room of the destination) entries of
+    segment i at out_offsets[i], (+inf, -1) in the rest of the destination's room; slots outside every destination segment keep `fill` (None: zero bytes)."""
+    src = np.ascontiguousarray(entries).view(NEAREST_ENTRY_DTYPE).reshape(-1)
+    cap = src.size if capacity is None else int(capacity)
+    out = np.zeros(int(out_capacity), dtype=NEAREST_ENTRY_DTYPE) if fill is None else np.ascontiguousarray(fill).view(NEAREST_ENTRY_DTYPE).reshape(-1).copy()
+    first, room = _segment_ranges(offsets, cap)
+    dfirst, droom = _segment_ranges(out_offsets, int(out_capacity))
+    for i in range(first.size):
+        c = max(0, min(int(counts[i]), int(room[i]), int(droom[i])))
+        out[dfirst[i]:dfirst[i] + c] = src[first[i]:first[i] + c]
+        out[dfirst[i] + c:dfirst[i] + droom[i]] = empty_entry()
+    return out
+
+
 # ---- capsule queries: the numpy statement of include/hagrid/capsule.h (same operations, same order, same bits) ---------------------------
 
 def _clamp01(x):

@@ -65,7 +65,16 @@
 // A triangle arrives once per cell that references it: one already in the list is dropped; one that fell off the end never comes back,
 // because the last entry only decreases; one of an earlier page is kept out by the cursor order.  Hence: the list for k is a prefix of
 // the list for k + 1, pages concatenated are all candidates sorted, and with k = 1, no cursor and no labels the entry is (d2, id) of Best.
-// There is no count of the ball's content: with pruning at the k-th best the walk never sees the rest.  A full list means "ask again".
+// The k-list has no count of the ball's content: with pruning at the k-th best the walk never sees the rest.  A full list means "ask again" -- or ask RefSink:
+//
+// ---- the whole ball (hagrid_amd.h: hagrid_ball_refs) ------------------------------------------------------------------------------
+// RefSink is the third accumulator: its pruning field d2 is r2 and NEVER MOVES, so one walk sees every candidate (the candidate rule above without a
+// cursor).  It keeps nothing: an accepted offer -- a REFERENCE -- is counted and, while the query's room lasts, handed to a store as (position, d2, id) in walk
+// order.  THE MARGIN holds as it stands: every pruning comparison is `lower bound > r2 * (1 + 2^-10)` with a constant on the right, a sub-block pruned holds
+// nothing within r, a triangle at exactly r2 is never pruned (equality does not satisfy `>`).  What does NOT carry over is "offering a triangle twice changes
+// nothing": a triangle arrives once per visit of a cell that lists it, so R, the number of references, is a property of the grid and the walk (R >= the
+// number of candidates, the set of ids among them IS the candidate set, equal ids carry equal d2 bits).  The sorted, duplicate-free list is one segmented
+// sort away: hagrid/unique_lists.h.
 #ifndef HAGRID_CLOSEST_H
 #define HAGRID_CLOSEST_H
 
@@ -198,6 +207,37 @@ struct NearList {
         HAGRID_UNROLL
         for (int i = 0; i < KMAX; i++)
             if (i == j) { out_id = id[i]; out_d2 = dd[i]; }
+    }
+};
+
+/// Every candidate of one query, as it arrives (the header: "the whole ball").  STORE: store(position, d2, id), called for the first `room` references.
+/// offer / insert are split like NearList's, so that another query shape can offer its own d2 to the same sink.
+template <typename STORE>
+struct RefSink {
+    float d2;                   ///< what the walk prunes with: r2, for the whole walk
+    int count;                  ///< references so far (R when the walk is over)
+    int room;                   ///< references the store takes
+    int label;                  ///< the query's label (< 0: skips nothing)
+    const int* tri_labels;      ///< three labels per triangle, or null
+    STORE store;
+
+    /// before init: the room, the labels (null: none)
+    HOST DEVICE void setup(int slots, int query_label, const int* labels) { room = slots; label = query_label; tri_labels = labels; }
+    HOST DEVICE void init(const vec3&, float r2) { d2 = r2; count = 0; }
+    HOST DEVICE void offer(const Tri& tri, int ref, const vec3& p) {
+        if (tri_labels && label >= 0) {
+            const int* l = tri_labels + 3 * size_t(ref);
+            if (l[0] == label || l[1] == label || l[2] == label) return;
+        }
+        Pair r;
+        if (!point_tri(tri, p, r)) return;
+        insert(r.d2, ref);
+    }
+    /// the candidate (c, ref) of a pair that the labels do not skip
+    HOST DEVICE void insert(const float c, int ref) {
+        if (!(c <= d2)) return;                                                 // NaN, or beyond r2
+        if (count < room) store(count, c, ref);
+        count++;
     }
 };
 

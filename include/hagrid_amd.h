@@ -369,8 +369,8 @@ int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, const void* 
  * Promises: the list for k is a prefix of the list for k + 1; the pages concatenated are the full sorted list of all candidates; the answer is that of the
  * brute force over all triangles (hagrid_amd/scene.py: nearest_tris), and that of the unlabelled query over the scene with the skipped triangles deleted,
  * ids unchanged; with k = 1, no cursor and no labels, entries are (d2, id) of hagrid_closest_points and records its whole 32-byte output, bit for bit.
- * There is NO exact count of the ball's content and no "k + 1 says more": the walk prunes at the k-th best and never sees the rest.  A full list means
- * "ask again".  counters: NULL, or DEVICE int64[5] (8-byte aligned) to which the batch totals are ADDED: queries, cells visited, triangles tested,
+ * THIS entry point has no exact count of the ball's content and no "k + 1 says more": the walk prunes at the k-th best and never sees the rest.  A full list
+ * means "ask again"; the whole ball at once, counted and in CSR form, is hagrid_ball_refs below.  counters: NULL, or DEVICE int64[5] (8-byte aligned) to which the batch totals are ADDED: queries, cells visited, triangles tested,
  * sub-blocks pruned, lists that came back full -- the last one tells a paging caller with one scalar whether another page is needed.
  * Asynchronous on the context's stream; walks the CONSTRUCTION format (include/hagrid/closest.h); the traversal image, ray binning and the
  * hints kept for the nearest-hit path are neither used nor touched.  HAGRID_EINVAL: everything hagrid_closest_points refuses (a released grid, a bad
@@ -380,6 +380,42 @@ int hagrid_closest_points(hagrid_ctx* ctx, const hagrid_grid* grid, const void* 
 int hagrid_nearest_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points, int k,
                         const void* cursors, const void* query_labels, const void* tri_labels, void* entries, void* records,
                         void* counters, uint32_t flags);
+
+/* Extension (no reference counterpart): BALL LISTS -- EVERY triangle within r of each point, sorted, in CSR form, without paging (radius-neighbour lists:
+ * particle-mesh contact, cloth proximity, blending over all neighbours).  Additive: HAGRID_ABI_VERSION stays 3.  The list of query i is the candidates of
+ * hagrid_nearest_tris without a cursor, ALL of them, in the order (d2 ascending, id ascending), d2 point_tri's bits, labels as there; r < 0, a NaN coordinate
+ * or a NaN radius gives an empty list.  Three staged, asynchronous entry points; the caller owns every buffer and both scans (none of them asks for memory):
+ *   hagrid_ball_refs (count) -> exclusive scan -> hagrid_ball_refs (fill) -> hagrid_unique_lists -> exclusive scan -> hagrid_compact_lists.
+ * An entry is 8 bytes {float32 d2; int32 id} as hagrid_nearest_tris'; the EMPTY entry is {+inf, -1}.  A SEGMENT i of a buffer of `capacity` entries is the
+ * slots [offsets[i], offsets[i + 1]) (offsets DEVICE int64[n + 1], 8-byte aligned): its ROOM is the range's length, and 0 if that is negative or the range
+ * leaves [0, capacity] -- the rule of hagrid_list_crossings.  Nothing outside a segment is read or written.
+ *
+ * hagrid_ball_refs: the walk of hagrid_nearest_tris with a bound that stays r2 (include/hagrid/closest.h, "the whole ball").  A REFERENCE of query i is one
+ * accepted offer: a triangle arrives once per visit of a cell that lists it, so R_i, the number of references, is a property of the grid and the walk, not of
+ * the scene; R_i >= m_i, the list's length; the ids among the references are exactly the candidates; equal ids carry equal d2 bits.
+ *   count mode  offsets NULL, entries NULL, capacity 0: counts[i] = R_i (counts DEVICE int32[num_points], 4-byte aligned).
+ *   fill mode   offsets given: the first min(R_i, room) references in walk order, then the EMPTY entry in every slot left over; counts may be NULL.  With
+ *               offsets the exclusive sums of count mode's counts every slot is written exactly once.
+ *   counters    NULL, or DEVICE int64[6] ADDED to: queries, cells visited, triangles tested, sub-blocks pruned, references written, queries with R_i > room
+ *               (count mode adds 0 to the last two).
+ * HAGRID_EINVAL: everything hagrid_nearest_tris refuses of its grid, points, labels and flags; a negative capacity; count mode with entries or a capacity;
+ * count mode without counts; fill mode with entries NULL and capacity > 0; a misaligned buffer.  num_points = 0 is HAGRID_OK.
+ *
+ * hagrid_unique_lists (needs no grid; include/hagrid/unique_lists.h): every segment in place -- entries with id < 0 or a NaN d2 are dropped, the rest sorted
+ * by (d2 by float comparison, id), entries equal in id reduced to one (CONTRACT: equal ids in one segment carry equal d2 bits), the m_i survivors at the front,
+ * EMPTY in every other slot, counts[i] = m_i (DEVICE int32[num_lists]).  counters: NULL, or DEVICE int64[4] ADDED to: lists, slots, survivors, lists sorted
+ * in global memory (longer than the on-chip capacity).
+ * hagrid_compact_lists: copies the first min(counts[i], room of the source, room of the destination) entries of segment i to out_offsets[i] of out_entries
+ * and fills the rest of the destination's room with EMPTY.  counters: NULL, or DEVICE int64[4] ADDED to: lists, entries copied, lists cut short, 0.
+ * Both: HAGRID_EINVAL for a flag, negative num_lists or capacity, NULL offsets or counts, NULL entries with a capacity > 0, a misaligned buffer. */
+int hagrid_ball_refs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* points, int num_points,
+                     const void* query_labels, const void* tri_labels, const void* offsets, void* counts, void* entries,
+                     int64_t capacity, void* counters, uint32_t flags);
+int hagrid_unique_lists(hagrid_ctx* ctx, int num_lists, const void* offsets, void* entries, int64_t capacity, void* counts,
+                        void* counters, uint32_t flags);
+int hagrid_compact_lists(hagrid_ctx* ctx, int num_lists, const void* offsets, const void* entries, int64_t capacity,
+                         const void* counts, const void* out_offsets, void* out_entries, int64_t out_capacity, void* counters,
+                         uint32_t flags);
 
 /* Extension (no reference counterpart): CAPSULE queries -- for every SEGMENT of a batch the k nearest triangles within its radius, nearest first, paged
  * (the edge-edge half of a cloth or rod step's proximity pairs; a character's or a robot link's capsule; "does this cable, or this line of sight, clear
@@ -403,7 +439,7 @@ int hagrid_nearest_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tr
  * Promises: the lists are those of the brute force over all triangles, bit for bit; the list for k is a prefix of the list for k + 1; the pages
  * concatenated are all candidates, sorted; the labelled answer is the unlabelled answer over the scene without the skipped triangles, ids unchanged;
  * with a == b, the first label of each pair set and the second -1, entries and records are hagrid_nearest_tris' for the points (a, r), bit for bit --
- * hence at k = 1 without cursor or labels hagrid_closest_points' output.  There is no exact count of the capsule's content (as hagrid_nearest_tris).
+ * hence at k = 1 without cursor or labels hagrid_closest_points' output.  This entry point has no exact count of the capsule's content (as hagrid_nearest_tris; ball lists are for points).
  * Asynchronous on the context's stream; walks the CONSTRUCTION format (include/hagrid/capsule.h); the traversal image, ray binning and the
  * hints kept for the nearest-hit path are neither used nor touched.  HAGRID_EINVAL and HAGRID_ERANGE (num_segments * k beyond 2^31 - 1): everything
  * hagrid_nearest_tris refuses.  num_segments = 0 is HAGRID_OK (null buffers are then fine). */
