@@ -736,6 +736,110 @@ def tris_in_obbs(grid: Grid, tris, obbs, k: int = MAX_OVERLAP_IDS, query_labels=
     return {"offsets": offsets, "ids": e.contiguous(), "pages": pages, "complete": complete}
 
 
+# ---- overlap lists: ALL of every region query's answer in one pass (hagrid_box_refs, hagrid_tri_refs, hagrid_obb_refs) -------------
+
+def box_refs(grid: Grid, tris: int, boxes: int, n: int, counts: int = 0, offsets: int = 0, entries: int = 0, capacity: int = 0, counters: int = 0):
+    """Extension (hagrid_box_refs): stage 1 of the OVERLAP LISTS for boxes -- the walk of overlap_boxes with a list that keeps nothing.  A REFERENCE is one
+    triangle >= first that meets the box, as the walk meets it; a triangle arrives once per visit of a cell that lists it, so references hold duplicates.
+    Count mode (offsets = 0, entries = 0, capacity = 0): counts[i] (int32[n]) = R_i, the references of box i.  Fill mode: offsets int64[n + 1] -- box i owns
+    the slots [offsets[i], offsets[i + 1]) of `entries` (capacity slots of NEAREST_ENTRY_DTYPE) and writes its first min(R_i, room) references in walk order
+    as (+0.0, id), then the empty entry (+inf, -1); the room rule is list_crossings'.  counters: 0, or a device int64[6] added to (boxes, cells visited,
+    triangle / box tests, sub-blocks pruned, references written, boxes that did not fit).  unique_lists and compact_lists make the lists of it.  Device
+    addresses; asynchronous on the manager's stream.  Walks the construction format: not for a grid given up with release_for_traversal."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_box_refs(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(boxes or 0), int(n), C.c_void_p(offsets or 0), C.c_void_p(counts or 0),
+                                       C.c_void_p(entries or 0), int(capacity), C.c_void_p(counters or 0), 0), "box_refs")
+
+
+def tri_refs(grid: Grid, tris: int, queries: int, n: int, counts: int = 0, offsets: int = 0, entries: int = 0, capacity: int = 0, first: int = 0, query_labels: int = 0,
+             tri_labels: int = 0, counters: int = 0):
+    """Extension (hagrid_tri_refs): stage 1 of the OVERLAP LISTS for contact queries -- box_refs with the queries, first and labels of overlap_tris; the
+    third counter counts the pairs offered to the triangle / triangle test."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_tri_refs(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(queries or 0), int(n), C.c_void_p(first or 0), C.c_void_p(query_labels or 0),
+                                       C.c_void_p(tri_labels or 0), C.c_void_p(offsets or 0), C.c_void_p(counts or 0), C.c_void_p(entries or 0), int(capacity),
+                                       C.c_void_p(counters or 0), 0), "tri_refs")
+
+
+def obb_refs(grid: Grid, tris: int, obbs: int, n: int, counts: int = 0, offsets: int = 0, entries: int = 0, capacity: int = 0, query_labels: int = 0, tri_labels: int = 0,
+             counters: int = 0):
+    """Extension (hagrid_obb_refs): stage 1 of the OVERLAP LISTS for oriented boxes -- box_refs with the records and labels of overlap_obbs; the third counter
+    counts the pairs offered to the box / triangle test."""
+    mem = grid.mem or _current
+    _check(mem, mem._L.hagrid_obb_refs(mem._ctx, C.byref(grid.pod), C.c_void_p(tris or 0), C.c_void_p(obbs or 0), int(n), C.c_void_p(query_labels or 0),
+                                       C.c_void_p(tri_labels or 0), C.c_void_p(offsets or 0), C.c_void_p(counts or 0), C.c_void_p(entries or 0), int(capacity),
+                                       C.c_void_p(counters or 0), 0), "obb_refs")
+
+
+def _label_pair(who: str, ptr, query_labels, tri_labels):
+    """the device addresses of the two label arrays, (0, 0) for none; one without the other is refused here as the entry points refuse it"""
+    if (query_labels is None) != (tri_labels is None):
+        raise HagridError(f"{who}: query_labels and tri_labels are given together or not at all")
+    return (ptr(query_labels), ptr(tri_labels)) if query_labels is not None else (0, 0)
+
+
+def _overlap_lists(mem, n: int, dev, refs_stage) -> dict:
+    """the protocol of ball_lists with refs_stage(counts, offsets, entries, capacity) as stage 1: count, torch.cumsum, fill, unique_lists, torch.cumsum,
+    compact_lists; TWO scalars go to the host (the totals that size the scratch and the output)"""
+    import torch
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    refs_stage(counts.data_ptr(), 0, 0, 0)
+    ref_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum(counts, 0, dtype=torch.int64, out=ref_offsets[1:])
+    refs = int(ref_offsets[-1].item())
+    scratch = torch.empty((refs, 2), dtype=torch.int32, device=dev)
+    refs_stage(0, ref_offsets.data_ptr(), scratch.data_ptr() if refs else 0, refs)
+    unique_lists(n, ref_offsets.data_ptr(), scratch.data_ptr() if refs else 0, refs, counts.data_ptr(), mem=mem)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[-1].item())
+    out = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    compact_lists(n, ref_offsets.data_ptr(), scratch.data_ptr() if refs else 0, refs, counts.data_ptr(), offsets.data_ptr(), out.data_ptr() if total else 0, total, mem=mem)
+    return {"offsets": offsets, "ids": out[:, 1].contiguous(), "refs": refs}
+
+
+def box_lists(grid: Grid, tris, boxes) -> dict:
+    """ALL the triangles that meet every box, ascending by id, in CSR form, WITHOUT paging: box_refs (count), torch.cumsum, box_refs (fill), unique_lists,
+    torch.cumsum, compact_lists on torch tensors; TWO scalars go to the host.  boxes: a float32 tensor (n, 8) on the device (BOX_QUERY_DTYPE rows; `first` is
+    respected); tris: a tensor or a device address.  The manager must run on torch's current stream.  Returns "offsets" int64 (n + 1,), "ids" int32 (total,)
+    -- what scene.box_lists states, and what paging overlap_boxes to the end concatenates to -- and "refs", the total of R_i: the scratch (8 bytes each) a
+    caller of the staged entry points needs.  Linear in the list where paging is quadratic."""
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    rec = boxes.reshape(-1, 8)
+    n = int(rec.shape[0])
+    return _overlap_lists(grid.mem or _current, n, rec.device,
+                          lambda counts, offsets, entries, capacity: box_refs(grid, ptr(tris), rec.data_ptr(), n, counts=counts, offsets=offsets, entries=entries, capacity=capacity))
+
+
+def contact_lists(grid: Grid, tris, queries, first=None, query_labels=None, tri_labels=None) -> dict:
+    """ALL the scene triangles every query triangle touches, ascending by id, in CSR form, WITHOUT paging: the protocol of box_lists over tri_refs.  queries: a
+    float32 tensor (n, 12) on the device (may be the scene's own array); first ((n,) int32), query_labels ((n, 3) int32) and tri_labels ((N, 3) int32): torch
+    tensors on the device or None, the labels both or neither (tris and tri_labels may be device addresses).  Returns what box_lists returns; what
+    scene.contact_lists states.  contact_lists(grid, tris, tris, first=arange(1, N + 1), query_labels=labels, tri_labels=labels) gives ALL self-intersections
+    of a mesh, each pair once, at its smaller id -- self_intersections without the bound k."""
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    rec = queries.reshape(-1, 12)
+    n = int(rec.shape[0])
+    ql, tl = _label_pair("contact_lists", ptr, query_labels, tri_labels)
+    return _overlap_lists(grid.mem or _current, n, rec.device,
+                          lambda counts, offsets, entries, capacity: tri_refs(grid, ptr(tris), rec.data_ptr(), n, counts=counts, offsets=offsets, entries=entries, capacity=capacity,
+                                                                              first=ptr(first) if first is not None else 0, query_labels=ql, tri_labels=tl))
+
+
+def obb_lists(grid: Grid, tris, obbs, query_labels=None, tri_labels=None) -> dict:
+    """ALL the triangles that meet every oriented box, ascending by id, in CSR form, WITHOUT paging: the protocol of box_lists over obb_refs.  Arguments as
+    tris_in_obbs, whose "offsets" and "ids" these are; what scene.obb_lists states."""
+    ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+    rec = obbs.reshape(-1, 16)
+    n = int(rec.shape[0])
+    ql, tl = _label_pair("obb_lists", ptr, query_labels, tri_labels)
+    return _overlap_lists(grid.mem or _current, n, rec.device,
+                          lambda counts, offsets, entries, capacity: obb_refs(grid, ptr(tris), rec.data_ptr(), n, counts=counts, offsets=offsets, entries=entries, capacity=capacity,
+                                                                              query_labels=ql, tri_labels=tl))
+
+
 INSIDE_WINDING = 1       # HAGRID_INSIDE_WINDING
 
 
@@ -1129,6 +1233,6 @@ __all__ = ["MemManager", "Grid", "build_grid", "merge_grid", "flatten_grid", "ex
            "frame_workspace_layout", "render_frame", "SHADE_DEPTH", "SHADE_GRAY", "SHADE_HEAT", "BOUNCE_REDRAW_MISSES",
            "traverse_grid_multi", "shade_layers", "MAX_HITS", "MeshScene",
            "traverse_grid_filtered", "skip_filters", "RAY_MASK_ALL",
-           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "ball_refs", "unique_lists", "compact_lists", "ball_lists", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "segment_tris", "tris_near_segments", "SEGMENT_DTYPE", "SEGMENT_RECORD_DTYPE", "overlap_boxes", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
+           "closest_points", "POINT_QUERY_DTYPE", "CLOSEST_DTYPE", "nearest_tris", "tris_within", "ball_refs", "unique_lists", "compact_lists", "ball_lists", "MAX_NEAREST", "NEAREST_ENTRY_DTYPE", "segment_tris", "tris_near_segments", "SEGMENT_DTYPE", "SEGMENT_RECORD_DTYPE", "overlap_boxes", "box_refs", "tri_refs", "obb_refs", "box_lists", "contact_lists", "obb_lists", "voxelize", "BOX_QUERY_DTYPE", "MAX_OVERLAP_IDS", "OVERLAP_ANY",
            "overlap_tris", "self_intersections", "overlap_obbs", "obb_records", "tris_in_obbs", "OBB_DTYPE",
            "count_crossings", "list_crossings", "crossing_lists", "points_inside", "inside_lattice", "fill_lattice", "solid_voxels", "INSIDE_WINDING"]

@@ -216,9 +216,9 @@ __global__ void __launch_bounds__(kBlock) overlap_step(ExpandK k, const Entry* _
 constexpr int kSelectItems = 16;                      // cells per thread
 constexpr int kSelectTile = kBlock * kSelectItems;    // cells per workgroup
 
-template <int axis>
+// (the axis is an argument, uniform over the launch: the three passes differ in this one mask -- one kernel, not three; the product library's kernel budget)
 __global__ void __launch_bounds__(kBlock) expand_select(const Cell* __restrict__ cells, Cell* __restrict__ new_cells, unsigned char* __restrict__ cell_flags,
-                                                        int num_cells, int* __restrict__ list, int* __restrict__ count) {
+                                                        int num_cells, int* __restrict__ list, int* __restrict__ count, int axis) {
     __shared__ int tile_list[kSelectTile];
     __shared__ int tile_count, tile_base;
     if (threadIdx.x == 0) tile_count = 0;
@@ -272,7 +272,7 @@ __global__ void __launch_bounds__(kBlock) expand_listed(ExpandK k, const Entry* 
 template <int axis, bool SUBSET_ONLY>
 void listed_step(hipStream_t st, const ExpandK& k, const Entry* entries, const int* refs, const float4* tris, const Cell* cells, Cell* other,
                  unsigned char* flags, int n, int* list, int* count) {
-    expand_select<axis><<<grid_blocks(n, kSelectTile), kBlock, 0, st>>>(cells, other, flags, n, list, count);
+    expand_select<<<grid_blocks(n, kSelectTile), kBlock, 0, st>>>(cells, other, flags, n, list, count, axis);
     expand_listed<axis, SUBSET_ONLY><<<grid_blocks(2ll * n, kBlock), kBlock, 0, st>>>(k, entries, refs, tris, cells, other, flags, list, count);
 }
 

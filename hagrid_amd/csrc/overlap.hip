@@ -17,12 +17,10 @@
 // rolled loops; the kernel is compiled for four wavefronts per SIMD (amdgpu_waves_per_eu), which the allocator meets with 128 VGPRs and no scratch.
 //
 // ORIENTED BOXES (hagrid_overlap_obbs, DESIGN.md 4.16, include/hagrid/obb.h) have a kernel of their own further down, obb_tris_kernel: the one above has no
-// register left for a third mode.
-#include "trav_common.h"
+// register left for a third mode.  The accessors the kernels read grid and queries through (OverlapGrid, DevQuery, DevFilter, DevObb) are overlap_dev.h's,
+// shared with overlap_lists.hip.
+#include "overlap_dev.h"
 #include "wave_prims.h"
-
-#include "hagrid/obb.h"
-#include "hagrid/overlap.h"
 
 #include <string>
 
@@ -34,9 +32,6 @@ namespace ho = hagrid::overlap;
 namespace hb = hagrid::obb;
 
 namespace {
-
-// the accessor of overlap.h: the grid and the clip box
-struct OverlapGrid : DevGrid { ho::Clip clip; };
 
 struct OverlapArgs {
     const float4* __restrict__ boxes;        // null: the lattice form
@@ -50,27 +45,6 @@ struct OverlapArgs {
     int n, k, any;
     float ox, oy, oz, sx, sy, sz;            // lattice: origin, voxel size
     int nx, ny;                              // lattice: voxels along x and y (x fastest)
-};
-
-// the query of overlap.h's TriFilter for one lane: the record and the labels are read again for every candidate that has met the box -- few do, the
-// lines stay in the vector L1, and nothing of the query but the box is live across the walk
-struct DevQuery {
-    const float4* __restrict__ queries;      // the launch's arrays (uniform) and this lane's query: addresses are formed where they are used
-    const int* __restrict__ labels;          // of the queries, or null
-    const int* __restrict__ tri_labels;
-    int i;
-    __device__ __forceinline__ Tri tri() const { return load_tri(queries, i); }
-    __device__ __forceinline__ bool labelled() const { return labels != nullptr; }
-    __device__ __forceinline__ int label(int j) const { return labels[3 * size_t(i) + j]; }
-    __device__ __forceinline__ int tri_label(int id, int j) const { return tri_labels[3 * size_t(id) + j]; }
-};
-
-// the pair filter of the launch: nothing for boxes, TriFilter for the contact form (uniform over the launch)
-struct DevFilter {
-    ho::TriFilter<DevQuery> f;
-    bool on;
-    __device__ __forceinline__ bool counts_box_tests() const { return !on; }
-    __device__ __forceinline__ bool accept(int id, const Tri& t, int& tests) const { return !on || f.accept(id, t, tests); }
 };
 
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) overlap_boxes_kernel(const OverlapGrid g, const OverlapArgs a) {
@@ -162,30 +136,6 @@ struct ObbArgs {
     int* __restrict__ counts;                // may be null
     unsigned long long* __restrict__ counters;   // may be null
     int n, k, any;
-};
-
-__device__ __forceinline__ hb::Obb load_obb(const float4* __restrict__ obbs, int i) {
-    const float4* p = obbs + 4 * size_t(i);
-    const float4 c = p[0], u = p[1], v = p[2], w = p[3];
-    hb::Obb b;
-    b.c = vec3(c.x, c.y, c.z); b.u = vec3(u.x, u.y, u.z); b.v = vec3(v.x, v.y, v.z); b.w = vec3(w.x, w.y, w.z);
-    return b;
-}
-
-// the query of obb.h's ObbFilter for one lane
-struct DevObb {
-    const float4* __restrict__ obbs;
-    const int* __restrict__ labels;          // of the queries, or null
-    const int* __restrict__ tri_labels;
-    int i;
-    __device__ __forceinline__ hb::Obb box() const {
-        int j = i;
-        HAGRID_MADE_HERE(j);                  // the record is read HERE, at every use: no load of it is moved ahead of the walk's loops and kept
-        return load_obb(obbs, j);
-    }
-    __device__ __forceinline__ bool labelled() const { return labels != nullptr; }
-    __device__ __forceinline__ int label() const { return labels[i]; }
-    __device__ __forceinline__ int tri_label(int id, int j) const { return tri_labels[3 * size_t(id) + j]; }
 };
 
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) obb_tris_kernel(const OverlapGrid g, const ObbArgs a) {

@@ -147,6 +147,9 @@ SIGNATURES = {
     "hagrid_overlap_lattice": (_i32, [_vp, C.POINTER(GridPOD), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int), _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_tris": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.c_uint32]),
     "hagrid_overlap_obbs": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, C.c_uint32]),
+    "hagrid_box_refs": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, C.c_uint32]),
+    "hagrid_tri_refs": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_uint32]),
+    "hagrid_obb_refs": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.c_uint32]),
     "hagrid_count_crossings": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _vp, _i32, _vp, C.c_uint32]),
     "hagrid_list_crossings": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, C.c_uint32]),
     "hagrid_points_inside": (_i32, [_vp, C.POINTER(GridPOD), _vp, _vp, _i32, C.POINTER(C.c_float), _i32, _vp, _vp, _vp, C.c_uint32]),

@@ -1397,6 +1397,80 @@ def overlap_obbs(tris: np.ndarray, obbs: np.ndarray, k: int = 8, query_labels=No
     return {"ids": ids, "counts": np.minimum(sizes, k + 1).astype(np.int32), "sizes": sizes}
 
 
+# ---- overlap lists: ALL of S for every region query (hagrid_box_refs, hagrid_tri_refs, hagrid_obb_refs then unique and compact) --------
+
+def _region_lists(T: np.ndarray, B: np.ndarray, first, needs_surface: bool, pair_filter, chunk_pairs: int) -> dict:
+    """Every triangle j >= first[i] that meets the clipped box B[i] (overlap_pairs) and passes pair_filter(query rows, triangle ids) -> bool, per query
+    ascending by id, in CSR form.  Pairs whose bounding intervals miss each other are left out before the tests: the triangle / box test says the same."""
+    n, N = B.shape[0], T.shape[0]
+    sizes = np.zeros(n, dtype=np.int64); chunks = []
+    with np.errstate(all="ignore"):
+        V = tri_vertices(T)
+        tmin = np.fmin(V[:, 0], np.fmin(V[:, 1], V[:, 2])); tmax = np.fmax(V[:, 0], np.fmax(V[:, 1], V[:, 2]))
+        surface = tris_have_surface(T) if needs_surface else np.ones(N, dtype=bool)
+        tid = np.arange(N, dtype=np.int64)[None, :]
+        m = max(1, chunk_pairs // max(N, 1))
+        for o in range(0, n if N else 0, m):
+            b = B[o:o + m]
+            active = (b[:, 0:3] <= b[:, 4:7]).all(axis=1)
+            near = ~((tmin[None, :, :] > b[:, None, 4:7]) | (tmax[None, :, :] < b[:, None, 0:3])).any(axis=2)      # the bounds check of the triangle / box test
+            near &= active[:, None] & surface[None, :] & (tid >= first[o:o + m, None])
+            rows, col = np.nonzero(near)                       # by row, then by id ascending
+            keep = overlap_pairs(T[col], b[rows])
+            rows, col = rows[keep], col[keep]
+            keep = pair_filter(o + rows, col)
+            rows, col = rows[keep], col[keep]
+            sizes[o:o + b.shape[0]] = np.bincount(rows, minlength=b.shape[0])
+            chunks.append(col.astype(np.int32))
+    offsets = np.zeros(n + 1, dtype=np.int64); np.cumsum(sizes, out=offsets[1:])
+    return {"offsets": offsets, "ids": np.concatenate(chunks) if chunks else np.zeros(0, np.int32)}
+
+
+def box_lists(tris: np.ndarray, boxes: np.ndarray, grid=None, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of the box lists (hagrid_box_refs, then hagrid_unique_lists and hagrid_compact_lists): ALL of the set S that overlap_boxes defines --
+    `first`, the clip and overlap_pairs as there -- for every box, ascending by id: "offsets" int64 (n + 1,), "ids" int32 (total,).  What the pages of the
+    k-list concatenate to; overlap_boxes' "sizes" are the list lengths, its "ids" the lists' first k."""
+    glo, ghi = grid_box(tris) if grid is None else grid
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); B = clip_boxes(boxes, glo, ghi)
+    return _region_lists(T, B, B[:, 3].view(np.int32).astype(np.int64), False, lambda rows, col: np.ones(rows.size, dtype=bool), chunk_pairs)
+
+
+def contact_lists(tris: np.ndarray, queries: np.ndarray, first=None, query_labels=None, tri_labels=None, grid=None, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of the contact lists (hagrid_tri_refs ...): ALL of the set S that overlap_tris defines -- first, labels, surface, the grown and clipped
+    query box, tri_tri_pairs as there -- for every query, ascending by id, in CSR form as box_lists."""
+    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
+    glo, ghi = grid_box(tris) if grid is None else grid
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); Q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 12)
+    B = clip_boxes(query_boxes(Q, glo, ghi), glo, ghi)
+    first = np.zeros(Q.shape[0], np.int64) if first is None else np.asarray(first).astype(np.int64)
+
+    def pair(rows, col):
+        keep = np.ones(rows.size, dtype=bool)
+        if query_labels is not None:
+            keep = ~labels_shared(np.asarray(query_labels).reshape(-1, 3)[rows], np.asarray(tri_labels).reshape(-1, 3)[col])
+        keep[keep] = tri_tri_pairs(Q[rows[keep]], T[col[keep]])
+        return keep
+    return _region_lists(T, B, first, True, pair, chunk_pairs)
+
+
+def obb_lists(tris: np.ndarray, obbs: np.ndarray, query_labels=None, tri_labels=None, grid=None, chunk_pairs: int = 1 << 21) -> dict:
+    """The definition of the oriented-box lists (hagrid_obb_refs ...): ALL of the set S that overlap_obbs defines -- `first`, the label, surface, the grown and
+    clipped bounding box, obb_pairs as there -- for every box, ascending by id, in CSR form as box_lists."""
+    assert (query_labels is None) == (tri_labels is None), "query_labels and tri_labels are given together or not at all"
+    glo, ghi = grid_box(tris) if grid is None else grid
+    T = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12); O = _obb_rows(obbs)
+    B = clip_boxes(obb_boxes(O, glo, ghi), glo, ghi)
+
+    def pair(rows, col):
+        keep = np.ones(rows.size, dtype=bool)
+        if query_labels is not None:
+            ql = np.asarray(query_labels, np.int32).reshape(-1)[rows]
+            keep = ~((ql >= 0)[:, None] & (ql[:, None] == np.asarray(tri_labels, np.int32).reshape(-1, 3)[col])).any(axis=1)
+        keep[keep] = obb_pairs(T[col[keep]], O[rows[keep]])
+        return keep
+    return _region_lists(T, B, O[:, 3].view(np.int32).astype(np.int64), True, pair, chunk_pairs)
+
+
 # ---- crossing queries: the numpy statement of include/hagrid/crossings.h (same operations, same order, same bits) ---------------------------
 
 INSIDE_WINDING = 1

@@ -14,10 +14,14 @@
 // A box record is 32 bytes, the layout of BBox: min.xyz, int32 `first` (the pad slot after min), max.xyz, pad 0.  With
 // S = {j >= first : j meets the box}, m = |S| and 1 <= k <= 8 the answer is the min(k, m) smallest ids of S, ascending, in k slots (unused
 // slots -1), and count = min(m, k + 1): k + 1 says "there are more".  So the list for k is a prefix of the list for k + 1, and a caller
-// pages through S by asking again with first = last id + 1.  A full, variable-length list is NOT offered: a triangle is referenced by
-// several cells, the build inserts by the separating-axis test and not by the bounding box (so no cell is the canonical owner of a
-// triangle inside a box), and expanded cell boxes overlap -- an exact list would need de-duplication across cells.  "The k smallest ids"
-// does not care how often a triangle is offered.
+// pages through S by asking again with first = last id + 1.  "The k smallest ids" does not care how often a triangle is offered.
+//   * ALL of S (hagrid_amd.h: hagrid_box_refs, hagrid_tri_refs, hagrid_obb_refs) comes from the same walk with a third list type, RefList,
+//     which keeps nothing: every triangle that `wants` lets through and that meets the box is a REFERENCE -- counted and, while the query's room lasts,
+//     handed to a store in walk order.  THE DUPLICATE MODEL: a triangle is referenced by several cells, the build inserts by the separating-axis test and
+//     not by the bounding box (so no cell is the canonical owner of a triangle inside a box), and expanded cell boxes overlap -- a triangle arrives once
+//     per visit of a cell that lists it, and only the cell tested last is recognised.  So R, the number of references of a query, is a property of the
+//     grid and the walk; R >= m, and the set of ids among the references is exactly S.  The sorted, duplicate-free list -- the pages of the k-list
+//     concatenated -- is one segmented sort away (hagrid/unique_lists.h): a reference is stored as the entry {+0.0f, id}, so that sort orders by id alone.
 //   * an INACTIVE box -- a NaN bound, or min > max on an axis -- has count 0, ids -1 and takes no walk;
 //   * a box with min == max is a point and gets whatever the test says;
 //   * THE CLIP: the query runs over a grid, and before anything else the box is clipped to the grid box grown by eps = GridConsts::abs_margin
@@ -160,6 +164,24 @@ struct IdList {
         HAGRID_UNROLL
         for (int j = 0; j < KMAX; j++) c += (j < cap && id[j] >= 0) ? 1 : 0;
         return c;
+    }
+};
+
+/// Every member of S as it arrives, duplicates included (the header: THE DUPLICATE MODEL).  STORE: store(position, id), called for the first `room`
+/// references.  Never "found": a walk with this list runs to its end (there is no ANY).
+template <typename STORE>
+struct RefList {
+    int count;          ///< references so far (R when the walk is over)
+    int room;           ///< references the store takes
+    int first;          ///< only ids >= first take part
+    STORE store;
+
+    HOST DEVICE void init(int first_) { first = first_; count = 0; }
+    HOST DEVICE bool found() const { return false; }
+    HOST DEVICE bool wants(int ref) const { return ref >= first; }
+    HOST DEVICE void take(int ref) {
+        if (count < room) store(count, ref);
+        count++;
     }
 };
 

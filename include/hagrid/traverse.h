@@ -104,6 +104,26 @@ inline void overlap_obbs(const Grid& grid, const Tri* tris, const void* obbs, in
     detail::check(detail::current_ctx(), hagrid_overlap_obbs(detail::current_ctx(), &p, tris, obbs, num_obbs, query_labels, tri_labels, k, ids, counts, counters,
                                                              any ? HAGRID_OVERLAP_ANY : 0u));
 }
+/// Extension: overlap lists, stage 1 (hagrid_amd.h: hagrid_box_refs, hagrid_tri_refs, hagrid_obb_refs; the list type and the duplicate model: overlap.h).  Records
+/// and labels as for overlap_boxes, overlap_tris and overlap_obbs.  offsets nullptr: count mode, counts[i] = the references of query i; else fill mode: the
+/// references as entries {+0.0f, id} into [offsets[i], offsets[i + 1]) of `entries` (capacity slots of 8 bytes).  counters: nullptr or int64[6] -- all DEVICE
+/// pointers.  hagrid_unique_lists and hagrid_compact_lists make the sorted lists of them.  Asynchronous on the context's stream.
+inline void box_refs(const Grid& grid, const Tri* tris, const BBox* boxes, int num_boxes, int* counts, const long long* offsets = nullptr, void* entries = nullptr, int64_t capacity = 0,
+                     void* counters = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_box_refs(detail::current_ctx(), &p, tris, boxes, num_boxes, offsets, counts, entries, capacity, counters, 0u));
+}
+inline void tri_refs(const Grid& grid, const Tri* tris, const Tri* queries, int num_queries, int* counts, const long long* offsets = nullptr, void* entries = nullptr, int64_t capacity = 0,
+                     void* counters = nullptr, const int* first = nullptr, const int* query_labels = nullptr, const int* tri_labels = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_tri_refs(detail::current_ctx(), &p, tris, queries, num_queries, first, query_labels, tri_labels, offsets, counts, entries, capacity,
+                                                         counters, 0u));
+}
+inline void obb_refs(const Grid& grid, const Tri* tris, const void* obbs, int num_obbs, int* counts, const long long* offsets = nullptr, void* entries = nullptr, int64_t capacity = 0,
+                     void* counters = nullptr, const int* query_labels = nullptr, const int* tri_labels = nullptr) {
+    hagrid_grid p = detail::to_pod(grid);
+    detail::check(detail::current_ctx(), hagrid_obb_refs(detail::current_ctx(), &p, tris, obbs, num_obbs, query_labels, tri_labels, offsets, counts, entries, capacity, counters, 0u));
+}
 
 /// Extension: crossing queries (hagrid_amd.h: hagrid_count_crossings, hagrid_list_crossings, hagrid_points_inside, hagrid_inside_lattice, hagrid_fill_lattice; the record, the paging and the walk:
 /// crossings.h).  records: num_rays Hit-shaped records (count, t_first, length, winding bits); counters: nullptr or int64[4] -- DEVICE pointers.  Asynchronous.

@@ -455,8 +455,8 @@ int hagrid_segment_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tr
  * With S_i = {j >= first : j meets box i}, m = |S_i| and 1 <= k <= HAGRID_MAX_OVERLAP_IDS:
  *   ids[i*k .. i*k + k-1]  (int32) the min(k, m) smallest ids of S_i, ascending; unused slots -1;
  *   counts[i]              (int32, counts may be NULL) min(m, k + 1): k + 1 says "there are more".
- * So the list for k is a prefix of the list for k + 1, and a caller pages through S_i with first = last id + 1.  Variable-length lists and exact counts
- * above k + 1 are not offered (a triangle is referenced by several cells; include/hagrid/overlap.h).  An INACTIVE box -- a NaN bound, or
+ * So the list for k is a prefix of the list for k + 1, and a caller pages through S_i with first = last id + 1.  The whole of S_i at once, counted and in CSR
+ * form, is hagrid_box_refs below (a triangle is referenced by several cells; include/hagrid/overlap.h).  An INACTIVE box -- a NaN bound, or
  * min > max on an axis -- has count 0 and ids -1; a box with min == max is a point.  Before the test every box is CLIPPED to the grid box grown
  * by 2^-16 of its largest |coordinate| (no triangle lies outside the grid box, so nothing is lost; a box inside keeps its bits): infinite and huge bounds
  * are legal and mean "no bound on this side", and a box beyond the grid meets nothing.  flags: 0 or HAGRID_OVERLAP_ANY (k must be 1): the walk stops at the first triangle that meets the box; ids[i] is SOME member of S_i or -1,
@@ -513,6 +513,37 @@ int hagrid_overlap_tris(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tr
  * (records 16-byte aligned, labels 4), and one label array without the other.  num_obbs = 0 is HAGRID_OK. */
 int hagrid_overlap_obbs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* obbs, int num_obbs, const void* query_labels,
                         const void* tri_labels, int k, void* ids, void* counts, void* counters, uint32_t flags);
+
+/* Extension (no reference counterpart): OVERLAP LISTS -- EVERY triangle that meets each box, contact query or oriented box, ascending by id, in CSR form,
+ * without paging (all contact pairs between two meshes, all self-intersections, everything inside a rigid body's box).  Additive: HAGRID_ABI_VERSION stays 3.
+ * For query i the set S_i is EXACTLY the one hagrid_overlap_boxes, hagrid_overlap_tris and hagrid_overlap_obbs define -- `first`, the clip to the grown grid
+ * box, the pair tests, labels, inactive queries (the empty list) as there -- and the list is ALL of S_i, ascending: what the pages of the k-list concatenate
+ * to.  There is no k and no HAGRID_OVERLAP_ANY: flags must be 0.  The protocol is the ball lists', with one of these three as stage 1:
+ *   hagrid_*_refs (count) -> exclusive scan -> hagrid_*_refs (fill) -> hagrid_unique_lists -> exclusive scan -> hagrid_compact_lists;
+ * the caller owns every buffer and both scans, and none of the three asks for memory.  A REFERENCE of query i is one member of S_i as the walk meets it: a
+ * triangle arrives once per visit of a cell that lists it and only the cell tested last is recognised (include/hagrid/overlap.h, THE DUPLICATE MODEL), so
+ * R_i, the number of references, is a property of the grid and the walk; R_i >= m_i = |S_i|; the set of ids among the references is exactly S_i.  Stage 1
+ * writes the 8-byte entry {+0.0f, id}: the distance word is a constant, so hagrid_unique_lists sorts by id alone and its contract (equal ids carry equal d2
+ * bits) holds trivially; the EMPTY entry stays {+inf, -1}.  Segments, their room and the two modes are hagrid_ball_refs':
+ *   count mode  offsets NULL, entries NULL, capacity 0: counts[i] = R_i (counts DEVICE int32[n], 4-byte aligned).
+ *   fill mode   offsets given (DEVICE int64[n + 1]): the first min(R_i, room) references in walk order, then the EMPTY entry in every slot of the segment that
+ *               is left; nothing outside the segment is written; counts may be NULL.
+ *   counters    NULL, or DEVICE int64[6] ADDED to: queries, cells visited, tests evaluated (the meaning of the third total of the k-list query of the same
+ *               shape), sub-blocks pruned, references written, queries with R_i > room (count mode adds 0 to the last two).
+ * Records, alignment and label rules: hagrid_box_refs takes the boxes of hagrid_overlap_boxes (`first` in the record's pad slot), hagrid_tri_refs the queries,
+ * first and labels of hagrid_overlap_tris, hagrid_obb_refs the records (`first` in the pad slot) and labels of hagrid_overlap_obbs.  The lattice form is left
+ * out: scene.lattice_boxes gives the same boxes explicitly.  HAGRID_EINVAL: what the k-list query of the same shape refuses of its grid, records and labels,
+ * and what hagrid_ball_refs refuses: any flag, a negative capacity, count mode with entries or a capacity, count mode without counts, fill mode with entries
+ * NULL and capacity > 0, a misaligned buffer.  n = 0 is HAGRID_OK.  Asynchronous on the context's stream; the CONSTRUCTION format is walked; the traversal
+ * image, ray binning and the hints kept for the nearest-hit path are neither used nor touched (hagrid_amd/csrc/overlap_lists.hip). */
+int hagrid_box_refs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* boxes, int num_boxes,
+                    const void* offsets, void* counts, void* entries, int64_t capacity, void* counters, uint32_t flags);
+int hagrid_tri_refs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* queries, int num_queries, const void* first,
+                    const void* query_labels, const void* tri_labels, const void* offsets, void* counts, void* entries,
+                    int64_t capacity, void* counters, uint32_t flags);
+int hagrid_obb_refs(hagrid_ctx* ctx, const hagrid_grid* grid, const void* tris, const void* obbs, int num_obbs,
+                    const void* query_labels, const void* tri_labels, const void* offsets, void* counts, void* entries,
+                    int64_t capacity, void* counters, uint32_t flags);
 
 /* Extension (no reference counterpart): CROSSING queries -- ALL the surfaces a ray crosses, and from that whether a point lies inside a closed surface
  * (thickness and path length through a solid, signed distance = hagrid_closest_points + inside, solid voxelization = hagrid_overlap_lattice + inside;
